@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — scan-pair registrations/sec of the MI355X Stein-ICP path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload C3]
+    python bench.py --gpus N --steps K --warmup W [--workload C3] [--dump-outputs DIR] [--full]
 
 A *step* is one full registration of one synthetic 64-beam scan pair through the C ABI:
 add_cloud (device→device copy of the resident clouds + particle reset) → set_initial_mean →
@@ -14,13 +14,17 @@ N > 1 runs BASELINE configuration C4 — 512 particles FIXED — with the SOURCE
 (`--split rows`, the default: every GPU searches and accumulates its rows for all particles, one all-gather
 of N × P × 176 B partial sums per iteration over RCCL; `--split particles` is the 512/N-particles-per-GPU
 layout) — so `value` is the raw registrations/s of the same 512-particle registration at every N
-(`"scaling": "strong"`).  Next to it the line carries
+(`"scaling": "strong"`).  With --full the line carries next to it
 `speedup_vs_1gpu` (rank 0 times the unsharded 512-particle registration on its own GPU in the same
 invocation, outside the timed region) and a `weak_scaling` record (C3 clouds, 128 particles per GPU,
-raw registrations/s).  The N = 1 line carries the one-GPU C4 rate as `c4_one_gpu` so that the
+raw registrations/s), and the N = 1 line carries the one-GPU C4 rate as `c4_one_gpu` so that the
 strong-scaling curve has its first point.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step and the workload description).  --dump-outputs DIR writes what
+the last timed step returned (state, mean, covariance; particles and weights of the solver after it) as DIR/<name>.npy in
+float64; the inputs are the same seeded clouds and particles in every run.  --full adds the records that take runs of
+their own:
   roofline      — the dominant kernel (k_stein_search_bf16 at C3): algorithmic flops of the reference's brute
                   force per launch time against the f32 matrix/vector peak, from live hipEvent timings on the
                   library's stream; roofline_hbm is the HBM view of the same kernel,
@@ -67,7 +71,22 @@ def parse():
     ap.add_argument("--mode", default="svn", choices=("svn", "svgd"), help="svn (headline) | svgd (first-order sibling, N = 1)")
     ap.add_argument("--split", default="rows", choices=("rows", "particles"),
                     help="N > 1: what is cut across the GPUs — source rows (default: nothing of size [B] replicated) or particles")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side records: roofline pass, CPU baselines, other configurations and precisions, "
+                         "scaling references")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, last, solver):
+    """What a caller of the timed path receives from its last step, plus the particle set the solver holds after it."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"state": np.array([int(last["state"])], np.float64),
+              "transformation": last["mean"], "cov_matrix": last["cov"],
+              "particles": solver.get_particles(), "particle_weight": solver.get_particle_weight()}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, np.float64))
 
 
 def time_steps(step, n, world, dist, torch, dev):
@@ -156,15 +175,17 @@ def main():
 
     def timed_step():
         st, mean, cov = step()
-        last["mean"] = mean
+        last["state"], last["mean"], last["cov"] = st, mean, cov
     # the timed region: exactly K steps of the product as a caller runs it — no event brackets, no profiling hooks
     el = time_steps(timed_step, a.steps, world, dist, torch, dev)
     mean = last["mean"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, solver)
 
     # roofline region: the SAME K steps once more, every kernel launch bracketed by hipEvents on the library's stream
     # (svnicp_set_profile; ~5 us of stream time per bracket, which is why this pass is not the one `value` comes from)
     kernel_ms = {}
-    if world == 1 and not a.no_profile:
+    if a.full and world == 1 and not a.no_profile:
         solver.set_profile(True)
         for _ in range(a.steps):
             step()
@@ -204,7 +225,7 @@ def main():
     }
 
     nside = max(2, min(5, a.steps))
-    if world > 1:
+    if a.full and world > 1:
         # strong-scaling reference: the same 512-particle registration, unsharded, on rank 0's GPU (others wait)
         one = None
         if rank == 0:
@@ -302,7 +323,7 @@ def main():
                                             "this is an effective rate, not an instruction count"}
         out["kernels"] = details
 
-    if world == 1 and not svgd and wl == "C3":
+    if a.full and world == 1 and not svgd and wl == "C3":
         # side records (few untimed-region steps each): SVNFullGrad = true, the one-GPU point of the C4 strong-scaling curve,
         # and the host cost of the multi-GPU driver (ShardedSVNICP at world size 1 against svnicp_align)
         solver.set_profile(False)
@@ -370,7 +391,7 @@ def main():
         out["sharded_driver_world1"] = {"ms_per_step": 1e3 * es_ / nside, "svnicp_align_ms_per_step": 1e3 * ep / nside,
                                         "host_overhead_ms": 1e3 * (es_ - ep) / nside}
 
-    if rank == 0 and world == 1 and a.cpu_sample != 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_sample != 0:
         orc = graft.load_oracle()
         Bs = B if a.cpu_sample < 0 else min(a.cpu_sample, B)
         rows = np.linspace(0, B - 1, Bs).astype(np.int64)      # evenly spaced over the scan, not its first beams
@@ -392,7 +413,7 @@ def main():
         if Bs == B:
             out["cpu_baseline"]["max_abs_pose_diff_vs_gpu"] = float(np.abs(op - mean).max())
 
-    if rank == 0 and world == 1 and a.cpu_sample != 0 and not svgd and wl == "C3":
+    if a.full and rank == 0 and world == 1 and a.cpu_sample != 0 and not svgd and wl == "C3":
         # BASELINE.json configs[0] is "the reference CPU path": the reference's solver is a libtorch tensor program, and
         # oracle/torch_restatement.py replays it op for op through the same ATen kernels (einsum / bmm / linalg_solve / median
         # on CPU, float64).  Timed here at C1 on this box's host cores beside the GPU's C1 registration (bounded: ~1-3 s).

@@ -1,5 +1,6 @@
-"""CPU tests of the oracle itself: pinned against the reference's own knn_cpu.cpp (oracle/_ref),
-cross-checked against the op-for-op libtorch restatement, and against the committed golden vectors."""
+"""CPU tests of the oracle itself: pinned against the reference's own knn_cpu.cpp (its outputs stored under
+tests/golden/knn_ref, and live through oracle/_ref where that is built), cross-checked against the op-for-op libtorch
+restatement, and against the committed golden vectors."""
 import os
 import sys
 
@@ -11,9 +12,19 @@ from conftest import so3_exp_np
 
 
 # ---------------------------------------------------------------- KNN stage: pinned by the reference
-def _grid_cloud(n, seed, span=6):
-    rng = np.random.default_rng(seed)
-    return rng.integers(-span, span + 1, size=(n, 3)).astype(np.float64)
+KNN_REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "knn_ref", "knn_cpu_ref.npz")
+
+
+def _reference_knn(orc, case):
+    """Inputs and outputs of the reference's float32 KNearestNeighborIdxCpu (unmodified, oracle/_ref) for one case, as
+    stored by tests/golden/make_knn_ref.py.  Where oracle/_ref is built, the live call must reproduce them bit for bit."""
+    g = np.load(KNN_REF, allow_pickle=False)
+    q, t, K = g[case + "_q"], g[case + "_t"], int(g[case + "_k"])
+    ri, rd = g[case + "_idx"], g[case + "_d2"]
+    if orc.ref_available():
+        li, ld = orc.ref_knn_cpu_f32(q, t, K)
+        assert np.array_equal(li, ri) and np.array_equal(ld, rd), "oracle/_ref no longer gives the stored outputs"
+    return q, t, K, ri, rd
 
 
 @pytest.mark.parametrize("B,M,K", [(40, 300, 1), (64, 500, 7), (33, 257, 32), (16, 150, 100), (5, 3, 4)])
@@ -22,10 +33,8 @@ def test_knn_oracle_vs_reference_knn_cpu_with_ties(orc, B, M, K):
     reference's float32 KNearestNeighborIdxCpu (unmodified, oracle/_ref) must give bit-identical
     indices and distances to both the f32 twin and the f64 oracle loop: this pins selection,
     strict-'<' tie breaking (lowest index wins), ascending order and zero padding for M < K."""
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    q, t = _grid_cloud(B, 1), _grid_cloud(M, 2)
-    ri, rd = orc.ref_knn_cpu_f32(q, t, K)
+    q, t, k, ri, rd = _reference_knn(orc, f"ties_{B}_{M}_{K}")
+    assert q.shape == (B, 3) and t.shape == (M, 3) and k == K
     fi, fd = orc.knn_topk_f32(q, t, K)
     di, dd = orc.knn_topk(q, t, K)
     assert np.array_equal(ri, fi) and np.array_equal(rd, fd)
@@ -39,13 +48,9 @@ def test_knn_oracle_vs_reference_knn_cpu_with_ties(orc, B, M, K):
 
 
 def test_knn_f32_twin_vs_reference_on_random_float_data(orc):
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(3)
-    q = rng.normal(size=(50, 3)).astype(np.float32)
-    t = rng.normal(size=(700, 3)).astype(np.float32)
-    ri, rd = orc.ref_knn_cpu_f32(q, t, 20)
-    fi, fd = orc.knn_topk_f32(q, t, 20)
+    q, t, K, ri, rd = _reference_knn(orc, "random")
+    assert q.dtype == np.float32 and q.shape == (50, 3) and t.shape == (700, 3) and K == 20
+    fi, fd = orc.knn_topk_f32(q, t, K)
     assert np.array_equal(ri, fi) and np.array_equal(rd, fd)
 
 
