@@ -261,6 +261,35 @@ const float *svnicp_prep_source_f32_devptr(svnicp_prep *prep); /* the same point
 int svnicp_prep_download(svnicp_prep *prep, int which /* 0 cropped, 1 map cloud, 2 source */, float *out_xyz,
                          int64_t cap_points, int64_t *n_out);   /* test tap */
 
+/* ---- deskew (motion compensation) ahead of the crop: OdometryPipeline::deskew_pointcloud (:357-447) ----------------------
+ * The reference deskews when deskew_cloud_ is set (on in config/ICP_parameters.yaml:18) and its pose buffer holds two poses
+ * (:551-554: from the third scan on), then crops the DESKEWED cloud (:556, scan_max_range included) and samples it as above.
+ * stamps: the per-point field "t" / "timestamp" / "time" (:364-367) of type stamp_type, widened to double (:372-381, :403-413);
+ * NULL = no such field: all zero, min == max, the raw scan goes on (:418) — "no stamps" means "no deskew", not an error.
+ * flags SVNICP_DESKEW_KITTI (cloud_topic "/kitti/velo/pointcloud", :385-401): stamps are ignored; each point p is rotated by
+ * 0.205 deg about (p x z).normalized() (a zero axis stays zero, Eigen) into a float32 copy and stamped 0.5 * (yaw / pi + 1),
+ * yaw = -atan2(y, x) of the corrected float32 coordinates, as a float.  min / max over the stamps (:414-417); min == max
+ * returns the UNMODIFIED scan (:418; KITTI: without the correction); otherwise s = (t - min) / (max - min) (:419-423) and
+ * p' = float32(Pose3::Expmap((s - 0.5) * delta_xi).transformFrom(double(p))) (:436-445).  delta_xi = Pose3::Logmap of
+ * start^-1 * finish of the last two buffered poses (:427-432), [omega, v] (the caller computes it; pipeline.py /
+ * registration_pipeline.hpp: se3_log).  Deliberate deviation: non-finite stamps take no part in min / max (the reference's
+ * std::minmax_element result depends on where a NaN sits) and their points come out as NaN, which the crop drops.
+ * mem_kind applies to xyz AND stamps.  SVNICP_ERR_INVALID for an unknown stamp_type or flag, a NULL or non-finite delta_xi.
+ * The outputs (cropped / map cloud / source / source_f32, the counts, scan_max_range) mean exactly what they mean after
+ * svnicp_prep_scan.  Same host synchronisation as svnicp_prep_scan (one, after the crop), two kernels in place of its crop
+ * kernel.  Float64 Expmap on the device with the expressions of registration_pipeline.hpp; GTSAM / Eigen / PCL are absent,
+ * so parity with the reference is unpinned. */
+#define SVNICP_STAMP_F64 0
+#define SVNICP_STAMP_F32 1
+#define SVNICP_STAMP_U32 2
+#define SVNICP_DESKEW_KITTI 1
+int svnicp_prep_scan_deskew(svnicp_prep *prep, const float *xyz, const void *stamps, int stamp_type, int64_t n, int mem_kind,
+                            const double delta_xi[6], int flags, double min_range, double max_range, double voxel_size,
+                            double *scan_max_range, int64_t *n_cropped, int64_t *n_map, int64_t *n_source);
+const float *svnicp_prep_deskewed_devptr(svnicp_prep *prep);   /* float32 [n][3]: every point after the deskew, before the crop */
+int svnicp_prep_download_deskewed(svnicp_prep *prep, float *out_xyz, int64_t cap_points, int64_t *n_out);   /* test tap; valid
+                                                                 until the next svnicp_prep_scan_deskew */
+
 #ifdef __cplusplus
 }
 #endif

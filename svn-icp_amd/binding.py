@@ -95,6 +95,11 @@ def load_library():
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = vp
     L.svnicp_prep_download.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.svnicp_prep_scan_deskew.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, dp, C.c_int, C.c_double, C.c_double, C.c_double, dp,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.svnicp_prep_deskewed_devptr.argtypes = [vp]
+    L.svnicp_prep_deskewed_devptr.restype = vp
+    L.svnicp_prep_download_deskewed.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.svnicp_set_initial_mean.argtypes = [vp, dp, dp]
     L.svnicp_set_k.argtypes = [vp, C.c_int]
     L.svnicp_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]

@@ -16,6 +16,17 @@
 // lowest sorted position among the points that attain it (stable sort: lowest input index) — the same winner as the
 // sequential loop, independent of scheduling.  Same arithmetic, same order of additions as the host code (float32 points
 // widened to float64).  HBM-bound integer/byte work; nothing here touches the matrix pipe.
+//
+// Deskew (svnicp_prep_scan_deskew): OdometryPipeline::deskew_pointcloud (:357-447), which the reference runs ahead of the crop
+// when deskew_cloud_ is set and the pose buffer holds two poses (:551-554).  k_deskew_stamps widens the per-point stamps
+// (uint32 / float32 / float64, :372-381, :403-413) to double — or, in KITTI mode (:385-401), rotates each point by 0.205° about
+// (p × ẑ).normalized() into scratch and derives its stamp from the yaw — and reduces min / max over the FINITE stamps (one
+// pair of atomics per workgroup, enc_f64).  k_deskew_crop replaces k_prep_crop on this path: per point s = (t − min)/(max − min)
+// (:419-423), Pose3::Expmap((s − 0.5)·δ).transformFrom(p) in float64 (:436-445), rounded once to float32 into the kept
+// deskewed buffer (min == max: the raw point, :418), then k_prep_crop's predicate and squared-norm maximum.  The expressions
+// are those of registration_pipeline.hpp (se3_exp, deskew_pointcloud, kitti_correct_and_stamp) and pipeline.py, in the same
+// order; only sin / cos / atan2 may differ from the host libm in the last bit.  After it, the exclusive scan, k_prep_compact
+// and the two samplings run as in svnicp_prep_scan, on the deskewed points.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -165,6 +176,127 @@ __global__ __launch_bounds__(256) void k_ds_gather(const float* __restrict__ in,
   if (out64) { out64[3 * (size_t)r] = (double)x; out64[3 * (size_t)r + 1] = (double)y; out64[3 * (size_t)r + 2] = (double)z; }   // ICPUtils.cpp:27-43
 }
 
+// ---- deskew (OdometryPipeline.cpp:357-447)
+struct Twist { double v[6]; };   // delta_xi = Pose3::Logmap(start^-1 * finish), [omega, v]
+
+// registration_pipeline.hpp: se3_exp (Pose3::Expmap) followed by transformFrom, row-major R, each row summed left to right
+__device__ __forceinline__ void se3_exp_apply(const double xi[6], double px, double py, double pz, float* q) {
+  const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+  const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+  const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+  double K2[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) K2[3 * i + j] = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
+  double ra, rb, vb, vc;
+  if (th < 1e-10) { ra = 1.0; rb = 0.5; vb = 0.5; vc = 0.0; }
+  else {
+    const double sn = sin(th), cs = cos(th);
+    ra = sn / th; rb = (1.0 - cs) / (th * th); vb = (1.0 - cs) / (th * th); vc = (th - sn) / (th * th * th);
+  }
+  double R[9], V[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { R[i] = ra * K[i] + rb * K2[i]; V[i] = vb * K[i] + vc * K2[i]; }
+  R[0] += 1.0; R[4] += 1.0; R[8] += 1.0; V[0] += 1.0; V[4] += 1.0; V[8] += 1.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double t = V[3 * i] * xi[3] + V[3 * i + 1] * xi[4] + V[3 * i + 2] * xi[5];
+    q[i] = (float)(((R[3 * i] * px + R[3 * i + 1] * py) + R[3 * i + 2] * pz) + t);
+  }
+}
+
+// stamps widened to double (KITTI: corrected point into kpts + its stamp); max of enc(t) -> dscal[1], max of ~enc(t) (the
+// minimum) -> dscal[2], finite stamps only; 0 = nothing seen (enc of a non-NaN double is neither 0 nor ~0)
+__global__ __launch_bounds__(256) void k_deskew_stamps(const float* __restrict__ in, const void* __restrict__ stamps, int type, int kitti,
+                                                       double ksin, double kcos, int64_t n, float* __restrict__ kpts, double* __restrict__ st,
+                                                       unsigned long long* __restrict__ dscal) {
+  __shared__ unsigned long long s_hi[4], s_lo[4];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long hi = 0, lo = 0;
+  if (i < n) {
+    double t;
+    if (kitti) {   // :385-401, the expressions of kitti_correct_and_stamp (AngleAxis::toRotationMatrix of Eigen 3; unpinned)
+      const double x = (double)in[3 * i], y = (double)in[3 * i + 1], z = (double)in[3 * i + 2];
+      double ax = y, ay = -x;
+      const double az = 0.0;
+      const double nn = (ax * ax + ay * ay) + az * az;
+      if (nn > 0.0) { const double r = sqrt(nn); ax = ax / r; ay = ay / r; }   // Eigen normalized(): a zero vector stays zero
+      const double sx = ksin * ax, sy = ksin * ay, sz = ksin * az;
+      const double cx = (1.0 - kcos) * ax, cy = (1.0 - kcos) * ay, cz = (1.0 - kcos) * az;
+      const double R[9] = {cx * ax + kcos, cx * ay - sz, cx * az + sy, cx * ay + sz, cy * ay + kcos, cy * az - sx, cx * az - sy, cy * az + sx,
+                           cz * az + kcos};
+      float q[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) q[d] = (float)((R[3 * d] * x + R[3 * d + 1] * y) + R[3 * d + 2] * z);
+      kpts[3 * i] = q[0]; kpts[3 * i + 1] = q[1]; kpts[3 * i + 2] = q[2];
+      const float yaw = (float)(-atan2((double)q[1], (double)q[0]));   // the float yaw of :397, correctly rounded
+      t = 0.5 * ((double)yaw / 3.14159265358979323846 + 1.0);
+    } else if (type == SVNICP_STAMP_F64) {
+      t = static_cast<const double*>(stamps)[i];
+    } else if (type == SVNICP_STAMP_F32) {
+      t = (double)static_cast<const float*>(stamps)[i];
+    } else {
+      t = (double)static_cast<const uint32_t*>(stamps)[i];
+    }
+    st[i] = t;
+    if (isfinite(t)) { hi = enc_f64(t); lo = ~hi; }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long a = __shfl_xor(hi, off, 64), b = __shfl_xor(lo, off, 64);
+    hi = a > hi ? a : hi; lo = b > lo ? b : lo;
+  }
+  if ((threadIdx.x & 63) == 0) { s_hi[threadIdx.x >> 6] = hi; s_lo[threadIdx.x >> 6] = lo; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) { hi = s_hi[w] > hi ? s_hi[w] : hi; lo = s_lo[w] > lo ? s_lo[w] : lo; }
+    if (hi) atomicMax(&dscal[1], hi);
+    if (lo) atomicMax(&dscal[2], lo);
+  }
+}
+
+// deskewed point -> out (kept), then k_prep_crop's predicate and squared-norm maximum (dscal[0]) on it
+__global__ __launch_bounds__(256) void k_deskew_crop(const float* __restrict__ in, const float* __restrict__ kpts, const double* __restrict__ st,
+                                                     int64_t n, Twist delta, double min2, double max2, float* __restrict__ out,
+                                                     int* __restrict__ keep, unsigned long long* dscal) {
+  __shared__ double s_m[4];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double n2 = -1.0;
+  if (i < n) {
+    const unsigned long long hi = dscal[1], lo = dscal[2];   // written by the previous launch
+    const double tmax = dec_f64(hi), tmin = dec_f64(~lo);
+    float q[3];
+    if (hi == 0 || tmin == tmax) {                          // no (finite) stamps, or min == max: *frame, the raw point (:418)
+      q[0] = in[3 * i]; q[1] = in[3 * i + 1]; q[2] = in[3 * i + 2];
+    } else {
+      const double t = st[i];
+      if (!isfinite(t)) {                                   // deliberate deviation (header): a point without a valid stamp is NaN
+        q[0] = q[1] = q[2] = __builtin_nanf("");
+      } else {
+        const float* src = kpts ? kpts : in;                // KITTI: the corrected copy (frame_points, :361, :392-394)
+        const double sp = (t - tmin) / (tmax - tmin) - 0.5;   // :419-423, then (s - 0.5) of :439
+        double xi[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) xi[k] = sp * delta.v[k];
+        se3_exp_apply(xi, (double)src[3 * i], (double)src[3 * i + 1], (double)src[3 * i + 2], q);
+      }
+    }
+    out[3 * i] = q[0]; out[3 * i + 1] = q[1]; out[3 * i + 2] = q[2];
+    const float x = q[0], y = q[1], z = q[2];
+    n2 = (double)((x * x + y * y) + z * z);           // k_prep_crop's arithmetic (OdometryPipeline.cpp:698)
+    keep[i] = (n2 < max2 && n2 > min2) ? 1 : 0;
+    if (!(n2 == n2)) n2 = -1.0;
+  }
+  double m = n2;
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+    if (m >= 0.0) atomicMax(&dscal[0], enc_f64(m));
+  }
+}
+
 std::string g_prep_error;
 
 }  // namespace
@@ -179,6 +311,13 @@ struct svnicp_prep {
   PBuf<unsigned long long> key, skey, d2bits, run_min, scal;   // scal: [0] max squared norm (encoded) [1..6] grid bounds
   PBuf<char> tmp;
   int64_t n_cropped = 0, n_map = 0, n_source = 0;
+  // svnicp_prep_scan_deskew: deskewed points (every point, kept), KITTI-corrected scratch, stamps as double, uploaded stamps,
+  // dscal: [0] max squared norm (encoded) [1] max stamp (encoded) [2] min stamp (complement of the encoding)
+  PBuf<float> deskewed, kpts;
+  PBuf<double> st;
+  PBuf<char> stamps_in;
+  PBuf<unsigned long long> dscal;
+  int64_t n_deskewed = 0;
 };
 
 namespace {
@@ -266,6 +405,7 @@ void svnicp_prep_destroy(svnicp_prep* p) {
   p->in.release(); p->cropped.release(); p->map_cloud.release(); p->source.release(); p->source64.release(); p->keep.release(); p->off.release();
   p->idx.release(); p->sidx.release(); p->flag.release(); p->pre.release(); p->run_pos.release(); p->key.release(); p->skey.release();
   p->d2bits.release(); p->run_min.release(); p->scal.release(); p->tmp.release();
+  p->deskewed.release(); p->kpts.release(); p->st.release(); p->stamps_in.release(); p->dscal.release();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
@@ -330,6 +470,103 @@ const float* svnicp_prep_cropped_devptr(svnicp_prep* p) { return p ? p->cropped.
 const float* svnicp_prep_map_cloud_devptr(svnicp_prep* p) { return p ? p->map_cloud.p : nullptr; }
 const double* svnicp_prep_source_devptr(svnicp_prep* p) { return p ? p->source64.p : nullptr; }
 const float* svnicp_prep_source_f32_devptr(svnicp_prep* p) { return p ? p->source.p : nullptr; }
+
+int svnicp_prep_scan_deskew(svnicp_prep* p, const float* xyz, const void* stamps, int stamp_type, int64_t n, int mem_kind,
+                            const double delta_xi[6], int flags, double min_range, double max_range, double voxel_size,
+                            double* scan_max_range, int64_t* n_cropped, int64_t* n_map, int64_t* n_source) {
+  if (!p || !scan_max_range || !n_cropped || !n_map || !n_source || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL)
+    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: bad argument");
+  if (stamp_type != SVNICP_STAMP_F64 && stamp_type != SVNICP_STAMP_F32 && stamp_type != SVNICP_STAMP_U32)
+    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown stamp_type");
+  if (!delta_xi) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is NULL");
+  for (int k = 0; k < 6; ++k)
+    if (!std::isfinite(delta_xi[k])) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is not finite");
+  if (flags & ~SVNICP_DESKEW_KITTI) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown flags");
+  PCHK(p, hipSetDevice(p->device));
+  p->n_cropped = p->n_map = p->n_source = p->n_deskewed = 0;
+  *n_cropped = *n_map = *n_source = 0;
+  if (n == 0) return SVNICP_OK;
+  const bool kitti = (flags & SVNICP_DESKEW_KITTI) != 0;
+  const float* din = xyz;
+  const void* dst = kitti ? nullptr : stamps;   // KITTI derives its stamps from the points (:385-401)
+  if (mem_kind != SVNICP_MEM_DEVICE) {
+    PCHK(p, p->in.ensure((size_t)n * 3));
+    PCHK(p, hipMemcpyAsync(p->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
+    din = p->in.p;
+    if (dst) {
+      const size_t bytes = (size_t)n * (stamp_type == SVNICP_STAMP_F64 ? 8 : 4);
+      PCHK(p, p->stamps_in.ensure(bytes));
+      PCHK(p, hipMemcpyAsync(p->stamps_in.p, dst, bytes, hipMemcpyHostToDevice, p->stream));
+      dst = p->stamps_in.p;
+    }
+  }
+  // ---- deskew (:357-447) fused with the crop (:692-704)
+  PCHK(p, p->deskewed.ensure((size_t)n * 3)); PCHK(p, p->keep.ensure((size_t)n)); PCHK(p, p->off.ensure((size_t)n));
+  PCHK(p, p->dscal.ensure(3));
+  if (kitti) PCHK(p, p->kpts.ensure((size_t)n * 3));
+  if (kitti || dst) PCHK(p, p->st.ensure((size_t)n));
+  PCHK(p, hipMemsetAsync(p->dscal.p, 0, 24, p->stream));   // 0 = nothing seen (max norm, max stamp, min stamp)
+  const unsigned g = (unsigned)((n + 255) / 256);
+  if (kitti || dst) {   // no stamp field: min == max == 0, the raw frame (:418); k_deskew_crop sees dscal[1] == 0
+    constexpr double kVerticalAngleOffset = (0.205 * 3.14159265358979323846) / 180.0;   // :386
+    hipLaunchKernelGGL(k_deskew_stamps, dim3(g), dim3(256), 0, p->stream, din, dst, stamp_type, kitti ? 1 : 0, std::sin(kVerticalAngleOffset),
+                       std::cos(kVerticalAngleOffset), n, kitti ? p->kpts.p : (float*)nullptr, p->st.p, p->dscal.p);
+    PCHK(p, hipGetLastError());
+  }
+  Twist tw;
+  for (int k = 0; k < 6; ++k) tw.v[k] = delta_xi[k];
+  hipLaunchKernelGGL(k_deskew_crop, dim3(g), dim3(256), 0, p->stream, din, kitti ? (const float*)p->kpts.p : (const float*)nullptr,
+                     (kitti || dst) ? (const double*)p->st.p : (const double*)nullptr, n, tw, min_range * min_range, max_range * max_range,
+                     p->deskewed.p, p->keep.p, p->dscal.p);
+  PCHK(p, hipGetLastError());
+  p->n_deskewed = n;
+  // ---- from here on svnicp_prep_scan's sequence, on the deskewed points
+  size_t b = 0;
+  PCHK(p, rocprim::exclusive_scan(nullptr, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  PCHK(p, p->tmp.ensure(b));
+  PCHK(p, rocprim::exclusive_scan(p->tmp.p, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  int last[2] = {0, 0};
+  unsigned long long enc = 0;
+  PCHK(p, hipMemcpyAsync(&last[0], p->off.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  PCHK(p, hipMemcpyAsync(&last[1], p->keep.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  PCHK(p, hipMemcpyAsync(&enc, p->dscal.p, 8, hipMemcpyDeviceToHost, p->stream));
+  PCHK(p, hipStreamSynchronize(p->stream));   // the only host synchronisation before the samplings, as in svnicp_prep_scan
+  if (enc) {
+    const unsigned long long bits = (enc & 0x8000000000000000ull) ? (enc & 0x7fffffffffffffffull) : ~enc;
+    double m;
+    std::memcpy(&m, &bits, 8);
+    if (m > *scan_max_range) *scan_max_range = m;       // :699, on the deskewed cloud (:556)
+  }
+  const int64_t nc = (int64_t)last[0] + last[1];
+  PCHK(p, p->cropped.ensure((size_t)(nc > 0 ? nc : 1) * 3));
+  hipLaunchKernelGGL(k_prep_compact, dim3(g), dim3(256), 0, p->stream, p->deskewed.p, n, p->keep.p, p->off.p, p->cropped.p);
+  PCHK(p, hipGetLastError());
+  p->n_cropped = nc;
+  int rc = downsample(p, p->cropped.p, nc, 0.5 * voxel_size, p->map_cloud, nullptr, &p->n_map);   // :559
+  if (rc) return rc;
+  rc = downsample(p, p->map_cloud.p, p->n_map, 1.5 * voxel_size, p->source, &p->source64, &p->n_source);   // :560
+  if (rc) return rc;
+  if (!(1.5 * voxel_size > 0.0) && p->n_source > 0) {
+    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: voxel_size must be positive");
+  }
+  PCHK(p, hipStreamSynchronize(p->stream));
+  *n_cropped = p->n_cropped; *n_map = p->n_map; *n_source = p->n_source;
+  return SVNICP_OK;
+}
+
+const float* svnicp_prep_deskewed_devptr(svnicp_prep* p) { return p ? p->deskewed.p : nullptr; }
+
+int svnicp_prep_download_deskewed(svnicp_prep* p, float* out_xyz, int64_t cap_points, int64_t* n_out) {
+  if (!p || !n_out) return SVNICP_ERR_INVALID;
+  PCHK(p, hipSetDevice(p->device));
+  *n_out = p->n_deskewed;
+  const int64_t n = p->n_deskewed < cap_points ? p->n_deskewed : cap_points;
+  if (n > 0 && out_xyz) {
+    PCHK(p, hipMemcpyAsync(out_xyz, p->deskewed.p, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
+    PCHK(p, hipStreamSynchronize(p->stream));
+  }
+  return SVNICP_OK;
+}
 
 int svnicp_prep_download(svnicp_prep* p, int which, float* out_xyz, int64_t cap_points, int64_t* n_out) {
   if (!p || !n_out || which < 0 || which > 2) return SVNICP_ERR_INVALID;

@@ -8,6 +8,8 @@
 // VoxelHashMap.cpp:22-42).  The reference does this with PCL / GTSAM / tsl::robin_map on the host; none of them exists
 // in this image, so the few operations needed are written out here (float32 points like pcl::PointXYZ, float64 poses).
 // The Python module svn-icp_amd/pipeline.py is the same sequence and serves as the cross-check in the tests.
+// With PipelineConfig::deskew the scan is first motion-compensated as OdometryPipeline::deskew_pointcloud does (:357-447,
+// run when the pose buffer holds two poses, :551-554); see deskew_pointcloud below.
 //
 // Where PCL / the hash map leave an order unspecified (iteration order of occupied leaves / voxels) this code emits
 // ascending leaf / voxel index; the solver's result does not depend on the order of the target points except through
@@ -22,6 +24,7 @@
 #include <map>
 #include <memory>
 #include <numeric>
+#include <stdexcept>
 #include <vector>
 
 #include "svnicp_hip_shim.hpp"
@@ -128,6 +131,84 @@ inline Cloud crop_pointcloud(const Cloud& in, double min_range, double max_range
     const double n2 = (double)(float)(xy + zz);
     if (n2 > *scan_max_range) *scan_max_range = n2;
     if (n2 < max_range * max_range && n2 > min_range * min_range) out.push_back(p);
+  }
+  return out;
+}
+
+// ------------------------------------------------------------------------------------------------ deskew (:357-447)
+// The same float32 / float64 steps as pipeline.py (kitti_correct_and_stamp, deskew_pointcloud) and csrc/scan_prep.hip
+// (k_deskew_stamps, k_deskew_crop).  Parity unpinned: GTSAM and Eigen are absent, Pose3::Expmap is se3_exp above and
+// transformFrom is R·p + t with each row summed left to right.
+constexpr double kKittiVerticalAngleOffset = (0.205 * 3.14159265358979323846) / 180.0;   // :386
+
+// per-point stamp field of PointField type UINT32 / FLOAT32 / FLOAT64, widened to double (:372-381, :403-413)
+template <typename T>
+inline std::vector<double> widen_stamps(const T* p, size_t n) {
+  std::vector<double> o(n);
+  for (size_t i = 0; i < n; ++i) o[i] = static_cast<double>(p[i]);
+  return o;
+}
+
+// the KITTI branch (:385-401): p in double; axis = (p x z).normalized() = (y, -x, 0)/|.| (Eigen's normalized() leaves a zero
+// vector as it is); AngleAxisd(0.205 deg, axis) * p stored into the float32 point; stamp 0.5 * (yaw / pi + 1) with the float
+// yaw = -atan2(y, x) of the corrected float32 coordinates (formed as the double atan2 rounded once to float: the correctly
+// rounded float result).  The rotation matrix is Eigen 3's AngleAxis::toRotationMatrix() (sin*axis, (1-c)*axis, diagonal
+// last), the product summed left to right — unpinned (Eigen absent).
+inline void kitti_correct_and_stamp(const Cloud& in, Cloud* out, std::vector<double>* stamps) {
+  const double sn = std::sin(kKittiVerticalAngleOffset), c = std::cos(kKittiVerticalAngleOffset);
+  out->resize(in.size());
+  stamps->resize(in.size());
+  for (size_t i = 0; i < in.size(); ++i) {
+    const double x = in[i][0], y = in[i][1], z = in[i][2];
+    double ax = y, ay = -x;
+    const double az = 0.0;
+    const double nn = (ax * ax + ay * ay) + az * az;
+    if (nn > 0.0) { const double r = std::sqrt(nn); ax = ax / r; ay = ay / r; }
+    const double sx = sn * ax, sy = sn * ay, sz = sn * az;
+    const double cx = (1.0 - c) * ax, cy = (1.0 - c) * ay, cz = (1.0 - c) * az;
+    const double R[9] = {cx * ax + c, cx * ay - sz, cx * az + sy, cx * ay + sz, cy * ay + c, cy * az - sx, cx * az - sy, cy * az + sx, cz * az + c};
+    for (int d = 0; d < 3; ++d) (*out)[i][d] = (float)((R[3 * d] * x + R[3 * d + 1] * y) + R[3 * d + 2] * z);
+    const float yaw = (float)(-std::atan2((double)(*out)[i][1], (double)(*out)[i][0]));
+    (*stamps)[i] = 0.5 * ((double)yaw / 3.14159265358979323846 + 1.0);
+  }
+}
+
+// OdometryPipeline::deskew_pointcloud (:357-447).  stamps: the widened per-point times, or nullptr (no "t" / "timestamp" /
+// "time" field, :364-367: all zero -> the raw frame).  kitti: stamps from kitti_correct_and_stamp instead.  min / max
+// (:414-417); min == max returns the UNMODIFIED frame (:418); else s = (t - min)/(max - min) (:419-423) and
+// p' = float32(Pose3::Expmap((s - 0.5) * delta).transformFrom(double(p))) (:436-445); delta = Pose3::Logmap(start^-1 * finish)
+// of the last two buffered poses (:427-432), [omega, v].  Deliberate deviation: non-finite stamps take no part in min / max
+// (std::minmax_element's answer depends on where a NaN sits) and their points come out NaN, which the crop drops.
+inline Cloud deskew_pointcloud(const Cloud& in, const std::vector<double>* stamps, const std::array<double, 6>& delta, bool kitti) {
+  Cloud corrected;
+  std::vector<double> kst;
+  const Cloud* src = &in;
+  if (kitti) {
+    kitti_correct_and_stamp(in, &corrected, &kst);
+    src = &corrected;
+    stamps = &kst;
+  }
+  if (!stamps) return in;
+  if (stamps->size() != in.size()) throw std::invalid_argument("deskew_pointcloud: one stamp per point");
+  bool any = false;
+  double tmin = 0, tmax = 0;
+  for (double t : *stamps)
+    if (std::isfinite(t)) {
+      if (!any || t < tmin) tmin = t;
+      if (!any || t > tmax) tmax = t;
+      any = true;
+    }
+  if (!any || tmin == tmax) return in;   // :418, *frame
+  Cloud out(in.size());
+  for (size_t i = 0; i < in.size(); ++i) {
+    const double t = (*stamps)[i];
+    if (!std::isfinite(t)) { out[i] = {NAN, NAN, NAN}; continue; }
+    const double sp = (t - tmin) / (tmax - tmin) - 0.5;
+    double xi[6];
+    for (int k = 0; k < 6; ++k) xi[k] = sp * delta[k];
+    const Pose3 T = se3_exp(xi);
+    const double x = (*src)[i][0], y = (*src)[i][1], z = (*src)[i][2];
+    for (int d = 0; d < 3; ++d) out[i][d] = (float)(((T.R[3 * d] * x + T.R[3 * d + 1] * y) + T.R[3 * d + 2] * z) + T.t[d]);
   }
   return out;
 }
@@ -270,6 +351,21 @@ class DevicePrep {
                          scan_max_range, &n_cropped, &n_map, &n_source) != 0)
       throw std::runtime_error(svnicp_prep_last_error(p_));
   }
+  // deskew (OdometryPipeline.cpp:357-447) ahead of the same crop + samplings; stamps of SVNICP_STAMP_* type or nullptr
+  void scan_deskew(const Cloud& points, const void* stamps, int stamp_type, const std::array<double, 6>& delta, bool kitti, double min_range,
+                   double max_range, double voxel_size, double* scan_max_range) {
+    if (svnicp_prep_scan_deskew(p_, points.empty() ? nullptr : &points[0][0], stamps, stamp_type, (int64_t)points.size(), SVNICP_MEM_HOST,
+                                delta.data(), kitti ? SVNICP_DESKEW_KITTI : 0, min_range, max_range, voxel_size, scan_max_range, &n_cropped,
+                                &n_map, &n_source) != 0)
+      throw std::runtime_error(svnicp_prep_last_error(p_));
+  }
+  Cloud download_deskewed() {   // test tap
+    int64_t n = 0;
+    if (svnicp_prep_download_deskewed(p_, nullptr, 0, &n) != 0) throw std::runtime_error(svnicp_prep_last_error(p_));
+    Cloud o((size_t)n);
+    if (n && svnicp_prep_download_deskewed(p_, &o[0][0], n, &n) != 0) throw std::runtime_error(svnicp_prep_last_error(p_));
+    return o;
+  }
   const float* cropped() { return svnicp_prep_cropped_devptr(p_); }
   const float* map_cloud() { return svnicp_prep_map_cloud_devptr(p_); }
   const double* source() { return svnicp_prep_source_devptr(p_); }
@@ -313,6 +409,8 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   int device = 0;
   bool gpu_map = false;  // keep the local map in HBM (DeviceVoxelMap): the target never crosses PCIe
   bool gpu_prep = false; // with gpu_map: crop and both uniform samplings on the device (DevicePrep): the raw scan is uploaded, no host pass over the points
+  bool deskew = false;   // deskew_cloud (config/ICP_parameters.yaml:18): motion compensation ahead of the crop once two poses exist (:551-554)
+  bool kitti = false;    // with deskew: the KITTI branch (cloud_topic "/kitti/velo/pointcloud", :385-401) instead of per-point stamps
 };
 
 struct ScanResult {
@@ -350,15 +448,33 @@ class RegistrationPipeline {
   const std::vector<Pose3>& poses() const { return poses_; }
 
   // one pass of ICP_processing's loop body for one LiDAR frame (points: n x 3 float32, sensor frame)
-  ScanResult process_scan(const Cloud& points, double stamp) {
+  ScanResult process_scan(const Cloud& points, double stamp) { return process(points, stamp, nullptr); }
+  // ... with the scan's per-point time field (widened to double), used when cfg.deskew is set
+  ScanResult process_scan(const Cloud& points, double stamp, const std::vector<double>& point_stamps) {
+    return process(points, stamp, &point_stamps);
+  }
+
+ private:
+  ScanResult process(const Cloud& points, double stamp, const std::vector<double>* point_stamps) {
     ScanResult res;
     res.stamp = stamp;
     Cloud cropped, to_map, source;
+    const bool deskew = cfg_.deskew && poses_.size() >= 2;                                             // :552
+    std::array<double, 6> delta{};
+    if (deskew) delta = se3_log(poses_[poses_.size() - 2].inverse() * poses_.back());                  // :427-432
     if (dprep_) {
-      dprep_->scan(points, cfg_.min_range, cfg_.max_range, cfg_.voxel_size, &scan_max_range_);         // :556-560 on the device
-      bytes_h2d_ += points.size() * 12;
+      if (deskew) {                                                                                    // :551-560 on the device
+        const bool st = point_stamps && !cfg_.kitti;
+        dprep_->scan_deskew(points, st ? point_stamps->data() : nullptr, SVNICP_STAMP_F64, delta, cfg_.kitti, cfg_.min_range, cfg_.max_range,
+                            cfg_.voxel_size, &scan_max_range_);
+        bytes_h2d_ += points.size() * 12 + (st ? point_stamps->size() * 8 : 0);
+      } else {
+        dprep_->scan(points, cfg_.min_range, cfg_.max_range, cfg_.voxel_size, &scan_max_range_);       // :556-560 on the device
+        bytes_h2d_ += points.size() * 12;
+      }
     } else {
-      cropped = crop_pointcloud(points, cfg_.min_range, cfg_.max_range, &scan_max_range_);             // :556
+      const Cloud deskewed = deskew ? deskew_pointcloud(points, point_stamps, delta, cfg_.kitti) : Cloud{};   // :553
+      cropped = crop_pointcloud(deskew ? deskewed : points, cfg_.min_range, cfg_.max_range, &scan_max_range_);   // :556
       to_map = downsample_uniform(cropped, 0.5 * cfg_.voxel_size);                                     // :559
       source = downsample_uniform(to_map, 1.5 * cfg_.voxel_size);                                      // :560
     }
@@ -417,7 +533,6 @@ class RegistrationPipeline {
     return res;
   }
 
- private:
   static std::vector<double> widen(const Cloud& c) {
     std::vector<double> o(3 * c.size());
     for (size_t i = 0; i < c.size(); ++i)

@@ -127,6 +127,114 @@ def downsample_uniform(points: np.ndarray, radius: float) -> np.ndarray:
     return p[order[first]]
 
 
+# ----------------------------------------------------------------------------- deskew (motion compensation)
+# OdometryPipeline::deskew_pointcloud (OdometryPipeline.cpp:357-447), run ahead of the crop when deskew_cloud_ is set and the
+# pose buffer holds two poses (:551-554).  Restated with the float32 / float64 steps of the reference; the same expressions, in
+# the same order, are in registration_pipeline.hpp (deskew_pointcloud) and csrc/scan_prep.hip (k_deskew_*).  Parity unpinned:
+# GTSAM and Eigen are absent, so Pose3::Expmap / transformFrom and AngleAxis are written out (se3_exp's formulas).
+KITTI_VERTICAL_ANGLE_OFFSET = (0.205 * math.pi) / 180.0     # :386
+STAMP_DTYPES = (np.float64, np.float32, np.uint32)          # PointField FLOAT64 / FLOAT32 / UINT32 (:403-413)
+
+
+def kitti_correct_and_stamp(points: np.ndarray):
+    """The KITTI branch of deskew_pointcloud (:385-401) -> (corrected float32 [n,3], stamps float64 [n]).
+    Per point: p in double; axis = (p × ẑ).normalized() = (y, −x, 0)/|·| (Eigen's normalized() leaves a zero vector as it is);
+    AngleAxisd(0.205°, axis) * p stored back into the float32 point; stamp 0.5·(yaw/π + 1) with yaw = −atan2(y, x) of the
+    float32 corrected coordinates, a float (std::atan2's float overload; formed here as the float64 atan2 rounded once to
+    float32 — the correctly rounded value — identically in all three layers).  AngleAxis::toRotationMatrix() is Eigen 3's
+    (sin·axis, (1−c)·axis, diagonal last); the matrix-vector product is summed left to right — unpinned (Eigen absent)."""
+    f = np.asarray(points, np.float32)[:, :3]
+    x, y, z = (f[:, d].astype(np.float64) for d in range(3))
+    ax, ay = y.copy(), -x                                       # p × (0, 0, 1) = (y·1 − z·0, z·0 − x·1, x·0 − y·0)
+    n2 = (ax * ax + ay * ay) + 0.0 * 0.0
+    nz = n2 > 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nrm = np.sqrt(n2)
+        ax = np.where(nz, ax / nrm, ax)
+        ay = np.where(nz, ay / nrm, ay)
+    az = np.zeros_like(ax)
+    a = KITTI_VERTICAL_ANGLE_OFFSET
+    sn, c = math.sin(a), math.cos(a)
+    sx, sy, sz = sn * ax, sn * ay, sn * az                      # sin_axis
+    cx, cy, cz = (1.0 - c) * ax, (1.0 - c) * ay, (1.0 - c) * az   # cos1_axis
+    R = [[cx * ax + c, cx * ay - sz, cx * az + sy],
+         [cx * ay + sz, cy * ay + c, cy * az - sx],
+         [cx * az - sy, cy * az + sx, cz * az + c]]
+    out = np.empty((f.shape[0], 3), np.float32)
+    for d in range(3):
+        out[:, d] = ((R[d][0] * x + R[d][1] * y) + R[d][2] * z).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        yaw = (-np.arctan2(out[:, 1].astype(np.float64), out[:, 0].astype(np.float64))).astype(np.float32)
+    stamps = 0.5 * (yaw.astype(np.float64) / math.pi + 1.0)
+    return out, stamps
+
+
+def _se3_exp_rows(xi: np.ndarray):
+    """se3_exp for many twists at once ([n,6] -> R [n,9] row-major, t [n,3]), in the operation order of the C++ se3_exp
+    (registration_pipeline.hpp: hat, mul3 summed left to right, lin3 = b·K + c·K², then the diagonal) and of the device."""
+    w0, w1, w2 = xi[:, 0], xi[:, 1], xi[:, 2]
+    z = np.zeros_like(w0)
+    K = [z, -w2, w1, w2, z, -w0, -w1, w0, z]
+    K2 = [(K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j] for i in range(3) for j in range(3)]
+    th = np.sqrt((w0 * w0 + w1 * w1) + w2 * w2)
+    small = th < 1e-10
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sn, cs = np.sin(th), np.cos(th)
+        ra = np.where(small, 1.0, sn / th)
+        rb = np.where(small, 0.5, (1.0 - cs) / (th * th))
+        vb = np.where(small, 0.5, (1.0 - cs) / (th * th))
+        vc = np.where(small, 0.0, (th - sn) / (th * th * th))
+    R = [ra * K[i] + rb * K2[i] for i in range(9)]
+    V = [vb * K[i] + vc * K2[i] for i in range(9)]
+    for i in (0, 4, 8):
+        R[i] = R[i] + 1.0
+        V[i] = V[i] + 1.0
+    v0, v1, v2 = xi[:, 3], xi[:, 4], xi[:, 5]
+    t = [(V[3 * i] * v0 + V[3 * i + 1] * v1) + V[3 * i + 2] * v2 for i in range(3)]
+    return R, t
+
+
+def deskew_pointcloud(points: np.ndarray, stamps, delta6, kitti: bool = False) -> np.ndarray:
+    """OdometryPipeline::deskew_pointcloud (:357-447) -> float32 [n,3].
+    stamps: the per-point field ``t`` / ``timestamp`` / ``time`` (:364-367) as float64, float32 or uint32, widened to double
+    (:372-381); None = no such field: the vector stays zero, min == max and the raw frame comes back (:418).  kitti: the
+    ``/kitti/velo/pointcloud`` branch (:385-401) replaces the stamps by kitti_correct_and_stamp.  min / max over the stamps
+    (:414-417); min == max returns the UNMODIFIED frame (:418, in KITTI mode without the vertical correction); otherwise
+    s = (t − min)/(max − min) (:419-423) and every point becomes Pose3::Expmap((s − 0.5)·δ).transformFrom(p) (:436-445), p the
+    float32 point widened to double, the result rounded once to float32; δ = Pose3::Logmap(start⁻¹·finish) of the last two
+    buffered poses (:427-432), [ω, v].  Deliberate deviation: non-finite stamps take no part in min / max (the reference's
+    std::minmax_element answer depends on where a NaN sits) and their points come out as NaN, which the crop drops."""
+    f = np.asarray(points, np.float32)[:, :3]
+    delta6 = np.asarray(delta6, np.float64).reshape(6)
+    if kitti:
+        src, t = kitti_correct_and_stamp(f)
+    else:
+        if stamps is None:
+            return f.copy()
+        st = np.asarray(stamps)
+        if st.dtype.type not in STAMP_DTYPES:
+            raise ValueError(f"deskew_pointcloud: stamp type {st.dtype} (float64, float32 or uint32)")
+        if st.shape != (f.shape[0],):
+            raise ValueError("deskew_pointcloud: one stamp per point")
+        src, t = f, st.astype(np.float64)
+    fin = np.isfinite(t)
+    if not fin.any():
+        return f.copy()
+    tmin, tmax = float(t[fin].min()), float(t[fin].max())
+    if tmin == tmax:
+        return f.copy()                                        # :418, *frame: the raw points
+    with np.errstate(invalid="ignore"):
+        s = (t - tmin) / (tmax - tmin)
+    sp = np.where(fin, s - 0.5, 0.0)                           # (the non-finite ones are set to NaN below)
+    R, tr = _se3_exp_rows(sp[:, None] * delta6[None, :])
+    x, y, z = (src[:, d].astype(np.float64) for d in range(3))
+    out = np.empty_like(src)
+    for d in range(3):
+        out[:, d] = (((R[3 * d] * x + R[3 * d + 1] * y) + R[3 * d + 2] * z) + tr[d]).astype(np.float32)
+    out[~fin] = np.nan
+    return out
+
+
 # ----------------------------------------------------------------------------- local map
 def transform_f32(cloud, T) -> np.ndarray:
     """pcl::transformPointCloud of float32 points with gtsam's DOUBLE Matrix4 (VoxelHashMap.cpp:23-25): every coordinate
@@ -234,6 +342,15 @@ class DeviceVoxelHashMap:
         return out
 
 
+# stamp types and flags of svnicp_prep_scan_deskew (include/svnicp_hip.h)
+SVNICP_STAMP_F64, SVNICP_STAMP_F32, SVNICP_STAMP_U32 = 0, 1, 2
+SVNICP_DESKEW_KITTI = 1
+
+
+def _is_cuda_tensor(x) -> bool:
+    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
+
+
 class DevicePreprocessor:
     """crop_pointcloud + the two uniform samplings of a scan on the device (svnicp_prep_* of the C ABI, csrc/scan_prep.hip):
     the raw float32 scan is uploaded once, the cropped cloud, the map cloud (float32) and the source cloud (float64 rows)
@@ -261,20 +378,92 @@ class DevicePreprocessor:
         except Exception:
             pass
 
-    def scan(self, points: np.ndarray, min_range: float, max_range: float, voxel_size: float, scan_max_range: float) -> float:
-        """-> updated scan_max_range; counts in n_cropped / n_map / n_source, clouds behind the *_ptr properties."""
+    def scan(self, points, min_range: float, max_range: float, voxel_size: float, scan_max_range: float, *, stamps=None,
+             delta=None, kitti: bool = False) -> float:
+        """-> updated scan_max_range; counts in n_cropped / n_map / n_source, clouds behind the *_ptr properties.
+        With ``delta`` (Pose3::Logmap of start⁻¹·finish, [ω, v]) the scan is deskewed on the device first
+        (svnicp_prep_scan_deskew, deskew_pointcloud's semantics): ``stamps`` float64 / float32 / uint32 per point, or None;
+        ``kitti`` the KITTI branch.  ``points`` / ``stamps`` may be CUDA torch tensors (SVNICP_MEM_DEVICE: nothing uploaded)."""
         from . import binding
         C = self._C
-        pts = np.ascontiguousarray(np.asarray(points, np.float32)[:, :3])
+        keep = []                                          # host arrays / tensors that must outlive the call
+        pts_ptr, n, mem, up = self._cloud_arg(points, keep)
         smr = C.c_double(float(scan_max_range))
         nc, nm, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        rc = self._L.svnicp_prep_scan(self._h, pts.ctypes.data_as(C.c_void_p), pts.shape[0], 0, float(min_range), float(max_range),
-                                      float(voxel_size), C.byref(smr), C.byref(nc), C.byref(nm), C.byref(ns))
+        if delta is None:
+            if stamps is not None or kitti:
+                raise ValueError("DevicePreprocessor.scan: stamps / kitti need delta")
+            rc = self._L.svnicp_prep_scan(self._h, pts_ptr, n, mem, float(min_range), float(max_range),
+                                          float(voxel_size), C.byref(smr), C.byref(nc), C.byref(nm), C.byref(ns))
+            what = "svnicp_prep_scan"
+        else:
+            st_ptr, st_type, st_up = self._stamps_arg(stamps, n, mem, keep)
+            up += st_up
+            d = np.ascontiguousarray(np.asarray(delta, np.float64).reshape(6))
+            rc = self._L.svnicp_prep_scan_deskew(self._h, pts_ptr, st_ptr, st_type, n, mem, d.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 SVNICP_DESKEW_KITTI if kitti else 0, float(min_range), float(max_range),
+                                                 float(voxel_size), C.byref(smr), C.byref(nc), C.byref(nm), C.byref(ns))
+            what = "svnicp_prep_scan_deskew"
         if rc:
-            raise binding.SvnIcpError(f"svnicp_prep_scan failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+            raise binding.SvnIcpError(f"{what} failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
         self.n_cropped, self.n_map, self.n_source = int(nc.value), int(nm.value), int(ns.value)
-        self.bytes_uploaded = pts.nbytes
+        self.bytes_uploaded = up
         return float(smr.value)
+
+    def _cloud_arg(self, points, keep):
+        """-> (pointer, n, mem_kind, bytes that cross PCIe)"""
+        C = self._C
+        if _is_cuda_tensor(points):
+            import torch
+            t = points.detach().to(torch.float32)[:, :3].contiguous()
+            keep.append(t)
+            return C.c_void_p(t.data_ptr()), int(t.shape[0]), 1, 0
+        pts = np.ascontiguousarray(np.asarray(points, np.float32)[:, :3])
+        keep.append(pts)
+        return pts.ctypes.data_as(C.c_void_p), int(pts.shape[0]), 0, pts.nbytes
+
+    def _stamps_arg(self, stamps, n, mem, keep):
+        """-> (pointer or None, SVNICP_STAMP_*, bytes that cross PCIe); stamps live where the points live (one mem_kind)"""
+        C = self._C
+        if stamps is None:
+            return None, SVNICP_STAMP_F64, 0
+        if _is_cuda_tensor(stamps):
+            import torch
+            codes = {torch.float64: SVNICP_STAMP_F64, torch.float32: SVNICP_STAMP_F32, torch.uint32: SVNICP_STAMP_U32}
+            if mem != 1 or stamps.dtype not in codes:
+                raise ValueError("DevicePreprocessor.scan: CUDA stamps need CUDA points and dtype float64 / float32 / uint32")
+            t = stamps.detach().reshape(-1).contiguous()
+            if t.shape[0] != n:
+                raise ValueError("DevicePreprocessor.scan: one stamp per point")
+            keep.append(t)
+            return C.c_void_p(t.data_ptr()), codes[t.dtype], 0
+        if mem != 0:
+            raise ValueError("DevicePreprocessor.scan: host stamps need host points")
+        st = np.ascontiguousarray(np.asarray(stamps).reshape(-1))
+        codes = {np.dtype(np.float64): SVNICP_STAMP_F64, np.dtype(np.float32): SVNICP_STAMP_F32, np.dtype(np.uint32): SVNICP_STAMP_U32}
+        if st.dtype not in codes:
+            raise ValueError(f"DevicePreprocessor.scan: stamp type {st.dtype} (float64, float32 or uint32)")
+        if st.shape[0] != n:
+            raise ValueError("DevicePreprocessor.scan: one stamp per point")
+        keep.append(st)
+        return st.ctypes.data_as(C.c_void_p), codes[st.dtype], st.nbytes
+
+    def download_deskewed(self) -> np.ndarray:
+        """Every point of the last svnicp_prep_scan_deskew after the deskew, before the crop — float32 rows (test tap)."""
+        from . import binding
+        C = self._C
+        n = C.c_int64(0)
+        rc = self._L.svnicp_prep_download_deskewed(self._h, None, 0, C.byref(n))
+        out = np.zeros((int(n.value), 3), np.float32)
+        if rc == 0 and out.size:
+            rc = self._L.svnicp_prep_download_deskewed(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n))
+        if rc:
+            raise binding.SvnIcpError(f"svnicp_prep_download_deskewed failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+        return out
+
+    @property
+    def deskewed_ptr(self) -> int:
+        return int(self._L.svnicp_prep_deskewed_devptr(self._h) or 0)
 
     @property
     def cropped_ptr(self) -> int:
@@ -392,6 +581,8 @@ class PipelineConfig:
     particle_count: int = 128
     gpu_map: bool = False          # keep the local map in HBM (DeviceVoxelHashMap): the target never crosses PCIe
     gpu_prep: bool = False         # with gpu_map: crop and both uniform samplings on the device (DevicePreprocessor): the raw scan is uploaded, no host pass over the points
+    deskew: bool = False           # deskew_cloud (config/ICP_parameters.yaml:18): motion compensation from the last two poses ahead of the crop (:551-554)
+    kitti: bool = False            # with deskew: the KITTI branch (cloud_topic "/kitti/velo/pointcloud", :385-401) instead of per-point stamps
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
 
@@ -431,16 +622,26 @@ class RegistrationPipeline:
     def _particles(self) -> np.ndarray:
         return initialize_particles(self.cfg.particle_count, PRIOR_UB, PRIOR_LB, self._rng)   # set_initPose, :661-667
 
-    def process_scan(self, points: np.ndarray, stamp: float) -> ScanResult:
+    def process_scan(self, points: np.ndarray, stamp: float, point_stamps=None) -> ScanResult:
+        """point_stamps: the scan's per-point time field (float64 / float32 / uint32), used when cfg.deskew is set."""
         c = self.cfg
         t0 = time.perf_counter()
         dev = c.gpu_map and c.gpu_prep
+        delta = None
+        if c.deskew and len(self.poses) >= 2:                                                                   # :552
+            delta = se3_log(np.linalg.inv(self.poses[-2]) @ self.poses[-1])                                     # :427-432
         if dev:
             if self._prep is None:
                 self._prep = DevicePreprocessor(self.device)
-            self.scan_max_range = self._prep.scan(points, c.min_range, c.max_range, c.voxel_size, self.scan_max_range)  # :556-560
+            if delta is None:
+                self.scan_max_range = self._prep.scan(points, c.min_range, c.max_range, c.voxel_size, self.scan_max_range)  # :556-560
+            else:                                                                                               # :551-560
+                self.scan_max_range = self._prep.scan(points, c.min_range, c.max_range, c.voxel_size, self.scan_max_range,
+                                                      stamps=point_stamps, delta=delta, kitti=c.kitti)
             self.bytes_h2d += self._prep.bytes_uploaded
         else:
+            if delta is not None:
+                points = deskew_pointcloud(points, point_stamps, delta, c.kitti)                               # :553
             cropped, self.scan_max_range = crop_pointcloud(points, c.min_range, c.max_range, self.scan_max_range)   # :556
             to_map = downsample_uniform(cropped, 0.5 * c.voxel_size)                                                # :559
             source = downsample_uniform(to_map, 1.5 * c.voxel_size)                                                 # :560

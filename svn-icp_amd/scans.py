@@ -129,6 +129,71 @@ def lidar_scan(scene: Scene, R: np.ndarray, t: np.ndarray, n_points: int, stream
     return pts[:n_points].astype(np.float32).astype(np.float64)
 
 
+def _raycast_rows(scene: Scene, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
+    """_raycast with one origin per ray (origins [N,3]): the scan of a moving sensor."""
+    n = dirs.shape[0]
+    t_best = np.full(n, np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = (scene.ground_z - origins[:, 2]) / dirs[:, 2]
+        t_best = np.where((t > 0) & (t < t_best), t, t_best)
+        for axis, half in ((0, scene.half_x), (1, scene.half_y)):
+            for sgn in (-1.0, 1.0):
+                t = (sgn * half - origins[:, axis]) / dirs[:, axis]
+                t_best = np.where((t > 0) & (t < t_best), t, t_best)
+        inv = 1.0 / dirs
+        for c0 in range(0, n, 32768):
+            sl = slice(c0, c0 + 32768)
+            t0 = (scene.boxes_lo[None, :, :] - origins[sl, None, :]) * inv[sl, None, :]
+            t1 = (scene.boxes_hi[None, :, :] - origins[sl, None, :]) * inv[sl, None, :]
+            tn = np.minimum(t0, t1).max(axis=2)
+            tf = np.maximum(t0, t1).min(axis=2)
+            hit = (tf >= tn) & (tf > 0)
+            tb = np.where(hit, np.where(tn > 0, tn, tf), np.inf).min(axis=1)
+            t_best[sl] = np.minimum(t_best[sl], tb)
+    return t_best
+
+
+@dataclass
+class Sweep:
+    points: np.ndarray      # [n,3] float32-rounded float64, sensor frame at each point's firing time
+    stamps: np.ndarray      # [n] float64 seconds: t0 + s_c * period
+    stamps_ns: np.ndarray   # [n] uint32 nanoseconds since the start of the sweep: round(s_c * period * 1e9)
+    world: np.ndarray       # [n,3] float64 world hit points (the exact ray hits when noise = 0)
+    s: np.ndarray           # [n] normalised firing time s_c of each point
+
+
+def lidar_sweep(scene: Scene, T_mid: np.ndarray, delta6, n_points: int, stream: int, seed: int = SEED, noise: float = 0.02,
+                period: float = 0.1, t0: float = 0.0) -> Sweep:
+    """One sweep of a spinning 64-beam LiDAR that MOVES while it turns: column c fires at normalised time
+    s_c = (c + 0.5) / cols from the sensor pose T(s_c) = T_mid · Exp((s_c − 0.5)·delta6) (delta6 = [omega, v], the motion over
+    one period, gtsam Pose3::Expmap convention).  Same beams, column order and noise stream as lidar_scan; each point is returned
+    in the sensor frame of its own firing time — the skewed scan a deskew (OdometryPipeline.cpp:357-447) corrects."""
+    from .pipeline import se3_exp
+    T_mid = np.asarray(T_mid, float)
+    delta6 = np.asarray(delta6, float).reshape(6)
+    cols = max(1, n_points // 64)
+    el = np.deg2rad(np.linspace(-24.8, 2.0, 64))
+    az = (np.arange(cols) + 0.5) * (2.0 * math.pi / cols)
+    azg, elg = np.meshgrid(az, el, indexing="ij")  # column-major firing order
+    d_s = np.stack([np.cos(elg) * np.cos(azg), np.cos(elg) * np.sin(azg), np.sin(elg)], -1).reshape(-1, 3)
+    s_col = (np.arange(cols) + 0.5) / cols
+    Ts = np.stack([T_mid @ se3_exp((s - 0.5) * delta6) for s in s_col])         # [cols,4,4]
+    Rs = np.repeat(Ts[:, :3, :3], 64, axis=0)
+    ts = np.repeat(Ts[:, :3, 3], 64, axis=0)
+    d_w = np.einsum("nij,nj->ni", Rs, d_s)
+    rng = _raycast_rows(scene, ts, d_w)
+    rng = rng + noise * normal01(stream, rng.shape[0], seed)
+    rng = np.clip(rng, 1.0, 100.0)
+    pts = d_s * rng[:, None]
+    world = ts + d_w * rng[:, None]
+    s = np.repeat(s_col, 64)
+    if pts.shape[0] < n_points:  # n_points not a multiple of 64: repeat the head
+        k = n_points - pts.shape[0]
+        pts, world, s = (np.concatenate([a, a[:k]], 0) for a in (pts, world, s))
+    pts, world, s = pts[:n_points], world[:n_points], s[:n_points]
+    return Sweep(pts.astype(np.float32).astype(np.float64), t0 + s * period, np.round(s * period * 1e9).astype(np.uint32), world, s)
+
+
 @dataclass
 class ScanPair:
     source: np.ndarray      # [B,3] sensor frame of the displaced pose
