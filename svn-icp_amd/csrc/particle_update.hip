@@ -1585,6 +1585,7 @@ hipError_t launch_small_registration(const AccumPlan& plan, AccumArgs a, const U
     s.spts_per_block = (int)spb;
     s.GS = (int)((a.B + spb - 1) / spb);
   }
+  if (!search_offsets_fit(a.Ppad, a.K)) return hipErrorInvalidValue;   // search_limits.hpp
   const int n_prep = (P + PREP_PW - 1) / PREP_PW + ((!u.svgd && !u.full_grad) ? 1 : 0);
   const int n_dir = (P + 3) / 4;
   int grid = s.GS + 1;

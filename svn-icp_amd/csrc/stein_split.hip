@@ -157,6 +157,7 @@ hipError_t launch_build_table3(const int32_t* idx, int64_t B, int K, const doubl
 // search kernel, then (launch_accumulate_split) the accumulation kernel; api.hip brackets them separately
 hipError_t launch_search_split(const AccumPlan& plan, AccumArgs a, hipStream_t st) {
   a.Ppad = plan.Ppad; a.pts_per_block = plan.pts_per_block; a.spts_per_block = plan.spts_per_block;
+  if (!search_offsets_fit(a.Ppad, a.K)) return hipErrorInvalidValue;   // search_limits.hpp
   switch (plan.PW) {
     case 16: return launch_srb<16, 1>(plan, a, st);
     case 32: return launch_srb<32, 1>(plan, a, st);

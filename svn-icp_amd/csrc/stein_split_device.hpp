@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include "kernels.hpp"
 #include "stein_common.hpp"
+#include "search_limits.hpp"
 
 namespace svnicp {
 
@@ -87,10 +88,10 @@ __device__ __forceinline__ bf8 split_a3(float x) {   // [a1 a1 | a1 a2 | a2 a3 |
   return __builtin_bit_cast(bf8, t);
 }
 __device__ __forceinline__ bf8 split_b3(float x) {   // [b1 b2 | b3 b1 | b2 b1 | 0 0]
-  const unsigned int r0 = cvt_pk_bf16(x, x);
-  const float e1 = x - __uint_as_float(r0 & 0xffff0000u);
+  // cvt_pk_bf16(0, v) is the bf16 rounding of v as a float (high half, zero low half): no mask needed
+  const float e1 = x - __uint_as_float(cvt_pk_bf16(0.0f, x));
+  const float e2 = e1 - __uint_as_float(cvt_pk_bf16(0.0f, e1));
   const unsigned int q0 = cvt_pk_bf16(x, e1);
-  const float e2 = e1 - __uint_as_float(q0 & 0xffff0000u);
   const unsigned int q1 = cvt_pk_bf16(e2, x);
   const unsigned int q2 = cvt_pk_bf16(e1, x);
   const u4v t = {q0, q1, q2, 0u};
@@ -170,10 +171,10 @@ constexpr float kEpsBf16 = (float)SVNICP_SEARCH_EPS_U * 5.9604644775390625e-08f;
 // (16·rb + 4·mk + 0..3) of one particle: a tile.  Keeping the smallest and second smallest of all 24 scores of a lane cost
 // 32 slow-class + 24 tag instructions per column block — measured (timing-only builds): the second minimum alone was 31 % of
 // the kernel, the per-score tags 11 %.  Now a lane keeps the minimum of each tile (v_min3 + v_min), tags the six TILE minima
-// (3 bits row block, 2 bits lane group) and tracks the smallest and second smallest tile minimum: 19 slow + 6 tags per column
-// block.  That decides between tiles; inside the winning tile the lane that owns the particle scores the four candidates
-// itself, one step later, from an array-of-rows copy of the table (tablef: 64 contiguous bytes per lane, requested at the end
-// of the step, consumed after the next step's transform), in float32 FMAs on the same inputs:
+// (4·row block + lane group in the low five bits: the tile's own index) and tracks the smallest and second smallest tile
+// minimum: 19 slow + 6 tags per column block.  That decides between tiles; inside the winning tile the lane that owns the
+// particle scores the four candidates itself from the point's LDS copy of the rows (s_rows, written from the A operands),
+// in float32 FMAs on the same inputs:
 //   (a) inside the tile: packed VALU scores v1 < v2 (2 tag bits, 3 ulp) with v2 − v1 > 2·EPS + 2^-21(|v1| + |v2|): each
 //       VALU score is within EPS of the exact score (inputs (i), three roundings <= 3.01u·Σ|products|, (iv)), so the tile's
 //       other three candidates are strictly farther in exact arithmetic than the VALU argmin t*;
@@ -222,7 +223,11 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
   constexpr int ST = 4 * BW;       // source points between two steps of a wave (four waves along the points)
   constexpr bool PIPE = NPT == 1;  // one point per step: its table rows are fetched a step ahead
   constexpr int NTILE = 4 * NRB + (TAIL ? 1 : 0);   // tiles of four consecutive candidates per source point
-  __shared__ float4 s_rows[4][NPT][4][NTILE];   // per wave and point: row k = (c'x, c'y, c'z, |c'|²) at [k & 3][k >> 2]
+  // per wave and point: four planes (c'x, c'y, c'z, |c'|²), candidate k at float k of a plane, so that one float4 of a plane
+  // is one component of a whole tile.  The plane stride RS is an ODD multiple of 16 floats: the 64 lanes of a row-block store
+  // (component mk, candidate 16·rb + mj) then hit 16·(odd·mk mod 4) + mj = 64 different banks.
+  constexpr int RS = 16 * (((4 * NTILE + 15) / 16) | 1);
+  __shared__ float4 s_rows[4][NPT][4][RS / 4];
   __shared__ float4 s_scr4[4][64];       // per wave: (−2x', 1) of each particle lane of the group in flight
   __shared__ double s_pose[WP][12][64];  // the lanes' total poses, re-read every step: 24 VGPRs less than keeping them
   __shared__ unsigned int s_queue[kQueueCap];   // undecided pairs: (point − blk_lo) << 8 | particle lane of the workgroup
@@ -246,14 +251,16 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
   const SVNICP_CONST_AS v4f* ctab = (const SVNICP_CONST_AS v4f*)a.tablea;
   // LDS copy of a point's rows, written from the A-operand registers: lane (mj, mk) holds component mk of candidates
   // 16·rb + mj — one 4-byte store per row block
-  float* const rows_w = reinterpret_cast<float*>(&s_rows[wave][0][mj & 3][mj >> 2]) + mk;
+  float* const rows_w = reinterpret_cast<float*>(&s_rows[wave][0][mk][0]) + mj;
   const int64_t blk_lo = (int64_t)bx * a.spts_per_block;
   const int64_t blk_hi = (blk_lo + a.spts_per_block < a.B) ? blk_lo + a.spts_per_block : a.B;
+  static_assert(BW <= kSearchPointsPerStep, "search_limits.hpp bounds the pair offsets for at most this many points per step");
   __syncthreads();
   const int64_t nfirst = blk_lo + wave * BW;
 
   int pend_idx = 0;       // winner's target index of the previous step, stored one step late (see the end of the step)
-  size_t pend_off = 0;
+  int32_t* pend_row = a.kidx;   // wave-uniform: the kidx row of the step's first point (+ pbase) …
+  unsigned int pend_off4 = 0;    // … and the lane's 32-bit BYTE offset from it (search_limits.hpp)
   bool pend_have = false;
   v4f alo_n, ahi_n;   // PIPE: table rows of the NEXT step, in flight while this step's tiles run
   // … and the next point's source row, local origin and C2 — as VECTOR loads (lanes 0-2, 3-5: one double each; every lane:
@@ -318,11 +325,11 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
         const float v = rb == 0 ? alo.x : rb == 1 ? alo.y : rb == 2 ? alo.z : rb == 3 ? alo.w
                       : rb == 4 ? ahi.x : rb == 5 ? ahi.y : rb == 6 ? ahi.z : ahi.w;
         afr[rb] = split_a3(v);
-        rows_w[(pt * 4 * NTILE + 4 * rb) * 4] = v;   // row 16·rb + mj lives at [(mj & 3)][4·rb + (mj >> 2)]
+        rows_w[pt * 4 * RS + 16 * rb] = v;
       }
       if constexpr (TAIL) {   // candidates 16·NRB … +3 sit in row block NRB of the table (lanes mj < 4): the tile the owner lanes score
         const float v = NRB == 4 ? ahi.x : NRB == 5 ? ahi.y : NRB == 6 ? ahi.z : ahi.w;
-        if (mj < 4) rows_w[(pt * 4 * NTILE + 4 * NRB) * 4] = v;
+        if (mj < 4) rows_w[pt * 4 * RS + 16 * NRB] = v;
       }
     };
     if constexpr (PIPE) {
@@ -379,11 +386,13 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
         bool have_m = false;   // (m1, m2) hold a pair
         bool have_p = false;   // (wp, rp) hold a pair waiting for its partner
         v4f dcur = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[0], bfr, zero, 0, 0, 0);
+        v4f dnext = dcur;
+        if (NRB > 1) dnext = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[NRB > 1 ? 1 : 0], bfr, zero, 0, 0, 0);
 #pragma unroll
-        for (int rb = 0; rb < NRB; ++rb) {  // tile rb+1 goes to the matrix pipe before the VALU consumes tile rb
-          v4f dnext = dcur;
-          if (rb + 1 < NRB) dnext = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[rb + 1], bfr, zero, 0, 0, 0);
-          const float pk = pack_slot3(fmin_raw(fmin3_raw(dcur[0], dcur[1], dcur[2]), dcur[3]), (unsigned int)rb);
+        for (int rb = 0; rb < NRB; ++rb) {  // tiles rb+1, rb+2 go to the matrix pipe before the VALU consumes tile rb
+          v4f dn2 = dnext;
+          if (rb + 2 < NRB) dn2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[rb + 2 < NRB ? rb + 2 : 0], bfr, zero, 0, 0, 0);
+          const float pk = pack_slot3(fmin_raw(fmin3_raw(dcur[0], dcur[1], dcur[2]), dcur[3]), 4u * rb);
           if (np == 0) { pend0 = pk; np = 1; }
           else if (np == 1) { pend1 = pk; np = 2; }
           else {
@@ -403,7 +412,7 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
               }
             }
           }
-          dcur = dnext;
+          dcur = dnext; dnext = dn2;
         }
         // what is left over when NRB is not a multiple of six
         if (!have_m) { m1 = __builtin_huge_valf(); m2 = __builtin_huge_valf(); }
@@ -417,7 +426,7 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
       // its own entry and its row partner's; after v_permlane32_swap on those two results lane group mk holds both halves of
       // column block mk.  Six swaps, no copies, no selects; the result lands in the lane that owns the particle.
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) b1[cb] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(b1[cb]), 0x18u, (unsigned int)mk << 3, 0xBA));
+      for (int cb = 0; cb < 4; ++cb) b1[cb] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(b1[cb]), 3u, (unsigned int)mk, 0xBA));
       auto merge2 = [&](float p1, float q1, float p2, float q2, float& o1, float& o2) {
         o1 = fmin_raw(p1, q1);
         o2 = fmin_raw(fmax_raw(p1, q1), fmin_raw(p2, q2));
@@ -435,44 +444,47 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
         const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(h2[0]), __float_as_uint(h2[1]), false, false);
         merge2(__uint_as_float(r1[0]), __uint_as_float(r1[1]), __uint_as_float(r2[0]), __uint_as_float(r2[1]), b1own, b2own);
       }
+      // the four candidates of tile `tile` scored by this lane from the LDS planes, in float32 FMAs on the matrix pipe's inputs
+      // (a finite sentinel past K).  Each plane's float4 is one component of the four candidates: the pairs of scores are
+      // packed FMAs on registers as they arrive, with no copies to pair them up.
+      auto score_tile = [&](int tile, float* sc) {
+        const float4 cx = s_rows[wave][bs][0][tile], cy = s_rows[wave][bs][1][tile];
+        const float4 cz = s_rows[wave][bs][2][tile], cc = s_rows[wave][bs][3][tile];
+        sc[0] = __builtin_fmaf(cx.x, mm0, __builtin_fmaf(cy.x, mm1, __builtin_fmaf(cz.x, mm2, cc.x)));
+        sc[1] = __builtin_fmaf(cx.y, mm0, __builtin_fmaf(cy.y, mm1, __builtin_fmaf(cz.y, mm2, cc.y)));
+        sc[2] = __builtin_fmaf(cx.z, mm0, __builtin_fmaf(cy.z, mm1, __builtin_fmaf(cz.z, mm2, cc.z)));
+        sc[3] = __builtin_fmaf(cx.w, mm0, __builtin_fmaf(cy.w, mm1, __builtin_fmaf(cz.w, mm2, cc.w)));
+      };
       if constexpr (TAIL) {   // candidates 16·NRB … +3: one more tile (row block NRB of lane group 0), scored by the owner lane
-        const float4* tl = &s_rows[wave][bs][0][4 * NRB];   // rows 16·NRB + t at [t][4·NRB]: the same address in every lane (broadcast)
         float sc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const float4 c = tl[t * NTILE];  // (c'x, c'y, c'z, |c'|²), a finite sentinel past K
-          sc[t] = __builtin_fmaf(c.x, mm0, __builtin_fmaf(c.y, mm1, __builtin_fmaf(c.z, mm2, c.w)));
-        }
-        const float pk = pack_slot(fmin_raw(fmin3_raw(sc[0], sc[1], sc[2]), sc[3]), 0x1fu, (unsigned int)NRB);
+        score_tile(4 * NRB, sc);   // the same address in every lane (broadcast)
+        const float pk = pack_slot3(fmin_raw(fmin3_raw(sc[0], sc[1], sc[2]), sc[3]), 4u * NRB);
         b2own = fmed3_raw(b1own, b2own, pk);
         b1own = fmin_raw(b1own, pk);
       }
 
       const int pin = g * PW + pl;                        // particle lane inside the workgroup
       const bool valid = inb && (a.p_lo + pbase + pin) < a.p_hi;
-      const unsigned int wbits = __float_as_uint(b1own);
-      int tile = (int)(((wbits & 7u) << 2) | ((wbits >> 3) & 3u));    // 4·rb + mk: candidates 4·tile … 4·tile + 3
+      int tile = (int)(__float_as_uint(b1own) & 31u);   // the tag is 4·rb + mk: candidates 4·tile … 4·tile + 3
       tile = tile < NTILE ? tile : NTILE - 1;                         // (a NaN's tag bits are anything: stay inside the rows)
       const float thr = 2.0f * E + 3.83e-06f * (__builtin_fabsf(b1own) + __builtin_fabsf(b2own)) + 1.0e-30f;   // 2^-18 and a little
       const bool tiles_ok = b2own - b1own > thr;
       // inside the winning tile: the four candidates scored by this lane from the LDS rows, tagged with two bits
       float pk4[4];
       {
-        const float4* rt = &s_rows[wave][bs][0][tile];
         if constexpr (!PIPE) __builtin_amdgcn_wave_barrier();
+        float sc[4];
+        score_tile(tile, sc);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const float4 r = rt[t * NTILE];
-          const float sc = __builtin_fmaf(r.x, mm0, __builtin_fmaf(r.y, mm1, __builtin_fmaf(r.z, mm2, r.w)));
-          pk4[t] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(sc), 3u, (unsigned int)t, 0xBA));
-        }
+        for (int t = 0; t < 4; ++t) pk4[t] = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(sc[t]), 3u, (unsigned int)t, 0xBA));
       }
       const float w3 = fmin3_raw(pk4[0], pk4[1], pk4[2]), r3 = fmed3_raw(pk4[0], pk4[1], pk4[2]);
       const float v1 = fmin_raw(w3, pk4[3]), v2 = fmed3_raw(w3, r3, pk4[3]);
       const float thrv = 2.0f * E + 4.76837158203125e-07f * (__builtin_fabsf(v1) + __builtin_fabsf(v2)) + 1.0e-30f;   // 2^-21
       int kb = 4 * tile + (int)(__float_as_uint(v1) & 3u);
-      const bool ambiguous = valid && (!tiles_ok || !(v2 - v1 > thrv) || kb >= K);
-      kb = kb < K ? kb : 0;
+      // non-short-circuit: one lane mask, no branch and no mask -> register -> mask round trip (v_cndmask issues at ~1/5 rate)
+      const bool ambiguous = valid & (!tiles_ok | !(v2 - v1 > thrv) | (kb >= K));
+      kb = kb < K ? kb : K - 1;   // an undecided pair's byte and index are rewritten by the exact pass: only stay in the row
       unsigned long long am = __ballot(ambiguous);
       if (am) {  // rare (about one wave step in ten, a lane or two each): queue the undecided pairs for the exact pass below
         const int cnt = __builtin_popcountll(am);
@@ -496,18 +508,23 @@ __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) 
       // the winner's slot byte, and its target index for the accumulate kernel (one dependent load less over there).  The
       // index is a scattered load: it is STORED one step later, so that its latency hides behind the next step's tiles
       // (an undecided pair's two entries are rewritten by the exact pass)
-      if (pend_have) a.kidx[pend_off] = pend_idx;
+      // (64-bit row bases of the step's first point n are wave-uniform — scalar arithmetic; the lanes add 32-bit BYTE offsets,
+      // below 2^32 by search_limits.hpp, which the launchers check: the stores and the load take the scalar-base form)
+      if (pend_have) *(int32_t*)((char*)pend_row + pend_off4) = pend_idx;
       pend_have = inb;
+      pend_row = a.kidx + n * a.Ppad + pbase;   // (outside the branch: stays uniform)
       if (inb) {
-        pend_off = (size_t)b * a.Ppad + (pbase + pin);
-        a.kbest[pend_off] = (uint8_t)kb;
-        pend_idx = a.cand[(size_t)b * K + kb];
+        const unsigned int bl = (unsigned int)bs;   // b − n
+        const unsigned int off = bl * (unsigned int)a.Ppad + (unsigned int)pin;
+        (a.kbest + n * a.Ppad + pbase)[off] = (uint8_t)kb;
+        pend_off4 = 4u * off;
+        pend_idx = *(const int32_t*)((const char*)(a.cand + n * K) + 4u * (bl * (unsigned int)K + (unsigned int)kb));
       }
     }
     __builtin_amdgcn_wave_barrier();  // scratch is rewritten by the next step
   }
 
-  if (pend_have) a.kidx[pend_off] = pend_idx;
+  if (pend_have) *(int32_t*)((char*)pend_row + pend_off4) = pend_idx;
   // exact pass over the queued pairs: 32 lanes per pair, all waves of the workgroup, no lane waits for another pair
   __syncthreads();
   {
