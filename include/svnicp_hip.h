@@ -290,6 +290,68 @@ const float *svnicp_prep_deskewed_devptr(svnicp_prep *prep);   /* float32 [n][3]
 int svnicp_prep_download_deskewed(svnicp_prep *prep, float *out_xyz, int64_t cap_points, int64_t *n_out);   /* test tap; valid
                                                                  until the next svnicp_prep_scan_deskew */
 
+/* ---- range-image segmentation of a raw scan: LeGO-LOAM ImageProjection::cloudHandler (include/segmentation/ImageProjection.h)
+ * OdometryPipeline::lidar_msg_cb (:328-355) runs it on every raw scan when USE_Segmentation is set (declared true, :180; off
+ * in the shipped yamls) and hands GetSegmentedCloudPure() on, which returns segmentedCloud_ (:533-534).  Steps:
+ *   input       (:240)      points with a non-finite coordinate are dropped; input order and input indices are kept.
+ *   projection  (:281-325)  va = float(double(atan2f(z, sqrtf(x*x+y*y)) * 180.0f) / M_PI), q = (va + ang_bottom) / ang_res_y
+ *                           (float); q is converted to size_t as on x86-64: q in (-1, 0) is row 0, q <= -1 or trunc(q) >=
+ *                           n_scan drops the point.  h = float(double(atan2f(x, y) * 180.0f) / M_PI), col = -round((double(h)
+ *                           - 90) / double(ang_res_x)) + horizon_scan / 2 (double, C round); col >= H: col -= H; a negative
+ *                           or still too large col drops the point.  r = sqrtf(x*x + y*y + z*z); r < min_range drops it.
+ *                           Several points in one pixel: the LAST in input order wins (xyz and range).
+ *   ground      (:329-374)  rows 0..ground_scan_ind; pair (r, r+1) of a column is valid when both are filled and flat when
+ *                           fabsf(float(double(atan2f(dz, sqrtf(dx*dx+dy*dy)) * 180.0f) / M_PI) - mount_angle) <= 10.  The
+ *                           loop's overwrites give: ground(r) = -1 if r < G and pair (r, r+1) is invalid, else 1 if pair
+ *                           (r, r+1) or (r-1, r) is flat, else 0.
+ *   components  (:379-383, :435-531)  4-neighbour graph on the pixels that are filled and not ground (label 0); columns wrap,
+ *                           rows do not; an edge when atan2f(d2*sin(a), d1 - d2*cos(a)) > segment_theta (d1 / d2 the larger /
+ *                           smaller range, a = ang_res / 180 * pi of that direction).  A component (BFS from its row-major
+ *                           first pixel) is valid with >= 30 pixels, or with >= valid_point_num pixels on >= valid_line_num
+ *                           rows counting every member but the seed (lineCountFlag is set on push, :501).  Valid components
+ *                           are labelled 1, 2, ... in seed order, the others 999999.
+ *   output      (:384-414)  pixels row-major; kept when (label > 0 or ground == 1) and label != 999999, ground pixels only
+ *                           at j % 5 == 0, j <= 5 or j >= H - 5: the winning point's xyz and its input index.
+ * Deliberate deviation: every atan2f / sinf / cosf above is the float64 function of the float32 operands rounded once to
+ * float32 (sin / cos of the alphas on the host); everything else is IEEE + - * / sqrt with -ffp-contract=off.  Host libms'
+ * atan2f are not correctly rounded and disagree with each other, so this fixes one rule that the device and both host
+ * restatements (pipeline.py / registration_pipeline.hpp: segment_scan) follow bit for bit; a decision can differ from a
+ * glibc build of the reference only where a value lies within one float ulp of a threshold.
+ * Device form (csrc/range_segment.hip): owner image by atomicMax of the input index, per-pixel ground / label-init, union-
+ * find with minimum-index roots (the root of a component is its BFS seed, independent of scheduling), per-root size and row
+ * mask, validity and labels by an exclusive scan, a stable compaction.  One host synchronisation, at the end.
+ * The segmented buffers are the prep object's own: they may be passed to svnicp_prep_scan / svnicp_prep_scan_deskew with
+ * SVNICP_MEM_DEVICE (those calls never write them); valid until the next svnicp_prep_segment.  The per-point stamps of the
+ * raw message do not survive: segmentedCloud_ is PointXYZI, and the deskew that follows finds no time field (:363-381). */
+typedef struct svnicp_seg_params {
+  int32_t struct_size;           /* = sizeof(svnicp_seg_params) */
+  int32_t n_scan, horizon_scan, ground_scan_ind;   /* N_SCAN, Horizon_SCAN, groundScanInd (:63-68) */
+  float ang_res_x, ang_res_y, ang_bottom;          /* degrees */
+  float min_range, mount_angle, segment_theta;     /* sensorMinimumRange, sensorMountAngle (deg), segmentTheta (rad) (:112-114) */
+  int32_t valid_point_num, valid_line_num;         /* segmentValidPointNum, segmentValidLineNum (:115-116) */
+} svnicp_seg_params;
+/* the sensor blocks of ImageProjection.h:46-110 */
+#define SVNICP_SEG_VLP16 0
+#define SVNICP_SEG_HDL32E 1
+#define SVNICP_SEG_HDL64E 2     /* the one the header compiles in */
+#define SVNICP_SEG_VLS128 3
+#define SVNICP_SEG_RS32 4
+#define SVNICP_SEG_OS1_16 5
+#define SVNICP_SEG_OS1_64 6
+#define SVNICP_SEG_OS0_128 7
+int svnicp_seg_default_params(int sensor, svnicp_seg_params *out);   /* no device needed; SVNICP_ERR_INVALID for an unknown id */
+/* SVNICP_ERR_INVALID (nothing enqueued) unless 1 <= ground_scan_ind < n_scan <= 128, horizon_scan >= 1, n_scan * horizon_scan
+ * <= 2^19, finite positive ang_res_x / ang_res_y, finite ang_bottom / min_range / mount_angle / segment_theta and a matching
+ * struct_size.  params NULL = HDL-64E. */
+int svnicp_prep_segment(svnicp_prep *prep, const float *xyz, int64_t n, int mem_kind, const svnicp_seg_params *params,
+                        int64_t *n_segmented);
+const float *svnicp_prep_segmented_devptr(svnicp_prep *prep);          /* float32 [n_segmented][3] */
+const int32_t *svnicp_prep_segmented_index_devptr(svnicp_prep *prep);  /* int32 [n_segmented]: input index of each point */
+int svnicp_prep_download_segmented(svnicp_prep *prep, float *out_xyz, int32_t *out_index, int64_t cap_points, int64_t *n_out);
+int svnicp_prep_download_seg_images(svnicp_prep *prep, int32_t *owner, float *range, int8_t *ground, int32_t *label,
+                                    int64_t cap_pixels);   /* test taps: row-major [n_scan][horizon_scan] of the last call; owner
+                                                              -1 / range -100000 = empty; label as labelMat_ (-1, 1.., 999999) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,14 @@ class Params(C.Structure):
                 ("svn_full_grad", C.c_int32), ("optimizer", C.c_int32), ("record_trace", C.c_int32)]
 
 
+class SegParamsStruct(C.Structure):
+    """struct svnicp_seg_params (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_scan", C.c_int32), ("horizon_scan", C.c_int32), ("ground_scan_ind", C.c_int32),
+                ("ang_res_x", C.c_float), ("ang_res_y", C.c_float), ("ang_bottom", C.c_float), ("min_range", C.c_float),
+                ("mount_angle", C.c_float), ("segment_theta", C.c_float), ("valid_point_num", C.c_int32),
+                ("valid_line_num", C.c_int32)]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -100,6 +108,13 @@ def load_library():
     L.svnicp_prep_deskewed_devptr.argtypes = [vp]
     L.svnicp_prep_deskewed_devptr.restype = vp
     L.svnicp_prep_download_deskewed.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.svnicp_seg_default_params.argtypes = [C.c_int, C.POINTER(SegParamsStruct)]
+    L.svnicp_prep_segment.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(SegParamsStruct), C.POINTER(C.c_int64)]
+    for name in ("svnicp_prep_segmented_devptr", "svnicp_prep_segmented_index_devptr"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = vp
+    L.svnicp_prep_download_segmented.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.svnicp_prep_download_seg_images.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     L.svnicp_set_initial_mean.argtypes = [vp, dp, dp]
     L.svnicp_set_k.argtypes = [vp, C.c_int]
     L.svnicp_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]

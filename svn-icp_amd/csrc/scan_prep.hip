@@ -37,25 +37,11 @@
 
 #include "../../include/svnicp_hip.h"
 #include "kernels.hpp"
+#include "prep_state.hpp"
 
 namespace {
 
-template <typename T>
-struct PBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    if (cap > 0) n += n / 2;   // scans vary in size: do not re-allocate for every small growth
-    p = nullptr; cap = 0;
-    if (n == 0) n = 1;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+using svnicp_prep_detail::PBuf;
 
 __device__ __forceinline__ unsigned long long enc_f64(double v) {   // order-preserving double -> uint64
   const long long b = __double_as_longlong(v);
@@ -301,25 +287,6 @@ std::string g_prep_error;
 
 }  // namespace
 
-struct svnicp_prep {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  PBuf<float> in, cropped, map_cloud, source;
-  PBuf<double> source64;
-  PBuf<int> keep, off, idx, sidx, flag, pre, run_pos;
-  PBuf<unsigned long long> key, skey, d2bits, run_min, scal;   // scal: [0] max squared norm (encoded) [1..6] grid bounds
-  PBuf<char> tmp;
-  int64_t n_cropped = 0, n_map = 0, n_source = 0;
-  // svnicp_prep_scan_deskew: deskewed points (every point, kept), KITTI-corrected scratch, stamps as double, uploaded stamps,
-  // dscal: [0] max squared norm (encoded) [1] max stamp (encoded) [2] min stamp (complement of the encoding)
-  PBuf<float> deskewed, kpts;
-  PBuf<double> st;
-  PBuf<char> stamps_in;
-  PBuf<unsigned long long> dscal;
-  int64_t n_deskewed = 0;
-};
-
 namespace {
 
 int pfail(svnicp_prep* p, int code, const std::string& msg) { if (p) p->err = msg; else g_prep_error = msg; return code; }
@@ -406,6 +373,7 @@ void svnicp_prep_destroy(svnicp_prep* p) {
   p->idx.release(); p->sidx.release(); p->flag.release(); p->pre.release(); p->run_pos.release(); p->key.release(); p->skey.release();
   p->d2bits.release(); p->run_min.release(); p->scal.release(); p->tmp.release();
   p->deskewed.release(); p->kpts.release(); p->st.release(); p->stamps_in.release(); p->dscal.release();
+  p->seg.release();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }

@@ -2,8 +2,9 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1]
-//     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554)
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1]
+//     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
+//      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -31,6 +32,7 @@ int main(int argc, char** argv) {
   cfg.gpu_map = argc > 8 && atoi(argv[8]) != 0;
   cfg.gpu_prep = argc > 8 && atoi(argv[8]) >= 2;
   cfg.deskew = argc > 9 && atoi(argv[9]) != 0;
+  cfg.segmentation = argc > 10 && atoi(argv[10]) != 0;
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;

@@ -10,6 +10,8 @@
 // The Python module svn-icp_amd/pipeline.py is the same sequence and serves as the cross-check in the tests.
 // With PipelineConfig::deskew the scan is first motion-compensated as OdometryPipeline::deskew_pointcloud does (:357-447,
 // run when the pose buffer holds two poses, :551-554); see deskew_pointcloud below.
+// With PipelineConfig::segmentation the raw scan is first range-image segmented as ImageProjection::cloudHandler does
+// (USE_Segmentation, :328-355); see segment_scan below.
 //
 // Where PCL / the hash map leave an order unspecified (iteration order of occupied leaves / voxels) this code emits
 // ascending leaf / voxel index; the solver's result does not depend on the order of the target points except through
@@ -249,6 +251,141 @@ inline Cloud downsample_uniform(const Cloud& in, double radius) {
   return out;
 }
 
+// ------------------------------------------------------------------------------------------------ range-image segmentation
+// LeGO-LOAM's ImageProjection::cloudHandler (include/segmentation/ImageProjection.h), which OdometryPipeline::lidar_msg_cb runs
+// on every raw scan when USE_Segmentation is set (:328-355); the pipeline consumes segmentedCloud_ (GetSegmentedCloudPure,
+// :533-534).  The contract is written out in include/svnicp_hip.h; the same float32 / float64 steps are in pipeline.py
+// (segment_scan) and csrc/range_segment.hip.  Deliberate deviation: atan2f / sinf / cosf are the float64 functions of the float32
+// operands rounded once.  The components are found by the reference's own BFS (labelComponents, :435-531).
+struct SegImages {
+  std::vector<int32_t> owner;    // winning input index per pixel, -1 empty
+  std::vector<float> range;      // rangeMat_, -100000 empty
+  std::vector<int8_t> ground;    // groundMat_
+  std::vector<int32_t> label;    // labelMat_
+};
+
+namespace seg_detail {
+constexpr double kPi = 3.14159265358979323846;
+inline float atan2_f32(float y, float x) { return (float)std::atan2((double)y, (double)x); }
+inline float deg_f32(float a) { return (float)((double)(a * 180.0f) / kPi); }
+}  // namespace seg_detail
+
+// the sensor ImageProjection.h compiles in (HDL-64E, :63-68) and the constants of :112-116 (= svnicp_seg_default_params(SVNICP_SEG_HDL64E))
+inline svnicp_seg_params seg_hdl64e_params() {
+  svnicp_seg_params s;
+  s.struct_size = (int32_t)sizeof(svnicp_seg_params);
+  s.n_scan = 64; s.horizon_scan = 2250; s.ground_scan_ind = 7;
+  s.ang_res_x = (float)(360.0 / float(2250)); s.ang_res_y = (float)(26.8 / float(64 - 1)); s.ang_bottom = (float)24.8;
+  s.min_range = 1.0f; s.mount_angle = 0.0f; s.segment_theta = (float)(60.0 / 180.0 * seg_detail::kPi);
+  s.valid_point_num = 5; s.valid_line_num = 3;
+  return s;
+}
+
+inline SegImages segment_images(const Cloud& pts, const svnicp_seg_params& prm) {
+  using namespace seg_detail;
+  const int N = prm.n_scan, H = prm.horizon_scan, G = prm.ground_scan_ind;
+  const size_t NP = (size_t)N * H;
+  SegImages im;
+  im.owner.assign(NP, -1);
+  im.range.assign(NP, -100000.0f);
+  im.ground.assign(NP, 0);
+  im.label.assign(NP, 0);
+  for (size_t i = 0; i < pts.size(); ++i) {                                  // projectPointCloud (:281-325)
+    const float x = pts[i][0], y = pts[i][1], z = pts[i][2];
+    if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;   // removeNaNFromPointCloud (:240)
+    const float va = deg_f32(atan2_f32(z, std::sqrt(x * x + y * y)));
+    const float q = (va + prm.ang_bottom) / prm.ang_res_y;
+    if (!(q > -1.0f && q < (float)N)) continue;                              // size_t conversion as on x86-64
+    const int row = (int)q;
+    const float h = deg_f32(atan2_f32(x, y));
+    double c = -std::round(((double)h - 90.0) / (double)prm.ang_res_x) + (double)(H / 2);
+    if (c >= (double)H) c -= (double)H;
+    if (!(c >= 0.0 && c < (double)H)) continue;
+    const float r = std::sqrt((x * x + y * y) + z * z);
+    if (r < prm.min_range) continue;
+    const size_t p = (size_t)row * H + (size_t)c;
+    im.owner[p] = (int32_t)i;                                                // the last point wins
+    im.range[p] = r;
+  }
+  auto flat = [&](int32_t a, int32_t b) {                                    // groundRemoval's test, lower a, upper b
+    const float dx = pts[b][0] - pts[a][0], dy = pts[b][1] - pts[a][1], dz = pts[b][2] - pts[a][2];
+    const float ang = deg_f32(atan2_f32(dz, std::sqrt(dx * dx + dy * dy)));
+    return std::fabs(ang - prm.mount_angle) <= 10.0f;
+  };
+  for (int j = 0; j < H; ++j)                                                // groundRemoval (:329-374), its own loop order
+    for (int i = 0; i < G; ++i) {
+      const int32_t lo = im.owner[(size_t)i * H + j], up = im.owner[(size_t)(i + 1) * H + j];
+      if (lo < 0 || up < 0) { im.ground[(size_t)i * H + j] = -1; continue; }
+      if (flat(lo, up)) { im.ground[(size_t)i * H + j] = 1; im.ground[(size_t)(i + 1) * H + j] = 1; }
+    }
+  for (size_t p = 0; p < NP; ++p)
+    if (im.ground[p] == 1 || im.owner[p] < 0) im.label[p] = -1;
+  const float alpha_x = (float)((double)prm.ang_res_x / 180.0 * kPi), alpha_y = (float)((double)prm.ang_res_y / 180.0 * kPi);
+  const float sx = (float)std::sin((double)alpha_x), cx = (float)std::cos((double)alpha_x);
+  const float sy = (float)std::sin((double)alpha_y), cy = (float)std::cos((double)alpha_y);
+  std::vector<int> queue(NP), pushed(NP);
+  int32_t label_count = 1;
+  const int nbr[4][2] = {{-1, 0}, {0, 1}, {0, -1}, {1, 0}};
+  for (int row = 0; row < N; ++row)                                          // cloudSegmentation (:379-383)
+    for (int col = 0; col < H; ++col) {
+      if (im.label[(size_t)row * H + col] != 0) continue;
+      std::vector<bool> line(N, false);                                      // labelComponents (:435-531)
+      size_t qs = 0, qe = 0, np = 0;
+      queue[qe++] = row * H + col;
+      pushed[np++] = row * H + col;
+      while (qs < qe) {
+        const int from = queue[qs++];
+        const int fr = from / H, fc = from % H;
+        im.label[from] = label_count;
+        for (const auto& d : nbr) {
+          const int tr = fr + d[0];
+          int tc = fc + d[1];
+          if (tr < 0 || tr >= N) continue;
+          if (tc < 0) tc = H - 1;
+          if (tc >= H) tc = 0;
+          const int to = tr * H + tc;
+          if (im.label[to] != 0) continue;
+          const float d1 = std::max(im.range[from], im.range[to]), d2 = std::min(im.range[from], im.range[to]);
+          const float s = d[0] == 0 ? sx : sy, c = d[0] == 0 ? cx : cy;
+          if (atan2_f32(d2 * s, d1 - d2 * c) > prm.segment_theta) {
+            queue[qe++] = to;
+            im.label[to] = label_count;
+            line[tr] = true;
+            pushed[np++] = to;
+          }
+        }
+      }
+      bool feasible = np >= 30;
+      if (!feasible && np >= (size_t)prm.valid_point_num) {
+        int lines = 0;
+        for (int r = 0; r < N; ++r) lines += line[r] ? 1 : 0;
+        feasible = lines >= prm.valid_line_num;
+      }
+      if (feasible) ++label_count;
+      else for (size_t k = 0; k < np; ++k) im.label[pushed[k]] = 999999;
+    }
+  return im;
+}
+
+// segmentedCloud_ (:384-414) and the input index of each of its points
+inline Cloud segment_scan(const Cloud& pts, const svnicp_seg_params& prm, std::vector<int64_t>* src_index = nullptr) {
+  const SegImages im = segment_images(pts, prm);
+  const int N = prm.n_scan, H = prm.horizon_scan;
+  Cloud out;
+  if (src_index) src_index->clear();
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < H; ++j) {
+      const size_t p = (size_t)i * H + j;
+      const int32_t lab = im.label[p];
+      const bool g = im.ground[p] == 1;
+      if (!(lab > 0 || g) || lab == 999999) continue;
+      if (g && j % 5 != 0 && j > 5 && j < H - 5) continue;                  // most ground points are skipped
+      out.push_back(pts[(size_t)im.owner[p]]);
+      if (src_index) src_index->push_back(im.owner[p]);
+    }
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ local map
 // svnicp::VoxelHashMap (src/core/VoxelHashMap.cpp:22-101): voxel -> at most max_points points in insertion order; voxel index
 // = coordinates / voxel_size truncated TOWARD ZERO (Eigen cast<int>, :29); a voxel is dropped when its FIRST point is
@@ -359,6 +496,24 @@ class DevicePrep {
                                 &n_map, &n_source) != 0)
       throw std::runtime_error(svnicp_prep_last_error(p_));
   }
+  // range-image segmentation (ImageProjection::cloudHandler) -> number of points of the segmented cloud, kept in HBM
+  int64_t segment(const Cloud& points, const svnicp_seg_params& prm) {
+    int64_t n = 0;
+    if (svnicp_prep_segment(p_, points.empty() ? nullptr : &points[0][0], (int64_t)points.size(), SVNICP_MEM_HOST, &prm, &n) != 0)
+      throw std::runtime_error(svnicp_prep_last_error(p_));
+    return n;
+  }
+  const float* segmented() { return svnicp_prep_segmented_devptr(p_); }
+  // crop + samplings (or, with delta, deskew without stamps first) of a cloud already in HBM
+  void scan_device(const float* xyz, int64_t n, const std::array<double, 6>* delta, bool kitti, double min_range, double max_range,
+                   double voxel_size, double* scan_max_range) {
+    const int rc = delta ? svnicp_prep_scan_deskew(p_, xyz, nullptr, SVNICP_STAMP_F64, n, SVNICP_MEM_DEVICE, delta->data(),
+                                                   kitti ? SVNICP_DESKEW_KITTI : 0, min_range, max_range, voxel_size, scan_max_range,
+                                                   &n_cropped, &n_map, &n_source)
+                         : svnicp_prep_scan(p_, xyz, n, SVNICP_MEM_DEVICE, min_range, max_range, voxel_size, scan_max_range, &n_cropped,
+                                            &n_map, &n_source);
+    if (rc != 0) throw std::runtime_error(svnicp_prep_last_error(p_));
+  }
   Cloud download_deskewed() {   // test tap
     int64_t n = 0;
     if (svnicp_prep_download_deskewed(p_, nullptr, 0, &n) != 0) throw std::runtime_error(svnicp_prep_last_error(p_));
@@ -411,6 +566,9 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   bool gpu_prep = false; // with gpu_map: crop and both uniform samplings on the device (DevicePrep): the raw scan is uploaded, no host pass over the points
   bool deskew = false;   // deskew_cloud (config/ICP_parameters.yaml:18): motion compensation ahead of the crop once two poses exist (:551-554)
   bool kitti = false;    // with deskew: the KITTI branch (cloud_topic "/kitti/velo/pointcloud", :385-401) instead of per-point stamps
+  bool segmentation = false;   // USE_Segmentation (:180, :328-355): range-image segmentation of the raw scan first; the segmented
+                               // cloud has no time field (:363-381), so per-point stamps are dropped (KITTI deskew still runs)
+  svnicp_seg_params seg_params = seg_hdl64e_params();
 };
 
 struct ScanResult {
@@ -462,7 +620,13 @@ class RegistrationPipeline {
     const bool deskew = cfg_.deskew && poses_.size() >= 2;                                             // :552
     std::array<double, 6> delta{};
     if (deskew) delta = se3_log(poses_[poses_.size() - 2].inverse() * poses_.back());                  // :427-432
-    if (dprep_) {
+    if (cfg_.segmentation) point_stamps = nullptr;                                                     // segmentedCloud_: no time field
+    if (dprep_ && cfg_.segmentation) {                                                                 // :331-343 on the device
+      const int64_t n = dprep_->segment(points, cfg_.seg_params);
+      bytes_h2d_ += points.size() * 12;
+      dprep_->scan_device(dprep_->segmented(), n, deskew ? &delta : nullptr, cfg_.kitti, cfg_.min_range, cfg_.max_range, cfg_.voxel_size,
+                          &scan_max_range_);
+    } else if (dprep_) {
       if (deskew) {                                                                                    // :551-560 on the device
         const bool st = point_stamps && !cfg_.kitti;
         dprep_->scan_deskew(points, st ? point_stamps->data() : nullptr, SVNICP_STAMP_F64, delta, cfg_.kitti, cfg_.min_range, cfg_.max_range,
@@ -473,8 +637,10 @@ class RegistrationPipeline {
         bytes_h2d_ += points.size() * 12;
       }
     } else {
-      const Cloud deskewed = deskew ? deskew_pointcloud(points, point_stamps, delta, cfg_.kitti) : Cloud{};   // :553
-      cropped = crop_pointcloud(deskew ? deskewed : points, cfg_.min_range, cfg_.max_range, &scan_max_range_);   // :556
+      const Cloud segmented = cfg_.segmentation ? segment_scan(points, cfg_.seg_params) : Cloud{};     // :331-343
+      const Cloud& raw = cfg_.segmentation ? segmented : points;
+      const Cloud deskewed = deskew ? deskew_pointcloud(raw, point_stamps, delta, cfg_.kitti) : Cloud{};   // :553
+      cropped = crop_pointcloud(deskew ? deskewed : raw, cfg_.min_range, cfg_.max_range, &scan_max_range_);   // :556
       to_map = downsample_uniform(cropped, 0.5 * cfg_.voxel_size);                                     // :559
       source = downsample_uniform(to_map, 1.5 * cfg_.voxel_size);                                      // :560
     }

@@ -235,6 +235,208 @@ def deskew_pointcloud(points: np.ndarray, stamps, delta6, kitti: bool = False) -
     return out
 
 
+# ----------------------------------------------------------------------------- range-image segmentation
+# LeGO-LOAM's ImageProjection::cloudHandler (include/segmentation/ImageProjection.h), which OdometryPipeline::lidar_msg_cb runs
+# on every raw scan when USE_Segmentation is set (OdometryPipeline.cpp:328-355); the pipeline consumes GetSegmentedCloudPure(),
+# which returns segmentedCloud_ (:533-534).  The same steps, in the same float32 / float64 order, are in
+# registration_pipeline.hpp (segment_scan) and csrc/range_segment.hip (svnicp_prep_segment).  Deliberate deviation: every
+# atan2f / sinf / cosf of the reference is the float64 function of the float32 operands rounded once to float32 (the host
+# libm's float functions are not correctly rounded and differ between libraries), so the three forms agree bit for bit.
+SEG_EMPTY_RANGE = np.float32(-100000.0)      # rangeMat_ of an empty pixel (resetParameters)
+SEG_INVALID_LABEL = 999999                   # labelMat_ of a component that failed the validity test (:523-529)
+_F32 = np.float32
+
+
+@dataclass
+class SegParams:
+    """ImageProjection's sensor and segmentation constants (:63-68, :112-118); float fields hold float32 values."""
+    n_scan: int = 64
+    horizon_scan: int = 2250
+    ground_scan_ind: int = 7
+    ang_res_x: float = float(_F32(360.0 / 2250.0))
+    ang_res_y: float = float(_F32(26.8 / 63.0))
+    ang_bottom: float = float(_F32(24.8))
+    min_range: float = 1.0                   # sensorMinimumRange
+    mount_angle: float = 0.0                 # sensorMountAngle
+    segment_theta: float = float(_F32(60.0 / 180.0 * math.pi))
+    valid_point_num: int = 5                 # segmentValidPointNum
+    valid_line_num: int = 3                  # segmentValidLineNum
+
+    def alphas(self):
+        """(sin αx, cos αx, sin αy, cos αy) as float32, α = float(double(ang_res) / 180 · π) (:119-120)."""
+        out = []
+        for res in (self.ang_res_x, self.ang_res_y):
+            a = float(_F32(float(_F32(res)) / 180.0 * math.pi))
+            out += [_F32(math.sin(a)), _F32(math.cos(a))]
+        return tuple(out)
+
+
+def seg_params_struct(prm: SegParams):
+    """SegParams -> struct svnicp_seg_params (ctypes)."""
+    from .binding import SegParamsStruct
+    import ctypes as C
+    return SegParamsStruct(C.sizeof(SegParamsStruct), int(prm.n_scan), int(prm.horizon_scan), int(prm.ground_scan_ind),
+                           float(prm.ang_res_x), float(prm.ang_res_y), float(prm.ang_bottom), float(prm.min_range),
+                           float(prm.mount_angle), float(prm.segment_theta), int(prm.valid_point_num), int(prm.valid_line_num))
+
+
+def _seg_preset(n, h, rx, ry, bottom, g):
+    return SegParams(n_scan=n, horizon_scan=h, ground_scan_ind=g, ang_res_x=float(_F32(rx)), ang_res_y=float(_F32(ry)),
+                     ang_bottom=float(_F32(bottom)))
+
+
+# the sensor blocks of ImageProjection.h:46-110, each value as the header's expression evaluates it (double expression stored
+# to float; "int / float(...)" is a float division)
+SEG_PRESETS = {
+    "VLP-16": _seg_preset(16, 1800, 0.2, 2.0, 15.0 + 0.1, 7),
+    "HDL-32E": _seg_preset(32, 1800, 360.0 / float(_F32(1800)), 41.33 / float(_F32(31)), 30.67, 20),
+    "HDL-64E": _seg_preset(64, 2250, 360.0 / float(_F32(2250)), 26.8 / float(_F32(63)), 24.8, 7),
+    "VLS-128": _seg_preset(128, 1800, 0.2, 0.3, 25.0, 10),
+    "RS-LIDAR-32": _seg_preset(32, 2000, 0.18, _F32(40) / _F32(31), 25.0, 2),
+    "OS1-16": _seg_preset(16, 1024, 360.0 / float(_F32(1024)), 33.2 / float(_F32(15)), 16.6 + 0.1, 7),
+    "OS1-64": _seg_preset(64, 1024, 360.0 / float(_F32(1024)), 33.2 / float(_F32(63)), 16.6 + 0.1, 15),
+    "OS0-128": _seg_preset(128, 1024, 360.0 / float(_F32(1024)), _F32(90) / _F32(127), 45 + 0.1, 11),
+}
+SEG_PRESET_IDS = {name: k for k, name in enumerate(SEG_PRESETS)}   # SVNICP_SEG_* of include/svnicp_hip.h, same order
+
+
+def _atan2_f32(y, x):
+    """The project's atan2f: float64 atan2 of the float32 operands, rounded once (header: deliberate deviation)."""
+    return np.arctan2(np.asarray(y, np.float32).astype(np.float64), np.asarray(x, np.float32).astype(np.float64)).astype(np.float32)
+
+
+def _deg_f32(a):
+    """float(double(a * 180.0f) / M_PI) for float32 radians a."""
+    return ((a * _F32(180.0)).astype(np.float64) / math.pi).astype(np.float32)
+
+
+def _c_round(v):
+    """C round(): half away from zero, exact for every double."""
+    t = np.trunc(v)
+    return t + np.where(np.abs(v - t) >= 0.5, np.sign(v), 0.0)
+
+
+def _seg_project(points, prm: SegParams):
+    """copyPointCloud + projectPointCloud (:240, :281-325) -> owner image (int64 [N·H], -1 = empty) and the float32 ranges
+    of all points."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    N, H = int(prm.n_scan), int(prm.horizon_scan)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        finite = np.isfinite(p).all(axis=1)                                           # removeNaNFromPointCloud (:240)
+        va = _deg_f32(_atan2_f32(z, np.sqrt(x * x + y * y)))
+        q = (va + _F32(prm.ang_bottom)) / _F32(prm.ang_res_y)                         # float32; converted to size_t (x86-64)
+        row_ok = (q > _F32(-1.0)) & (q < _F32(N))
+        row = np.where(row_ok, np.trunc(np.where(row_ok, q, 0)), 0).astype(np.int64)
+        h = _deg_f32(_atan2_f32(x, y))
+        col = -_c_round((h.astype(np.float64) - 90.0) / float(_F32(prm.ang_res_x))) + float(H // 2)
+        col = np.where(col >= H, col - H, col)
+        col_ok = (col >= 0) & (col < H)
+        rng = np.sqrt((x * x + y * y) + z * z)
+        keep = finite & row_ok & col_ok & (rng >= _F32(prm.min_range))
+    owner = np.full(N * H, -1, np.int64)
+    idx = np.flatnonzero(keep)
+    pix = row[idx] * H + np.where(col_ok, col, 0).astype(np.int64)[idx]
+    np.maximum.at(owner, pix, idx)                                                    # the last point in input order wins
+    return owner, rng
+
+
+def segment_images(points, params: SegParams | None = None):
+    """ImageProjection's images for one scan -> (owner int32 [N,H] (winning input index, -1 empty), range float32 [N,H]
+    (-100000 empty), ground int8 [N,H] (groundMat_), label int32 [N,H] (labelMat_ after cloudSegmentation))."""
+    prm = params or SegParams()
+    N, H, G = int(prm.n_scan), int(prm.horizon_scan), int(prm.ground_scan_ind)
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    owner, rng = _seg_project(p, prm)
+    filled = owner >= 0
+    o = np.where(filled, owner, 0)
+    rimg = np.where(filled, rng[o] if p.shape[0] else SEG_EMPTY_RANGE, SEG_EMPTY_RANGE).astype(np.float32).reshape(N, H)
+    xyz = (p[o] if p.shape[0] else np.zeros((N * H, 3), np.float32)).reshape(N, H, 3)
+    filled = filled.reshape(N, H)
+    # groundRemoval (:329-374), closed form of the loop's overwrites
+    ground = np.zeros((N, H), np.int8)
+    if G > 0:
+        valid = filled[:G] & filled[1:G + 1]                                          # pair (r, r+1), r = 0..G-1
+        d = xyz[1:G + 1] - xyz[:G]
+        with np.errstate(invalid="ignore"):
+            ang = _deg_f32(_atan2_f32(d[..., 2], np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])))
+            flat = valid & (np.abs(ang - _F32(prm.mount_angle)) <= _F32(10))
+        up = np.zeros((G + 1, H), bool); up[:G] = flat                               # pair (r, r+1) flat
+        dn = np.zeros((G + 1, H), bool); dn[1:] = flat                               # pair (r-1, r) flat
+        inval = np.zeros((G + 1, H), bool); inval[:G] = ~valid
+        ground[:G + 1] = np.where(inval, -1, np.where(up | dn, 1, 0))
+    label = np.where((ground == 1) | ~filled, -1, 0).astype(np.int32)
+    # link predicates (symmetric): right (wrapping) and down neighbour
+    sx, cx, sy, cy = prm.alphas()
+    theta = _F32(prm.segment_theta)
+
+    def link(ra, rb, s, c):
+        d1, d2 = np.maximum(ra, rb), np.minimum(ra, rb)
+        return _atan2_f32(d2 * s, d1 - d2 * c) > theta
+
+    right = link(rimg, np.roll(rimg, -1, axis=1), sx, cx)
+    down = np.zeros((N, H), bool)
+    down[:-1] = link(rimg[:-1], rimg[1:], sy, cy)
+    _label_components(label, right, down, prm)
+    return owner.astype(np.int32).reshape(N, H), rimg, ground, label
+
+
+def _label_components(label, right, down, prm: SegParams):
+    """cloudSegmentation's seed loop and labelComponents (:379-383, :435-531), literally: row-major seeds, a FIFO queue,
+    lineCountFlag set on push only."""
+    N, H = label.shape
+    lab = label.reshape(-1)   # view
+    rl, dl = right.reshape(-1), down.reshape(-1)
+    count = 1
+    for seed in np.flatnonzero(lab == 0).tolist():
+        if lab[seed] != 0:
+            continue
+        queue = [seed]
+        pushed = [seed]
+        lines = set()
+        lab[seed] = count
+        head = 0
+        while head < len(queue):
+            a = queue[head]; head += 1
+            r, c = divmod(a, H)
+            nbrs = []
+            if r > 0:
+                nbrs.append((a - H, dl[a - H]))
+            b = r * H + (c + 1) % H
+            nbrs.append((b, rl[a]))
+            b = r * H + (c - 1) % H
+            nbrs.append((b, rl[b]))
+            if r < N - 1:
+                nbrs.append((a + H, dl[a]))
+            for b, ok in nbrs:
+                if lab[b] != 0 or not ok:
+                    continue
+                lab[b] = count
+                queue.append(b)
+                pushed.append(b)
+                lines.add(b // H)
+        n = len(pushed)
+        if n >= 30 or (n >= prm.valid_point_num and len(lines) >= prm.valid_line_num):
+            count += 1
+        else:
+            lab[pushed] = SEG_INVALID_LABEL
+
+
+def segment_scan(points, params: SegParams | None = None):
+    """ImageProjection::cloudHandler -> segmentedCloud_ (what GetSegmentedCloudPure returns, :384-414): float32 [n,3] and the
+    input index of every point (int64 [n]).  Pixels row-major; a pixel is kept when it belongs to a valid component or is
+    ground, ground pixels only at j % 5 == 0 or within 5 columns of the image edges."""
+    prm = params or SegParams()
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    owner, _, ground, label = segment_images(p, prm)
+    H = int(prm.horizon_scan)
+    j = np.arange(H)[None, :]
+    g = ground == 1
+    keep = ((label > 0) | g) & (label != SEG_INVALID_LABEL) & ~(g & (j % 5 != 0) & (j > 5) & (j < H - 5))
+    src = owner[keep].astype(np.int64)
+    return (p[src] if src.size else np.zeros((0, 3), np.float32)), src
+
+
 # ----------------------------------------------------------------------------- local map
 def transform_f32(cloud, T) -> np.ndarray:
     """pcl::transformPointCloud of float32 points with gtsam's DOUBLE Matrix4 (VoxelHashMap.cpp:23-25): every coordinate
@@ -366,6 +568,8 @@ class DevicePreprocessor:
         if rc:
             raise binding.SvnIcpError(f"svnicp_prep_create failed ({rc}): {self._L.svnicp_prep_last_error(None).decode()}")
         self.n_cropped = self.n_map = self.n_source = 0
+        self.n_segmented = 0
+        self.seg_shape = (0, 0)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -460,6 +664,87 @@ class DevicePreprocessor:
         if rc:
             raise binding.SvnIcpError(f"svnicp_prep_download_deskewed failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
         return out
+
+    def segment(self, points, params: SegParams | None = None) -> int:
+        """Range-image segmentation on the device (svnicp_prep_segment, segment_scan's semantics) -> n_segmented.  The
+        segmented cloud (float32 rows) and the input index of each of its points stay in HBM behind ``segmented_ptr`` /
+        ``segmented_index_ptr``; ``scan_device(segmented_ptr, n, …)`` pre-processes the cloud without a second upload.
+        ``points`` may be a CUDA torch tensor (nothing uploaded); ``bytes_uploaded`` counts the upload."""
+        from . import binding
+        C = self._C
+        keep = []
+        pts_ptr, n, mem, up = self._cloud_arg(points, keep)
+        prm = seg_params_struct(params or SegParams())
+        out = C.c_int64(0)
+        rc = self._L.svnicp_prep_segment(self._h, pts_ptr, n, mem, C.byref(prm), C.byref(out))
+        if rc:
+            raise binding.SvnIcpError(f"svnicp_prep_segment failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+        self.n_segmented = int(out.value)
+        self.seg_shape = (int(prm.n_scan), int(prm.horizon_scan))
+        self.bytes_uploaded = up
+        return self.n_segmented
+
+    def scan_device(self, ptr: int, n: int, min_range: float, max_range: float, voxel_size: float, scan_max_range: float, *,
+                    delta=None, kitti: bool = False) -> float:
+        """``scan`` of a float32 [n][3] cloud already in HBM (SVNICP_MEM_DEVICE), e.g. ``segmented_ptr``: nothing uploaded.
+        With ``delta`` the cloud goes through svnicp_prep_scan_deskew without stamps (KITTI with ``kitti``)."""
+        from . import binding
+        C = self._C
+        smr = C.c_double(float(scan_max_range))
+        nc, nm, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        if delta is None:
+            rc = self._L.svnicp_prep_scan(self._h, C.c_void_p(int(ptr)), int(n), 1, float(min_range), float(max_range), float(voxel_size),
+                                          C.byref(smr), C.byref(nc), C.byref(nm), C.byref(ns))
+            what = "svnicp_prep_scan"
+        else:
+            d = np.ascontiguousarray(np.asarray(delta, np.float64).reshape(6))
+            rc = self._L.svnicp_prep_scan_deskew(self._h, C.c_void_p(int(ptr)), None, SVNICP_STAMP_F64, int(n), 1,
+                                                 d.ctypes.data_as(C.POINTER(C.c_double)), SVNICP_DESKEW_KITTI if kitti else 0,
+                                                 float(min_range), float(max_range), float(voxel_size), C.byref(smr), C.byref(nc),
+                                                 C.byref(nm), C.byref(ns))
+            what = "svnicp_prep_scan_deskew"
+        if rc:
+            raise binding.SvnIcpError(f"{what} failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+        self.n_cropped, self.n_map, self.n_source = int(nc.value), int(nm.value), int(ns.value)
+        self.bytes_uploaded = 0
+        return float(smr.value)
+
+    def download_segmented(self):
+        """The last svnicp_prep_segment's cloud -> (float32 [n,3], input index int64 [n]) (test tap)."""
+        from . import binding
+        C = self._C
+        n = C.c_int64(0)
+        rc = self._L.svnicp_prep_download_segmented(self._h, None, None, 0, C.byref(n))
+        xyz = np.zeros((int(n.value), 3), np.float32)
+        idx = np.zeros(int(n.value), np.int32)
+        if rc == 0 and xyz.size:
+            rc = self._L.svnicp_prep_download_segmented(self._h, xyz.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                        xyz.shape[0], C.byref(n))
+        if rc:
+            raise binding.SvnIcpError(f"svnicp_prep_download_segmented failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+        return xyz, idx.astype(np.int64)
+
+    def download_seg_images(self):
+        """The last svnicp_prep_segment's images -> (owner int32, range float32, ground int8, label int32), each [N,H], as
+        segment_images returns them (test tap)."""
+        from . import binding
+        C = self._C
+        N, H = self.seg_shape
+        owner = np.zeros((N, H), np.int32); rng = np.zeros((N, H), np.float32)
+        ground = np.zeros((N, H), np.int8); label = np.zeros((N, H), np.int32)
+        rc = self._L.svnicp_prep_download_seg_images(self._h, owner.ctypes.data_as(C.c_void_p), rng.ctypes.data_as(C.c_void_p),
+                                                     ground.ctypes.data_as(C.c_void_p), label.ctypes.data_as(C.c_void_p), N * H)
+        if rc:
+            raise binding.SvnIcpError(f"svnicp_prep_download_seg_images failed ({rc}): {self._L.svnicp_prep_last_error(self._h).decode()}")
+        return owner, rng, ground, label
+
+    @property
+    def segmented_ptr(self) -> int:
+        return int(self._L.svnicp_prep_segmented_devptr(self._h) or 0)
+
+    @property
+    def segmented_index_ptr(self) -> int:
+        return int(self._L.svnicp_prep_segmented_index_devptr(self._h) or 0)
 
     @property
     def deskewed_ptr(self) -> int:
@@ -583,6 +868,8 @@ class PipelineConfig:
     gpu_prep: bool = False         # with gpu_map: crop and both uniform samplings on the device (DevicePreprocessor): the raw scan is uploaded, no host pass over the points
     deskew: bool = False           # deskew_cloud (config/ICP_parameters.yaml:18): motion compensation from the last two poses ahead of the crop (:551-554)
     kitti: bool = False            # with deskew: the KITTI branch (cloud_topic "/kitti/velo/pointcloud", :385-401) instead of per-point stamps
+    segmentation: bool = False     # USE_Segmentation (OdometryPipeline.cpp:180, :328-355): range-image segmentation of the raw scan first
+    seg_params: SegParams = field(default_factory=SegParams)   # the sensor of ImageProjection.h (SEG_PRESETS); HDL-64E by default
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
 
@@ -623,23 +910,37 @@ class RegistrationPipeline:
         return initialize_particles(self.cfg.particle_count, PRIOR_UB, PRIOR_LB, self._rng)   # set_initPose, :661-667
 
     def process_scan(self, points: np.ndarray, stamp: float, point_stamps=None) -> ScanResult:
-        """point_stamps: the scan's per-point time field (float64 / float32 / uint32), used when cfg.deskew is set."""
+        """point_stamps: the scan's per-point time field (float64 / float32 / uint32), used when cfg.deskew is set.
+
+        With cfg.segmentation the raw scan is segmented first (segment_scan; on the device with gpu_prep, where the segmented
+        cloud feeds the crop without a second upload).  As in the reference, the segmented message is a PointXYZI cloud with
+        no time field (OdometryPipeline.cpp:363-381): point_stamps are dropped, so deskew degenerates to min == max (no change);
+        the KITTI branch still runs, on the segmented cloud."""
         c = self.cfg
         t0 = time.perf_counter()
         dev = c.gpu_map and c.gpu_prep
         delta = None
         if c.deskew and len(self.poses) >= 2:                                                                   # :552
             delta = se3_log(np.linalg.inv(self.poses[-2]) @ self.poses[-1])                                     # :427-432
+        if c.segmentation:
+            point_stamps = None                                                                                 # segmentedCloud_ has no time field
         if dev:
             if self._prep is None:
                 self._prep = DevicePreprocessor(self.device)
-            if delta is None:
+            if c.segmentation:                                                                                  # :331-343 on the device
+                n = self._prep.segment(points, c.seg_params)
+                self.bytes_h2d += self._prep.bytes_uploaded
+                self.scan_max_range = self._prep.scan_device(self._prep.segmented_ptr, n, c.min_range, c.max_range, c.voxel_size,
+                                                             self.scan_max_range, delta=delta, kitti=c.kitti)
+            elif delta is None:
                 self.scan_max_range = self._prep.scan(points, c.min_range, c.max_range, c.voxel_size, self.scan_max_range)  # :556-560
             else:                                                                                               # :551-560
                 self.scan_max_range = self._prep.scan(points, c.min_range, c.max_range, c.voxel_size, self.scan_max_range,
                                                       stamps=point_stamps, delta=delta, kitti=c.kitti)
             self.bytes_h2d += self._prep.bytes_uploaded
         else:
+            if c.segmentation:
+                points, _ = segment_scan(points, c.seg_params)                                                 # :331-343
             if delta is not None:
                 points = deskew_pointcloud(points, point_stamps, delta, c.kitti)                               # :553
             cropped, self.scan_max_range = crop_pointcloud(points, c.min_range, c.max_range, self.scan_max_range)   # :556

@@ -129,6 +129,24 @@ def lidar_scan(scene: Scene, R: np.ndarray, t: np.ndarray, n_points: int, stream
     return pts[:n_points].astype(np.float32).astype(np.float64)
 
 
+def lidar_grid_scan(scene: Scene, R: np.ndarray, t: np.ndarray, sensor_params, stream: int, noise: float = 0.02,
+                    seed: int = SEED) -> np.ndarray:
+    """One scan that hits every pixel of a range image once (pipeline.SegParams / SEG_PRESETS): beams at the row centres
+    (elevation -ang_bottom + (row + 0.5)·ang_res_y degrees), azimuths at the column centres (atan2(x, y) = 90 - (col -
+    H/2)·ang_res_x degrees), fired column by column.  Sensor frame, float32-rounded float64 [n_scan·horizon_scan, 3].
+    (lidar_scan's 64 elevations lie ON the HDL-64E row boundaries instead.)"""
+    N, H = int(sensor_params.n_scan), int(sensor_params.horizon_scan)
+    el = np.deg2rad(-float(sensor_params.ang_bottom) + (np.arange(N) + 0.5) * float(sensor_params.ang_res_y))
+    h = np.deg2rad(90.0 - (np.arange(H) - H // 2) * float(sensor_params.ang_res_x))
+    hg, elg = np.meshgrid(h, el, indexing="ij")  # column-major firing order
+    d_s = np.stack([np.cos(elg) * np.sin(hg), np.cos(elg) * np.cos(hg), np.sin(elg)], -1).reshape(-1, 3)
+    d_w = d_s @ np.asarray(R, float).T
+    rng = _raycast(scene, np.asarray(t, float), d_w)
+    rng = rng + noise * normal01(stream, rng.shape[0], seed)
+    rng = np.clip(rng, 1.0, 100.0)
+    return (d_s * rng[:, None]).astype(np.float32).astype(np.float64)
+
+
 def _raycast_rows(scene: Scene, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
     """_raycast with one origin per ray (origins [N,3]): the scan of a moving sensor."""
     n = dirs.shape[0]
