@@ -54,8 +54,9 @@ typedef enum {
 #define SVNICP_MEM_HOST 0
 #define SVNICP_MEM_DEVICE 1
 
-/* svnicp::SteinICPParam — include/core/SVGDICP.h:41-57 (solver-relevant fields; batch_size,
- * normalize_cloud, convergence_steps, cov_filter_type are ignored by the reference solver) */
+/* svnicp::SteinICPParam — include/core/SVGDICP.h:41-57 (solver-relevant fields; normalize_cloud,
+ * convergence_steps, cov_filter_type are ignored by the reference solver; use_minibatch / batch_size
+ * are set through svnicp_set_minibatch, see "mini-batch" below) */
 typedef struct svnicp_params {
   int32_t struct_size;           /* = sizeof(svnicp_params)                                   */
   int32_t mode;                  /* SVNICP_MODE_*                                              */
@@ -137,6 +138,35 @@ int svnicp_get_runtime(svnicp_ctx *ctx, double out3[3]);             /* SVGDICP.
  *   single = fused|split    chain = auto|general|persistent   median = auto|stream|inline          correspondence = fast|full
  * The environment variable SVNICP_OPTIONS ("name=value;name=value") is read once, in svnicp_create. */
 int svnicp_set_option(svnicp_ctx *ctx, const char *name, const char *value);
+
+/* ---- mini-batch: SteinICPParam::use_minibatch / batch_size — SVGDICP::mini_batch_pair_generator (SVGDICP.cpp:176-199) -----
+ * With a batch, iteration i of both solvers works on the source rows idx[i][0..batch_size) of a table int32
+ * [iterations][batch_size] drawn with replacement (values in [0, B); batch_size may exceed B; a row drawn twice counts
+ * twice) instead of the whole scan: correspondences, point_filter, the H / b sums, the SVGD non-zero count and its
+ * (count + 1) normalisation are "over the batch"; gradient_scaling_factor_ stays the WHOLE cloud's size (:58, :454).  Stage A
+ * is unchanged but runs only on the rows that were drawn.  Early stop, history, particle update and outputs are unchanged.
+ * batch_size 0 = off (the default: full batch, exactly the launches of a context that never called this).
+ * Generated tables: the table of the n-th registration after this call (n = 0, 1, ...; svnicp_align_begin advances n) is, at
+ * flat position j of [0, iterations * batch_size), with splitmix64 as in svn-icp_amd/scans.py (arithmetic mod 2^64):
+ *   base = splitmix64(seed * 1000003 + n);  bits = splitmix64(base + j);  idx = floor(bits * B / 2^64)
+ * written on the device (no host pass); the Python mirror minibatch_indices() gives the same table bit for bit.  The
+ * reference draws with libtorch's CUDA generator, which is not reproduced: what is pinned is the arithmetic GIVEN the table.
+ * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID: batch_size < 0, a partial particle shard
+ * (svnicp_set_shard), a source-row shard (row_world > 1), the options correspondence=full and chain=persistent, and
+ * iterations * batch_size > 2^22 rows (about 2.5 KB of candidate tables per row: 10 GB).  In this mode
+ * svnicp_stage_candidates accepts only the whole range (0, B), svnicp_get_trace's corr is [I][P][batch_size], and
+ * svnicp_get_candidates / svnicp_get_candidate_dist2 return SVNICP_ERR_INVALID (see svnicp_get_minibatch_candidates). */
+int svnicp_set_minibatch(svnicp_ctx *ctx, int batch_size, uint64_t seed);
+/* an explicit table int32 [iterations][batch_size] (host or device memory; copied), used by EVERY following registration
+ * until svnicp_set_minibatch is called again: tests, replay of a recorded run.  A shape that does not match
+ * params.iterations, or a value outside [0, B), makes the registration fail with SVNICP_ERR_INVALID: a host table is checked
+ * in svnicp_align_begin; a device table is checked by the kernel that reads it (the value is never used as an address and
+ * no iteration runs), which svnicp_align reports when it returns and svnicp_align_async at svnicp_synchronize. */
+int svnicp_set_minibatch_indices(svnicp_ctx *ctx, const int32_t *idx, int iterations, int batch_size, int mem_kind);
+/* taps, valid after a registration in mini-batch mode */
+int svnicp_get_minibatch_indices(svnicp_ctx *ctx, int32_t *outIxb);      /* the table the last registration used */
+int svnicp_get_minibatch_candidates(svnicp_ctx *ctx, int32_t *outIxbxK); /* candidate target indices per drawn position */
+int svnicp_get_minibatch_rows(svnicp_ctx *ctx, int64_t out2[2]);         /* {unique rows drawn U, queries stage A ran} */
 
 /* ---- split-phase entry points: one process per GPU, particles sharded across ranks ----------
  * (new functionality; the reference is single-GPU).  Sequence per registration:

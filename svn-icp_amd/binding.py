@@ -150,6 +150,11 @@ def load_library():
     L.svnicp_candidates_devptr.restype = vp
     L.svnicp_sums_devptr.argtypes = [vp]
     L.svnicp_sums_devptr.restype = vp
+    L.svnicp_set_minibatch.argtypes = [vp, C.c_int, C.c_uint64]
+    L.svnicp_set_minibatch_indices.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.svnicp_get_minibatch_indices.argtypes = [vp, ip]
+    L.svnicp_get_minibatch_candidates.argtypes = [vp, ip]
+    L.svnicp_get_minibatch_rows.argtypes = [vp, C.POINTER(C.c_int64)]
     for name in declared_symbols():
         getattr(L, name)  # AttributeError here = the header declares a symbol the library does not export
     _lib = L

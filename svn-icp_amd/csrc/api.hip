@@ -116,6 +116,21 @@ struct svnicp_ctx {
   DevBuf<int32_t> arena, chunk_tab;    // stage A (Morton tiles): overflow chunks of the survivor pools and their table
   int arena_cap = 0;
   DevBuf<int32_t> full_idx;            // … and the nearest target of every (particle of the shard, source point): [P][B]
+  // mini-batch (svnicp_set_minibatch / svnicp_set_minibatch_indices; csrc/minibatch.hip).  mb_batch 0 = off.
+  int mb_batch = 0;
+  uint64_t mb_seed = 0, mb_n = 0;      // generated tables: seed, registrations begun since svnicp_set_minibatch
+  bool mb_explicit = false;            // an explicit table (mb_tab [mb_tab_I][mb_batch]) instead of generated ones
+  int mb_tab_I = 0;
+  std::vector<int32_t> mb_tab_h;       // the explicit table when it came from host memory: range-checked on the host …
+  int64_t mb_tab_checked_B = -1;       // … once per source size
+  bool mb_on = false, mb_have = false; // this registration runs on a table; its taps are valid (stage A has been enqueued)
+  bool mb_check = false;               // an explicit DEVICE table: its validation flag is read at the next synchronisation
+  int64_t mb_rows = 0, mb_nq = 0;      // iterations * batch; queries of stage A = min(B, mb_rows)
+  unsigned long long mb_base = 0;
+  int64_t qrows = 0;                   // query rows stage A is sized for: B, or mb_nq
+  DevBuf<int32_t> mb_tab, mb_idx, mb_flag, mb_pos, mb_bsum, mb_cand;
+  DevBuf<int> mb_ctl;
+  DevBuf<double> mb_src_u, mb_src;
   unsigned long long* dbg_phase = nullptr;   // debug option: per-phase wave cycles of k_knn_tiles (per context, per device)
   unsigned long long* dbg_upd = nullptr;     // debug option: phase cycles of k_particle_update
   bool finish_seen = true;   // the stop flag of the last registration has been folded into finish_iter
@@ -273,6 +288,8 @@ void svnicp_destroy(svnicp_ctx* c) {
   c->eul.release(); c->opt.release(); c->uctl.release(); c->rank_sums.release(); c->stage_fail_count.release(); c->stage_fail_list.release(); c->small_bar.release();
   c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->order_t.release(); c->qorder.release(); c->stat_n.release(); c->bbox.release(); c->tile_box.release(); c->sort_tmp.release();
   c->full_q.release(); c->full_d2.release(); c->full_idx.release(); c->arena.release(); c->chunk_tab.release();
+  c->mb_tab.release(); c->mb_idx.release(); c->mb_flag.release(); c->mb_pos.release(); c->mb_bsum.release(); c->mb_cand.release();
+  c->mb_ctl.release(); c->mb_src_u.release(); c->mb_src.release();
   c->pool_i.release(); c->torig.release(); c->pool2.release(); c->fail_list.release(); c->txf.release(); c->tyf.release(); c->tzf.release(); c->cmaxb.release(); c->tablef.release(); c->tablea.release(); c->kbest.release(); c->kidx.release(); c->sl_d.release(); c->sl_i.release(); c->fail_tau.release(); c->qrec.release(); c->anchor.release(); c->ambig.release(); c->emax.release(); c->fail_count.release(); c->cand_idx.release(); c->trcorr.release(); c->history.release(); c->ctl.release();
   if (c->dbg_phase) (void)hipFree(c->dbg_phase);
   if (c->dbg_upd) (void)hipFree(c->dbg_upd);
@@ -291,11 +308,13 @@ int svnicp_set_stream(svnicp_ctx* c, void* hip_stream) {
 }
 
 static int check_small_kernel(svnicp_ctx* c);
+static int check_minibatch_table(svnicp_ctx* c);
 int svnicp_synchronize(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (bind(c)) return SVNICP_ERR_HIP;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (const int rc = check_small_kernel(c)) return rc;
+  if (const int rc = check_minibatch_table(c)) return rc;
   if (c->have_result && c->h_stats) c->host_stats_valid = true;   // svnicp_finish's copy of the result block has landed
   return SVNICP_OK;
 }
@@ -476,7 +495,7 @@ static int ensure_target_layout(svnicp_ctx* c) {
   if (c->tune.knn == 0) want = 0;   // option "knn": v1 | v2 | brute | tiles (A/B for tests and profiling)
   if (c->tune.knn == 1) want = knn_scan_plan(c->Mp, c->K, &c->scan_Ms, &c->scan_rank, &c->scan_S2) ? 1 : 0;
   // small registrations (the scan-to-map loop's sizes, BASELINE C1): brute force in one launch, no target layout at all
-  if ((c->tune.knn == -1 && knn_brute_applicable(c->B, c->M, c->K)) || (c->tune.knn == 2 && c->K <= 128 && c->M < (1ll << 31))) want = 3;
+  if ((c->tune.knn == -1 && knn_brute_applicable(c->qrows, c->M, c->K)) || (c->tune.knn == 2 && c->K <= 128 && c->M < (1ll << 31))) want = 3;
   c->knn_variant = want;
   c->use_scan = want == 1;
   if (want == 3) return 0;
@@ -515,6 +534,33 @@ int svnicp_align_begin(svnicp_ctx* c) {
   if (bind(c)) return SVNICP_ERR_HIP;
   const int I = c->prm.iterations, P = c->P;
   const int64_t B = c->B;
+  // mini-batch: what this registration draws, and what it is not combined with
+  bool mb = false;
+  if (c->mb_batch != 0) {
+    const char* why = nullptr;
+    if (c->mb_batch < 0) why = "batch_size must be positive";
+    else if (c->shard_set && (c->p_lo != 0 || c->p_hi != P)) why = "a partial particle shard (svnicp_set_shard) is set";
+    else if (c->row_world > 1) why = "a source-row shard (svnicp_set_row_shard) is set";
+    else if (c->tune.full_corr) why = "option correspondence=full is set";
+    else if (c->tune.persistent) why = "option chain=persistent is set";
+    else if ((int64_t)I * c->mb_batch > kMinibatchMaxRows) why = "iterations * batch_size exceeds 2^22 table rows (about 2.5 KB of tables per row)";
+    else if (c->mb_explicit && c->mb_tab_I != I) why = "the explicit index table's iteration count differs from params.iterations";
+    if (why) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ") + why);
+    if (c->mb_explicit && !c->mb_tab_h.empty() && c->mb_tab_checked_B != B) {
+      for (const int32_t v : c->mb_tab_h)
+        if (v < 0 || (int64_t)v >= B)
+          return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the mini-batch index table holds " + std::to_string(v) + ", outside [0, " + std::to_string(B) + ")");
+      c->mb_tab_checked_B = B;
+    }
+    mb = I > 0;
+  }
+  c->mb_on = mb; c->mb_have = false; c->mb_check = false;
+  c->mb_rows = mb ? (int64_t)I * c->mb_batch : 0;
+  c->mb_nq = mb ? std::min<int64_t>(B, c->mb_rows) : 0;
+  c->qrows = mb ? c->mb_nq : B;
+  const int64_t Bq = c->qrows;                 // rows stage A runs on
+  const int64_t Bt = mb ? c->mb_rows : B;      // rows of the candidate tables
+  const int64_t Bi = mb ? c->mb_batch : B;     // rows one iteration works on
   c->S = knn_pool_size(c->K);
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   if (ensure_target_layout(c)) return c->err.empty() ? SVNICP_ERR_HIP : SVNICP_ERR_HIP;
@@ -525,17 +571,17 @@ int svnicp_align_begin(svnicp_ctx* c) {
       // survivors of the f32 pre-filter: 512 slots per query (median 127 at C3) + a shared arena of 512-slot chunks for the
       // heavy tail (C3: 0.4 % of the queries, 0.17 M entries; C5: 4 %, 3.1 M entries, up to 9016 per query)
       c->scan_S2 = kTilesBase + kTilesChunks * kTilesChunk;
-      c->arena_cap = (int)std::max<int64_t>(32768, B / 4);
-      HIPCHK(c, c->pool2.ensure((size_t)B * kTilesBase));
+      c->arena_cap = (int)std::max<int64_t>(32768, Bq / 4);
+      HIPCHK(c, c->pool2.ensure((size_t)Bq * kTilesBase));
       HIPCHK(c, c->arena.ensure((size_t)c->arena_cap * kTilesChunk));
-      HIPCHK(c, c->chunk_tab.ensure((size_t)B * kTilesChunks + 16 + (size_t)(B + 63) / 64 + 1));
+      HIPCHK(c, c->chunk_tab.ensure((size_t)Bq * kTilesChunks + 16 + (size_t)(Bq + 63) / 64 + 1));
     } else {
-      HIPCHK(c, c->pool2.ensure((size_t)B * c->scan_S2));
+      HIPCHK(c, c->pool2.ensure((size_t)Bq * c->scan_S2));
     }
-    HIPCHK(c, c->fail_list.ensure((size_t)B));
+    HIPCHK(c, c->fail_list.ensure((size_t)Bq));
     HIPCHK(c, c->fail_count.ensure(1));
-    HIPCHK(c, c->fail_tau.ensure((size_t)B));
-    HIPCHK(c, c->qrec.ensure((size_t)B * 6));  // 48-byte records
+    HIPCHK(c, c->fail_tau.ensure((size_t)Bq));
+    HIPCHK(c, c->qrec.ensure((size_t)Bq * 6));  // 48-byte records
     HIPCHK(c, c->pool_d.ensure((size_t)kFallbackGrid * 4 * kFallbackQW * c->S));   // fallback rows only
     HIPCHK(c, c->pool_i.ensure((size_t)kFallbackGrid * 4 * kFallbackQW * c->S));
     c->sliced_max = c->tune.fallback_sliced_max >= 0 ? c->tune.fallback_sliced_max : kFallbackSlicedMax;  // 0 forces the list-mode fallback
@@ -545,13 +591,19 @@ int svnicp_align_begin(svnicp_ctx* c) {
       HIPCHK(c, c->sl_i.ensure((size_t)c->sliced_max * knn_slice_count(c->K) * c->K));
     }
   } else {
-    HIPCHK(c, c->pool_d.ensure((size_t)B * c->S));
-    HIPCHK(c, c->pool_i.ensure((size_t)B * c->S));
+    HIPCHK(c, c->pool_d.ensure((size_t)Bq * c->S));
+    HIPCHK(c, c->pool_i.ensure((size_t)Bq * c->S));
   }
-  HIPCHK(c, c->cand_idx.ensure((size_t)B * c->K));
-  HIPCHK(c, c->cand_d2.ensure((size_t)B * c->K));
+  HIPCHK(c, c->cand_idx.ensure((size_t)Bq * c->K));   // mini-batch: the candidates of the unique drawn rows
+  HIPCHK(c, c->cand_d2.ensure((size_t)Bq * c->K));
+  if (mb) {
+    HIPCHK(c, c->mb_idx.ensure((size_t)Bt)); HIPCHK(c, c->mb_flag.ensure((size_t)B)); HIPCHK(c, c->mb_pos.ensure((size_t)B));
+    HIPCHK(c, c->mb_bsum.ensure((size_t)minibatch_scan_blocks(B))); HIPCHK(c, c->mb_ctl.ensure(2));
+    HIPCHK(c, c->mb_src_u.ensure((size_t)Bq * 3)); HIPCHK(c, c->mb_src.ensure((size_t)Bt * 3));
+    HIPCHK(c, c->mb_cand.ensure((size_t)Bt * c->K));
+  }
   c->accum_mode = c->tune.accum;   // option "accum": f64 | valu | split
-  HIPCHK(c, c->cmaxb.ensure((size_t)B));
+  HIPCHK(c, c->cmaxb.ensure((size_t)Bt));
   HIPCHK(c, c->ambig.ensure(2));   // [0] wave steps with an undecided lane, [1] undecided (point, particle) pairs (cleared by the begin kernel below)
   HIPCHK(c, c->history.ensure((size_t)(I > 0 ? I : 1) * 6 * P));
   c->hist_I = I; c->hist_P = P;
@@ -561,7 +613,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
     Tuning tn = c->tune;
     tn.small_chain = tn.small_chain && P >= 2 && P <= 128 && P <= tn.fused_update_max_p && !tn.update_fused && c->row_world == 1 &&
                      c->p_lo == 0 && c->p_hi == P && !tn.full_corr;
-    c->plan = plan_accumulate(nshard, B, c->K, c->num_cus, c->accum_mode, tn);
+    c->plan = plan_accumulate(nshard, Bi, c->K, c->num_cus, c->accum_mode, tn);
     if (c->tune.debug)
       fprintf(stderr, "[svnicp] stage-B plan: mode=%d PW=%d WP=%d TP=%d grid=%dx%d tiles/block=%d smem=%zu sgrid=%d pts/block=%d/%d\n", c->plan.f32,
               c->plan.PW, c->plan.WP, c->plan.TP, c->plan.grid_x, c->plan.grid_y, c->plan.tiles_per_block, c->plan.smem,
@@ -569,23 +621,23 @@ int svnicp_align_begin(svnicp_ctx* c) {
     if (c->plan.smem > 160u * 1024)   // K > 128 runs the LDS-tile VALU search: its smallest tile must fit one CU's LDS
       return fail(c, SVNICP_ERR_INVALID, "svnicp_align: knn_count " + std::to_string(c->K) + " needs " + std::to_string(c->plan.smem) +
                   " bytes of LDS per workgroup (limit 163840): the candidate count is too large for this particle count");
-    HIPCHK(c, c->partial.ensure((size_t)std::max(c->plan.grid_x, P == 1 ? single_particle_grid(B) : 0) * c->plan.Ppad * kNSums));
+    HIPCHK(c, c->partial.ensure((size_t)std::max(c->plan.grid_x, P == 1 ? single_particle_grid(Bi) : 0) * c->plan.Ppad * kNSums));
   } else {
     c->plan = AccumPlan{};
     c->plan.f32 = c->accum_mode == 3 ? 1 : c->accum_mode;
   }
-  if (c->plan.f32 != 3) HIPCHK(c, c->table.ensure((size_t)B * c->K * 3));  // the split variant gathers from the target cloud
-  if (c->plan.f32 == 3) { HIPCHK(c, c->tablea.ensure((size_t)B * 128)); HIPCHK(c, c->anchor.ensure((size_t)B * 3)); }
-  if (c->plan.f32 == 3) { HIPCHK(c, c->kbest.ensure((size_t)B * c->plan.Ppad)); HIPCHK(c, c->kidx.ensure((size_t)B * c->plan.Ppad)); }
-  else HIPCHK(c, c->tablef.ensure((size_t)B * c->K));
+  if (c->plan.f32 != 3) HIPCHK(c, c->table.ensure((size_t)Bt * c->K * 3));  // the split variant gathers from the target cloud
+  if (c->plan.f32 == 3) { HIPCHK(c, c->tablea.ensure((size_t)Bt * 128)); HIPCHK(c, c->anchor.ensure((size_t)Bt * 3)); }
+  if (c->plan.f32 == 3) { HIPCHK(c, c->kbest.ensure((size_t)Bi * c->plan.Ppad)); HIPCHK(c, c->kidx.ensure((size_t)Bi * c->plan.Ppad)); }
+  else HIPCHK(c, c->tablef.ensure((size_t)Bt * c->K));
   if (c->prm.record_trace) {
-    HIPCHK(c, c->trcorr.ensure((size_t)I * P * B));
+    HIPCHK(c, c->trcorr.ensure((size_t)I * P * Bi));
     HIPCHK(c, c->trH.ensure((size_t)I * P * 36));
     HIPCHK(c, c->trb.ensure((size_t)I * P * 6));
     HIPCHK(c, c->trN.ensure((size_t)I * P * 6));
     HIPCHK(c, c->trphi.ensure((size_t)I * P * 6));
     HIPCHK(c, c->trh.ensure((size_t)I + 1));
-    HIPCHK(c, hipMemsetAsync(c->trcorr.p, 0xff, (size_t)I * P * B * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->trcorr.p, 0xff, (size_t)I * P * Bi * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->trH.p, 0, (size_t)I * P * 36 * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->trb.p, 0, (size_t)I * P * 6 * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->trN.p, 0, (size_t)I * P * 6 * 8, c->stream));
@@ -622,6 +674,10 @@ int svnicp_align_begin(svnicp_ctx* c) {
     z.ctl = c->ctl.p; z.iterations = I;
     HIPCHK(c, launch_init_particles(c->init_pose.p, P, c->pose0, 2, c->R.p, c->t.p, c->Rtot.p, c->pose_out.p, 0,
                                     nullptr, c->stream, &z));
+  }
+  if (c->mb_batch > 0 && !c->mb_explicit) {   // the table of the n-th registration after svnicp_set_minibatch
+    c->mb_base = minibatch_stream_base(c->mb_seed, c->mb_n);
+    c->mb_n += 1;
   }
   c->particles_dirty = false;
   c->began = true;
@@ -684,7 +740,7 @@ static int stage_a(svnicp_ctx* c, const double* qsrc, const Pose0& pose, int K, 
       k.torig = c->torig.p; k.tile_box = c->tile_box.p; k.emax_bits = c->emax.p;
       k.M = c->M; k.Mp = c->Mp; k.n_tiles = (int)(c->Mp / 512); k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = c->scan_S2;
       k.pool = c->pool2.p; k.out_idx = out_idx; k.out_d2 = out_d2;
-      k.arena = c->arena.p; k.chunk_tab = c->chunk_tab.p; k.arena_cap = c->arena_cap; k.tab_rows = c->B;
+      k.arena = c->arena.p; k.chunk_tab = c->chunk_tab.p; k.arena_cap = c->arena_cap; k.tab_rows = c->qrows;
       k.scan_split = c->tune.scan_split == 4 ? 4 : 8;
       {  // a small stride coprime to n_groups: 17 sweeps over the curve (C3 1.04 -> 0.98 ms, C5 1.83 -> 1.65 ms against natural order)
         const unsigned int ng = (unsigned int)((n + 63) / 64);
@@ -694,7 +750,7 @@ static int stage_a(svnicp_ctx* c, const double* qsrc, const Pose0& pose, int K, 
         if (ng <= 2 || st >= ng) st = 1;
         k.group_stride = st;
       }
-      HIPCHK(c, hipMemsetAsync(c->chunk_tab.p, 0xff, ((size_t)c->B * kTilesChunks + 16 + (size_t)(c->B + 63) / 64 + 1) * sizeof(int32_t), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->chunk_tab.p, 0xff, ((size_t)c->qrows * kTilesChunks + 16 + (size_t)(c->qrows + 63) / 64 + 1) * sizeof(int32_t), c->stream));
       k.fail_list = c->fail_list.p; k.fail_count = c->fail_count.p; k.fail_tau = c->fail_tau.p; k.qrec = c->qrec.p;
       a.qthr = c->fail_tau.p;
       if (c->prm.record_trace) { HIPCHK(c, c->stat_n.ensure((size_t)c->B)); k.stat_n = c->stat_n.p; }
@@ -748,6 +804,24 @@ int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
   if (!c->began) return fail(c, SVNICP_ERR_INVALID, "svnicp_stage_candidates: call svnicp_align_begin first");
   if (b_lo < 0 || b_hi > c->B || b_lo > b_hi) return fail(c, SVNICP_ERR_INVALID, "svnicp_stage_candidates: bad row range");
   if (bind(c)) return SVNICP_ERR_HIP;
+  if (c->mb_on) {
+    // mini-batch: draw (or validate) the table, compact the drawn rows, stage A on those, expand to the epoch-major layout
+    if (b_lo != 0 || b_hi != c->B)
+      return fail(c, SVNICP_ERR_INVALID, "svnicp_stage_candidates: in mini-batch mode only the whole range (0, B) is accepted");
+    MinibatchArgs m{};
+    m.explicit_idx = c->mb_explicit ? c->mb_tab.p : nullptr; m.idx = c->mb_idx.p; m.n = c->mb_rows; m.B = c->B; m.base = c->mb_base;
+    m.flag = c->mb_flag.p; m.pos = c->mb_pos.p; m.block_sums = c->mb_bsum.p; m.mbctl = c->mb_ctl.p; m.ctl = c->ctl.p;
+    m.src = c->src.p; m.src_u = c->mb_src_u.p; m.n_q = c->mb_nq;
+    HIPCHK(c, prof_begin(c, KC_KNN));
+    HIPCHK(c, launch_minibatch_draw_compact(m, c->stream));
+    const int rc = stage_a(c, c->mb_src_u.p, c->pose0, c->K, c->cand_idx.p, c->cand_d2.p, 0, c->mb_nq);
+    if (rc) return rc;
+    HIPCHK(c, launch_minibatch_expand(m, c->cand_idx.p, c->K, c->mb_src.p, c->mb_cand.p, c->stream));
+    HIPCHK(c, prof_end(c));
+    c->mb_have = true;
+    c->mb_check = c->mb_explicit && c->mb_tab_h.empty();
+    return SVNICP_OK;
+  }
   HIPCHK(c, prof_begin(c, KC_KNN));
   const int rc = stage_a(c, c->src.p, c->pose0, c->K, c->cand_idx.p, c->cand_d2.p, b_lo, b_hi);
   if (rc) return rc;
@@ -765,12 +839,15 @@ int svnicp_build_candidate_table(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (!c->began) return fail(c, SVNICP_ERR_INVALID, "svnicp_build_candidate_table: call svnicp_align_begin first");
   if (bind(c)) return SVNICP_ERR_HIP;
+  if (c->mb_on && !c->mb_have) return fail(c, SVNICP_ERR_INVALID, "svnicp_build_candidate_table: call svnicp_stage_candidates(0, B) first");
   HIPCHK(c, prof_begin(c, KC_TABLE));
+  const int32_t* cand = c->mb_on ? c->mb_cand.p : c->cand_idx.p;   // mini-batch: one table row per drawn position
+  const int64_t rows = c->mb_on ? c->mb_rows : c->B;
   if (c->plan.f32 == 3)
-    HIPCHK(c, launch_build_table3(c->cand_idx.p, c->B, c->K, c->tgt.p, c->M, c->plan.f32 == 3 ? nullptr : c->table.p,
+    HIPCHK(c, launch_build_table3(cand, rows, c->K, c->tgt.p, c->M, c->plan.f32 == 3 ? nullptr : c->table.p,
                                   c->anchor.p, c->tablea.p, c->cmaxb.p, c->stream));
   else
-    HIPCHK(c, launch_build_table2(c->cand_idx.p, c->B, c->K, c->tgt.p, c->M, c->table.p, c->tablef.p, c->cmaxb.p, c->stream));
+    HIPCHK(c, launch_build_table2(cand, rows, c->K, c->tgt.p, c->M, c->table.p, c->tablef.p, c->cmaxb.p, c->stream));
   HIPCHK(c, prof_end(c));
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   c->have_candidates = true;
@@ -842,6 +919,17 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
   a.Rtot = c->Rtot.p; a.B = c->B; a.K = c->K;
   a.p_lo = c->p_lo; a.p_hi = c->p_hi; a.max_dist = c->prm.max_dist; a.partial = c->partial.p; a.ctl = c->ctl.p;
   a.corr = c->prm.record_trace ? c->trcorr.p + (size_t)it * c->P * c->B : nullptr;
+  if (c->mb_on) {
+    // mini-batch: the rows of this iteration lie contiguously at [it * batch, (it + 1) * batch) of the epoch-major tables, so
+    // the kernels see a cloud of `batch` rows; kbest / kidx / partial are per-iteration scratch
+    const size_t r0 = (size_t)it * c->mb_batch;
+    a.src = c->mb_src.p + 3 * r0; a.cand = c->mb_cand.p + r0 * c->K; a.cmax = c->cmaxb.p + r0; a.B = c->mb_batch;
+    if (c->table.p) a.table = c->table.p + r0 * c->K * 3;
+    if (c->tablef.p) a.tablef = c->tablef.p + r0 * c->K;
+    if (c->tablea.p) a.tablea = c->tablea.p + r0 * 128;
+    if (c->anchor.p) a.anchor = c->anchor.p + 3 * r0;
+    if (c->prm.record_trace) a.corr = c->trcorr.p + (size_t)it * c->P * c->mb_batch;
+  }
   a.svgd = c->prm.mode == SVNICP_MODE_SVGD ? 1 : 0;
   a.fin_iteration = -1;
   if (c->defer_fin && it >= 1) {   // the previous iteration's early-stop decision rides on this iteration's search launch
@@ -1032,6 +1120,20 @@ static int check_small_kernel(svnicp_ctx* c) {
   return SVNICP_OK;
 }
 
+// an explicit mini-batch table in DEVICE memory is validated by the draw kernel: its flag is read once the stream has drained
+static int check_minibatch_table(svnicp_ctx* c) {
+  if (!c->mb_check) return SVNICP_OK;
+  c->mb_check = false;
+  int w[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(w, c->mb_ctl.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (w[0]) {
+    c->have_result = false; c->finish_seen = true;   // nothing ran behind the flag: no result, no finish_iter to fold in
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the mini-batch index table holds a value outside [0, B); the registration did not run");
+  }
+  return SVNICP_OK;
+}
+
 int svnicp_align(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (c->shard_set && (c->p_lo != 0 || c->p_hi != c->P))
@@ -1042,6 +1144,7 @@ int svnicp_align(svnicp_ctx* c) {
   if (rc) return rc;  // negative status, or SVNICP_NO_OPTIMIZER
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if ((rc = check_small_kernel(c))) return rc;
+  if ((rc = check_minibatch_table(c))) return rc;
   c->host_stats_valid = c->h_stats != nullptr;
   return SVNICP_ALIGN_SUCCESS;
 }
@@ -1188,15 +1291,73 @@ int svnicp_get_kernel_ms(svnicp_ctx* c, double* ms5, int32_t* launches5) {  // S
   return SVNICP_OK;
 }
 
+static const char* const kMbCandMsg = "mini-batch mode: stage A ran on the drawn rows only, use svnicp_get_minibatch_candidates";
 int svnicp_get_candidates(svnicp_ctx* c, int32_t* out) {
   CTX_CHECK(c);
   if (!c->have_candidates) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
+  if (c->mb_on) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_get_candidates: ") + kMbCandMsg);
   return fetch(c, out, c->cand_idx.p, (size_t)c->B * c->K * 4);
 }
 int svnicp_get_candidate_dist2(svnicp_ctx* c, double* out) {
   CTX_CHECK(c);
   if (!c->have_candidates) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
+  if (c->mb_on) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_get_candidate_dist2: ") + kMbCandMsg);
   return fetch(c, out, c->cand_d2.p, (size_t)c->B * c->K * 8);
+}
+
+// ---- SteinICPParam::use_minibatch / batch_size ----
+int svnicp_set_minibatch(svnicp_ctx* c, int batch_size, uint64_t seed) {
+  CTX_CHECK(c);
+  c->mb_batch = batch_size;   // a negative value is refused by svnicp_align_begin
+  c->mb_seed = seed; c->mb_n = 0;
+  c->mb_explicit = false; c->mb_tab_I = 0; c->mb_tab_h.clear(); c->mb_tab_checked_B = -1;
+  c->have_candidates = false;
+  return SVNICP_OK;
+}
+
+int svnicp_set_minibatch_indices(svnicp_ctx* c, const int32_t* idx, int iterations, int batch_size, int mem_kind) {
+  CTX_CHECK(c);
+  if (!idx || iterations < 1 || batch_size < 1)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_set_minibatch_indices: need a table of iterations >= 1 rows of batch_size >= 1 indices");
+  const int64_t n = (int64_t)iterations * batch_size;
+  if (n > kMinibatchMaxRows) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_minibatch_indices: iterations * batch_size exceeds 2^22 table rows");
+  if (bind(c)) return SVNICP_ERR_HIP;
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // a registration in flight may still read the previous table
+  HIPCHK(c, c->mb_tab.ensure((size_t)n));
+  c->mb_tab_h.clear();
+  if (mem_kind == SVNICP_MEM_DEVICE) {
+    HIPCHK(c, hipMemcpyAsync(c->mb_tab.p, idx, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    c->mb_tab_h.assign(idx, idx + n);
+    HIPCHK(c, hipMemcpyAsync(c->mb_tab.p, c->mb_tab_h.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->mb_batch = batch_size; c->mb_explicit = true; c->mb_tab_I = iterations; c->mb_tab_checked_B = -1;
+  c->have_candidates = false;
+  return SVNICP_OK;
+}
+
+#define NEED_MINIBATCH(c, what)                                                                                          \
+  do {                                                                                                                   \
+    CTX_CHECK(c);                                                                                                        \
+    if (!(c)->mb_on || !(c)->mb_have) return fail((c), SVNICP_ERR_INVALID, what ": no registration in mini-batch mode yet"); \
+  } while (0)
+int svnicp_get_minibatch_indices(svnicp_ctx* c, int32_t* out) {
+  NEED_MINIBATCH(c, "svnicp_get_minibatch_indices");
+  return fetch(c, out, c->mb_idx.p, (size_t)c->mb_rows * 4);
+}
+int svnicp_get_minibatch_candidates(svnicp_ctx* c, int32_t* out) {
+  NEED_MINIBATCH(c, "svnicp_get_minibatch_candidates");
+  return fetch(c, out, c->mb_cand.p, (size_t)c->mb_rows * c->K * 4);
+}
+int svnicp_get_minibatch_rows(svnicp_ctx* c, int64_t out2[2]) {
+  NEED_MINIBATCH(c, "svnicp_get_minibatch_rows");
+  if (!out2) return SVNICP_ERR_INVALID;
+  int w[2] = {0, 0};
+  const int rc = fetch(c, w, c->mb_ctl.p, sizeof w);
+  if (rc) return rc;
+  out2[0] = w[1]; out2[1] = c->mb_nq;
+  return SVNICP_OK;
 }
 
 int svnicp_get_trace(svnicp_ctx* c, int32_t* corr, double* H, double* b, double* N, double* phi, double* h) {
@@ -1204,7 +1365,7 @@ int svnicp_get_trace(svnicp_ctx* c, int32_t* corr, double* H, double* b, double*
   if (!c->prm.record_trace) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_trace: params.record_trace was 0");
   const size_t I = (size_t)c->prm.iterations, P = (size_t)c->P;
   int rc = 0;
-  if (corr && (rc = fetch(c, corr, c->trcorr.p, I * P * (size_t)c->B * 4))) return rc;
+  if (corr && (rc = fetch(c, corr, c->trcorr.p, I * P * (size_t)(c->mb_on ? c->mb_batch : c->B) * 4))) return rc;
   if (H && (rc = fetch(c, H, c->trH.p, I * P * 36 * 8))) return rc;
   if (b && (rc = fetch(c, b, c->trb.p, I * P * 6 * 8))) return rc;
   if (N && (rc = fetch(c, N, c->trN.p, I * P * 6 * 8))) return rc;

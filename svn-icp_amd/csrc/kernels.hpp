@@ -251,6 +251,30 @@ const double* update_step_norms(const UpdateArgs& a);   // [P] norms the early-s
 hipError_t launch_reduce_partials(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* sums, const int* ctl,
                                   hipStream_t st);
 size_t update_uctl_doubles(int P);
+// ---------------- mini-batch tables (minibatch.hip) ----------------
+struct MinibatchArgs {
+  const int32_t* explicit_idx;  // [n] a caller's table (validated by the draw kernel), or nullptr: generated from `base`
+  int32_t* idx;                 // [n] the table this registration uses (n = iterations * batch, epoch-major)
+  int64_t n, B;                 // table positions, source rows
+  unsigned long long base;      // splitmix64(seed * 1000003 + registration): idx[j] = umul64hi(splitmix64(base + j), B)
+  int32_t* flag;                // [B] 1 = row drawn
+  int32_t* pos;                 // [B] position of a drawn row among the unique rows (ascending), -1 = not drawn
+  int32_t* block_sums;          // [minibatch_scan_blocks(B)]
+  int* mbctl;                   // [0] an explicit table held a value outside [0, B), [1] unique rows U
+  int* ctl;                     // the registration's control words: [0] stop flag, raised with mbctl[0]
+  const double* src;            // [B][3]
+  double* src_u;                // [n_q][3] unique rows, then copies of the last one
+  int64_t n_q;                  // queries stage A runs: min(B, n)
+};
+constexpr int64_t kMinibatchMaxRows = 1ll << 22;   // iterations * batch: about 2.5 KB of per-row tables each (10 GB)
+unsigned long long minibatch_stream_base(unsigned long long seed, unsigned long long registration);
+int64_t minibatch_scan_blocks(int64_t B);
+// memsets + draw/mark + scan + compaction + fill of src_u; no host synchronisation
+hipError_t launch_minibatch_draw_compact(const MinibatchArgs& a, hipStream_t st);
+// src_mb [n][3] = src[idx[j]], cand_mb [n][K] = cand_u[pos[idx[j]]] (one wave per position)
+hipError_t launch_minibatch_expand(const MinibatchArgs& a, const int32_t* cand_u, int K, double* src_mb, int32_t* cand_mb,
+                                   hipStream_t st);
+
 struct StatsArgs { const double* pose; int P; int mode; double* out; /* mean6,var6,cov36,weightsP */ };
 hipError_t launch_stats(const StatsArgs& a, hipStream_t st);
 

@@ -20,6 +20,9 @@ enum SteinICPState { ALIGN_SUCCESS = 1, NO_OPTIMIZER = 2 };  // SVGDICP.h:59-62
 
 struct SteinICPParam {  // SVGDICP.h:41-57 (same names and defaults; solver-relevant fields)
   int iterations = 50;
+  bool use_minibatch = false;   // SVGDICP::mini_batch_pair_generator (SVGDICP.cpp:176-199): batch_size rows per iteration
+  int batch_size = 50;
+  uint64_t minibatch_seed = 0;  // seed of the generated tables (not in the reference; svnicp_hip.h "mini-batch")
   double lr = 0.02;
   double max_dist = 1.0;
   std::string optimizer = "Adam";
@@ -45,6 +48,7 @@ class SVGDICP {
     q.optimizer = p.optimizer == "Adam" ? SVNICP_OPT_ADAM : p.optimizer == "RMSprop" ? SVNICP_OPT_RMSPROP
                 : p.optimizer == "SGD" ? SVNICP_OPT_SGD : p.optimizer == "Adagrad" ? SVNICP_OPT_ADAGRAD : SVNICP_OPT_NONE;
     if (svnicp_create(&q, device, init_pose.data(), P_, &h_) != 0) throw std::runtime_error(svnicp_last_error(nullptr));
+    if (p.use_minibatch) { batch_ = p.batch_size; chk(svnicp_set_minibatch(h_, p.batch_size, p.minibatch_seed)); }
   }
   virtual ~SVGDICP() { svnicp_destroy(h_); }
   SVGDICP(const SVGDICP&) = delete;
@@ -94,6 +98,19 @@ class SVGDICP {
   std::vector<double> get_runtime() { std::vector<double> o(3); chk(svnicp_get_runtime(h_, o.data())); return o; }
   void set_k(int k) { chk(svnicp_set_k(h_, k)); }
   void set_threshold(double max_dist) { chk(svnicp_set_max_dist(h_, max_dist)); }
+  // mini-batch (svnicp_hip.h "mini-batch"): rows per iteration from now on (0 = full batch), or an explicit table
+  void set_minibatch(int batch_size, uint64_t seed = 0) { chk(svnicp_set_minibatch(h_, batch_size, seed)); batch_ = batch_size; }
+  void set_minibatch_indices(const std::vector<int32_t>& table, int iterations, int batch_size) {
+    if (table.size() != (size_t)iterations * (size_t)batch_size) throw std::runtime_error("set_minibatch_indices: table size");
+    chk(svnicp_set_minibatch_indices(h_, table.data(), iterations, batch_size, SVNICP_MEM_HOST));
+    batch_ = batch_size;
+  }
+  std::vector<int32_t> get_minibatch_indices() {   // [iterations][batch_size] of the last registration
+    std::vector<int32_t> o((size_t)I_ * (size_t)(batch_ > 0 ? batch_ : 0));
+    chk(svnicp_get_minibatch_indices(h_, o.data()));
+    return o;
+  }
+  std::array<int64_t, 2> get_minibatch_rows() { std::array<int64_t, 2> o{}; chk(svnicp_get_minibatch_rows(h_, o.data())); return o; }
   svnicp_ctx* handle() { return h_; }
 
  protected:
@@ -101,6 +118,7 @@ class SVGDICP {
   [[noreturn]] void fail() { throw std::runtime_error(svnicp_last_error(h_)); }
   svnicp_ctx* h_ = nullptr;
   int P_, I_;
+  int batch_ = 0;
 };
 
 class SVNICP final : public SVGDICP {

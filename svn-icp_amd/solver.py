@@ -40,8 +40,8 @@ class SteinICPState(enum.IntEnum):  # include/core/SVGDICP.h:59-62
 @dataclass
 class SteinICPParam:  # include/core/SVGDICP.h:41-57 (same field names and defaults)
     iterations: int = 50
-    use_minibatch: bool = False      # never set by the reference node; ignored by its solver
-    batch_size: int = 50             # overwritten with N_src by the reference (SVGDICP.cpp:181)
+    use_minibatch: bool = False      # never set by the reference NODE; its solver acts on it (SVGDICP.cpp:176-199, :83; SVNICP.cpp:53)
+    batch_size: int = 50             # rows per iteration when use_minibatch is set; else the reference uses N_src (SVGDICP.cpp:181)
     lr: float = 0.02
     max_dist: float = 1.0
     normalize_cloud: bool = True     # normalize_factor_ == 1 in the reference (SVGDICP.cpp:32)
@@ -52,6 +52,7 @@ class SteinICPParam:  # include/core/SVGDICP.h:41-57 (same field names and defau
     KNN_count: int = 100
     SVN_full_grad: bool = True
     record_trace: bool = False       # test hook (not in the reference)
+    minibatch_seed: int = 0          # seed of the generated mini-batch tables (not in the reference: see minibatch_indices)
 
 
 @dataclass
@@ -67,6 +68,36 @@ def initialize_particles(particle_count: int, ub, lb, rng: np.random.Generator |
     rng = rng or np.random.default_rng()
     ub, lb = np.asarray(ub, np.float64).reshape(6, 1), np.asarray(lb, np.float64).reshape(6, 1)
     return (ub - lb) * rng.random((6, particle_count)) + lb
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64_int(x: int) -> int:
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    z = x
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def minibatch_indices(seed: int, registration: int, iterations: int, batch_size: int, n_source: int) -> np.ndarray:
+    """The mini-batch table the library generates on the device for registration ``registration`` (0, 1, ...) after
+    ``svnicp_set_minibatch(ctx, batch_size, seed)``, bit for bit (include/svnicp_hip.h): at flat position j
+
+        base = splitmix64(seed * 1000003 + registration);  bits = splitmix64(base + j);  idx = floor(bits * B / 2^64)
+
+    Returns int32 [iterations, batch_size] with values in [0, n_source)."""
+    from .scans import _splitmix64
+    I, b, B = int(iterations), int(batch_size), int(n_source)
+    if I < 0 or b < 0 or not 1 <= B < (1 << 31):
+        raise ValueError("need iterations >= 0, batch_size >= 0 and 1 <= n_source < 2^31")
+    base = _splitmix64_int((int(seed) * 1000003 + int(registration)) & _M64)
+    with np.errstate(over="ignore"):
+        bits = _splitmix64(np.arange(I * b, dtype=np.uint64) + np.uint64(base))
+    Bu, lo32, s32 = np.uint64(B), np.uint64(0xFFFFFFFF), np.uint64(32)
+    idx = ((bits >> s32) * Bu + (((bits & lo32) * Bu) >> s32)) >> s32      # the high 64 bits of bits * B, for B < 2^32
+    return idx.astype(np.int32).reshape(I, b)
 
 
 def _is_torch_cuda(x) -> bool:
@@ -94,6 +125,9 @@ class _SolverBase:
         self._B = self._M = 0
         self._K = int(parameters.KNN_count)
         self._keep = None
+        self._mb = 0      # rows per iteration in mini-batch mode, 0 = full batch
+        if parameters.use_minibatch:
+            self.set_minibatch(int(parameters.batch_size), int(parameters.minibatch_seed))
 
     # -- plumbing -------------------------------------------------------------------------
     @staticmethod
@@ -200,6 +234,52 @@ class _SolverBase:
     def set_option(self, name: str, value) -> None:
         """Test / profiling knob of this context (include/svnicp_hip.h: svnicp_set_option)."""
         self._check(self._L.svnicp_set_option(self._h, str(name).encode(), str(value).encode()), "svnicp_set_option")
+
+    # -- mini-batch (SteinICPParam.use_minibatch / batch_size; include/svnicp_hip.h "mini-batch") -------------------------
+    def set_minibatch(self, batch_size: int, seed: int = 0) -> None:
+        """Rows per iteration from now on (0 = full batch); registration n after this call uses
+        ``minibatch_indices(seed, n, iterations, batch_size, B)``."""
+        self._check(self._L.svnicp_set_minibatch(self._h, int(batch_size), int(seed) & _M64), "svnicp_set_minibatch")
+        self._mb = max(0, int(batch_size))
+
+    def set_minibatch_indices(self, table) -> None:
+        """An explicit table int32 [iterations, batch_size] (numpy, or an int32 CUDA torch tensor), used by every following
+        registration until ``set_minibatch`` is called again."""
+        if _is_torch_cuda(table):
+            import torch
+            t = table.to(torch.int32).contiguous()
+            if t.dim() != 2:
+                raise ValueError("the mini-batch table must be [iterations, batch_size]")
+            torch.cuda.current_stream(t.device).synchronize()
+            ptr, shape, kind = C.c_void_p(t.data_ptr()), t.shape, 1
+        else:
+            t = np.ascontiguousarray(np.asarray(table), np.int32)
+            if t.ndim != 2:
+                raise ValueError("the mini-batch table must be [iterations, batch_size]")
+            ptr, shape, kind = t.ctypes.data_as(C.c_void_p), t.shape, 0
+        self._check(self._L.svnicp_set_minibatch_indices(self._h, ptr, int(shape[0]), int(shape[1]), kind),
+                    "svnicp_set_minibatch_indices")
+        self._mb = int(shape[1])
+
+    def get_minibatch_indices(self) -> np.ndarray:
+        """The table the last registration used, int32 [iterations, batch_size]."""
+        out = np.zeros((int(self.config.iterations), self._mb), np.int32)
+        self._check(self._L.svnicp_get_minibatch_indices(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))),
+                    "svnicp_get_minibatch_indices")
+        return out
+
+    def get_minibatch_candidates(self) -> np.ndarray:
+        """Candidate target indices of every drawn position, int32 [iterations, batch_size, K]."""
+        out = np.zeros((int(self.config.iterations), self._mb, self._K), np.int32)
+        self._check(self._L.svnicp_get_minibatch_candidates(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))),
+                    "svnicp_get_minibatch_candidates")
+        return out
+
+    def get_minibatch_rows(self) -> tuple:
+        """(unique source rows drawn U, queries stage A ran n_q) of the last registration in mini-batch mode."""
+        out = (C.c_int64 * 2)()
+        self._check(self._L.svnicp_get_minibatch_rows(self._h, out), "svnicp_get_minibatch_rows")
+        return int(out[0]), int(out[1])
 
     def set_threshold(self, max_dist: float):
         self._check(self._L.svnicp_set_max_dist(self._h, float(max_dist)), "svnicp_set_max_dist")
@@ -319,6 +399,8 @@ class _SolverBase:
 
     def get_trace(self, with_corr: bool = True) -> dict:
         I, P, B = int(self.config.iterations), self._P, self._B
+        if self._mb > 0 and I > 0:
+            B = self._mb      # mini-batch: corr is [I][P][batch_size]
         d = dict(H=np.zeros((I, P, 36)), b=np.zeros((I, P, 6)), newton=np.zeros((I, P, 6)), phi=np.zeros((I, P, 6)),
                  h=np.zeros(I))
         corr = np.zeros((I, P, B), np.int32) if with_corr else None
