@@ -208,16 +208,6 @@ __global__ __launch_bounds__(256) void k_seg_emit(const float* __restrict__ in, 
   }
 }
 
-std::string g_seg_error;
-
-int sfail(svnicp_prep* p, int code, const std::string& msg) { if (p) p->err = msg; else g_seg_error = msg; return code; }
-#define SCHK(p, expr)                                                                                                       \
-  do {                                                                                                                      \
-    const hipError_t _e = (expr);                                                                                           \
-    if (_e != hipSuccess)                                                                                                   \
-      return sfail((p), _e == hipErrorOutOfMemory ? SVNICP_ERR_NOMEM : SVNICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 svnicp_seg_params make_params(int n, int h, float rx, float ry, float bottom, int g) {
   svnicp_seg_params s;
   s.struct_size = (int32_t)sizeof(svnicp_seg_params);
@@ -252,24 +242,24 @@ int svnicp_seg_default_params(int sensor, svnicp_seg_params* out) {
 
 int svnicp_prep_segment(svnicp_prep* p, const float* xyz, int64_t n, int mem_kind, const svnicp_seg_params* params, int64_t* n_segmented) {
   if (!p || !n_segmented || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL)
-    return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: bad argument");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: bad argument");
   svnicp_seg_params prm;
   if (params) {
     if (params->struct_size != (int32_t)sizeof(svnicp_seg_params))
-      return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: struct_size != sizeof(svnicp_seg_params)");
+      return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: struct_size != sizeof(svnicp_seg_params)");
     prm = *params;
   } else {
     svnicp_seg_default_params(SVNICP_SEG_HDL64E, &prm);
   }
   if (!(prm.ground_scan_ind >= 1 && prm.ground_scan_ind < prm.n_scan && prm.n_scan <= 128))
-    return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: need 1 <= ground_scan_ind < n_scan <= 128");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: need 1 <= ground_scan_ind < n_scan <= 128");
   if (!(prm.horizon_scan >= 1 && (int64_t)prm.n_scan * prm.horizon_scan <= (int64_t)1 << 19))
-    return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: need horizon_scan >= 1 and n_scan * horizon_scan <= 2^19");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: need horizon_scan >= 1 and n_scan * horizon_scan <= 2^19");
   if (!(std::isfinite(prm.ang_res_x) && prm.ang_res_x > 0.0f && std::isfinite(prm.ang_res_y) && prm.ang_res_y > 0.0f))
-    return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: ang_res_x / ang_res_y must be finite and positive");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: ang_res_x / ang_res_y must be finite and positive");
   if (!(std::isfinite(prm.ang_bottom) && std::isfinite(prm.min_range) && std::isfinite(prm.mount_angle) && std::isfinite(prm.segment_theta)))
-    return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: ang_bottom / min_range / mount_angle / segment_theta must be finite");
-  SCHK(p, hipSetDevice(p->device));
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_segment: ang_bottom / min_range / mount_angle / segment_theta must be finite");
+  HIPCHK(p, hipSetDevice(p->device));
   auto& S = p->seg;
   S.n_out = 0;
   *n_segmented = 0;
@@ -285,19 +275,19 @@ int svnicp_prep_segment(svnicp_prep* p, const float* xyz, int64_t n, int mem_kin
   S.n_pix = npix;
   const float* din = xyz;
   if (n > 0 && mem_kind != SVNICP_MEM_DEVICE) {
-    SCHK(p, S.in.ensure((size_t)n * 3));
-    SCHK(p, hipMemcpyAsync(S.in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(p, S.in.ensure((size_t)n * 3));
+    HIPCHK(p, hipMemcpyAsync(S.in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
     din = S.in.p;
   }
   const int64_t cap_out = n < npix ? n : npix;   // at most one point per pixel
-  SCHK(p, S.xyz.ensure((size_t)(cap_out > 0 ? cap_out : 1) * 3)); SCHK(p, S.index.ensure((size_t)(cap_out > 0 ? cap_out : 1)));
-  SCHK(p, S.owner.ensure((size_t)npix)); SCHK(p, S.parent.ensure((size_t)npix)); SCHK(p, S.size.ensure((size_t)npix));
-  SCHK(p, S.range.ensure((size_t)npix)); SCHK(p, S.ground.ensure((size_t)npix)); SCHK(p, S.rows.ensure((size_t)npix * 4));
-  SCHK(p, S.label.ensure((size_t)npix)); SCHK(p, S.flags.ensure((size_t)npix)); SCHK(p, S.pre.ensure((size_t)npix));
-  SCHK(p, hipMemsetAsync(S.owner.p, 0xff, (size_t)npix * 4, p->stream));   // -1: empty
+  HIPCHK(p, S.xyz.ensure((size_t)(cap_out > 0 ? cap_out : 1) * 3)); HIPCHK(p, S.index.ensure((size_t)(cap_out > 0 ? cap_out : 1)));
+  HIPCHK(p, S.owner.ensure((size_t)npix)); HIPCHK(p, S.parent.ensure((size_t)npix)); HIPCHK(p, S.size.ensure((size_t)npix));
+  HIPCHK(p, S.range.ensure((size_t)npix)); HIPCHK(p, S.ground.ensure((size_t)npix)); HIPCHK(p, S.rows.ensure((size_t)npix * 4));
+  HIPCHK(p, S.label.ensure((size_t)npix)); HIPCHK(p, S.flags.ensure((size_t)npix)); HIPCHK(p, S.pre.ensure((size_t)npix));
+  HIPCHK(p, hipMemsetAsync(S.owner.p, 0xff, (size_t)npix * 4, p->stream));   // -1: empty
   if (n > 0) {
     hipLaunchKernelGGL(k_seg_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->stream, din, n, K, S.owner.p);
-    SCHK(p, hipGetLastError());
+    HIPCHK(p, hipGetLastError());
   }
   const unsigned gp = (unsigned)((npix + 255) / 256);
   hipLaunchKernelGGL(k_seg_pixel, dim3(gp), dim3(256), 0, p->stream, din, S.owner.p, K, S.range.p, S.ground.p, S.label.p, S.parent.p,
@@ -305,18 +295,18 @@ int svnicp_prep_segment(svnicp_prep* p, const float* xyz, int64_t n, int mem_kin
   hipLaunchKernelGGL(k_seg_union, dim3(gp), dim3(256), 0, p->stream, S.range.p, S.label.p, K, S.parent.p);
   hipLaunchKernelGGL(k_seg_stats, dim3(gp), dim3(256), 0, p->stream, S.label.p, K, S.parent.p, S.size.p, S.rows.p);
   hipLaunchKernelGGL(k_seg_flags, dim3(gp), dim3(256), 0, p->stream, S.label.p, S.parent.p, S.size.p, S.rows.p, S.ground.p, K, S.flags.p);
-  SCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   size_t b = 0;
-  SCHK(p, rocprim::exclusive_scan(nullptr, b, S.flags.p, S.pre.p, 0ull, (size_t)npix, rocprim::plus<unsigned long long>(), p->stream));
-  SCHK(p, S.tmp.ensure(b));
-  SCHK(p, rocprim::exclusive_scan(S.tmp.p, b, S.flags.p, S.pre.p, 0ull, (size_t)npix, rocprim::plus<unsigned long long>(), p->stream));
+  HIPCHK(p, rocprim::exclusive_scan(nullptr, b, S.flags.p, S.pre.p, 0ull, (size_t)npix, rocprim::plus<unsigned long long>(), p->stream));
+  HIPCHK(p, S.tmp.ensure(b));
+  HIPCHK(p, rocprim::exclusive_scan(S.tmp.p, b, S.flags.p, S.pre.p, 0ull, (size_t)npix, rocprim::plus<unsigned long long>(), p->stream));
   hipLaunchKernelGGL(k_seg_emit, dim3(gp), dim3(256), 0, p->stream, din, S.owner.p, S.parent.p, S.flags.p, S.pre.p, K, S.label.p, S.xyz.p,
                      S.index.p);
-  SCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   unsigned long long last[2] = {0, 0};
-  SCHK(p, hipMemcpyAsync(&last[0], S.pre.p + (npix - 1), 8, hipMemcpyDeviceToHost, p->stream));
-  SCHK(p, hipMemcpyAsync(&last[1], S.flags.p + (npix - 1), 8, hipMemcpyDeviceToHost, p->stream));
-  SCHK(p, hipStreamSynchronize(p->stream));   // the only host synchronisation: the cloud is complete when the call returns
+  HIPCHK(p, hipMemcpyAsync(&last[0], S.pre.p + (npix - 1), 8, hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipMemcpyAsync(&last[1], S.flags.p + (npix - 1), 8, hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipStreamSynchronize(p->stream));   // the only host synchronisation: the cloud is complete when the call returns
   S.n_out = (int64_t)((last[0] + last[1]) & 0xffffffffull);
   *n_segmented = S.n_out;
   return SVNICP_OK;
@@ -327,27 +317,27 @@ const int32_t* svnicp_prep_segmented_index_devptr(svnicp_prep* p) { return p ? p
 
 int svnicp_prep_download_segmented(svnicp_prep* p, float* out_xyz, int32_t* out_index, int64_t cap_points, int64_t* n_out) {
   if (!p || !n_out) return SVNICP_ERR_INVALID;
-  SCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipSetDevice(p->device));
   *n_out = p->seg.n_out;
   const int64_t n = p->seg.n_out < cap_points ? p->seg.n_out : cap_points;
-  if (n > 0 && out_xyz) SCHK(p, hipMemcpyAsync(out_xyz, p->seg.xyz.p, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
-  if (n > 0 && out_index) SCHK(p, hipMemcpyAsync(out_index, p->seg.index.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
-  SCHK(p, hipStreamSynchronize(p->stream));
+  if (n > 0 && out_xyz) HIPCHK(p, hipMemcpyAsync(out_xyz, p->seg.xyz.p, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
+  if (n > 0 && out_index) HIPCHK(p, hipMemcpyAsync(out_index, p->seg.index.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipStreamSynchronize(p->stream));
   return SVNICP_OK;
 }
 
 int svnicp_prep_download_seg_images(svnicp_prep* p, int32_t* owner, float* range, int8_t* ground, int32_t* label, int64_t cap_pixels) {
   if (!p) return SVNICP_ERR_INVALID;
-  if (cap_pixels < p->seg.n_pix) return sfail(p, SVNICP_ERR_INVALID, "svnicp_prep_download_seg_images: cap_pixels < n_scan * horizon_scan");
-  SCHK(p, hipSetDevice(p->device));
+  if (cap_pixels < p->seg.n_pix) return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_download_seg_images: cap_pixels < n_scan * horizon_scan");
+  HIPCHK(p, hipSetDevice(p->device));
   const size_t np = (size_t)p->seg.n_pix;
   if (np > 0) {
-    if (owner) SCHK(p, hipMemcpyAsync(owner, p->seg.owner.p, np * 4, hipMemcpyDeviceToHost, p->stream));
-    if (range) SCHK(p, hipMemcpyAsync(range, p->seg.range.p, np * 4, hipMemcpyDeviceToHost, p->stream));
-    if (ground) SCHK(p, hipMemcpyAsync(ground, p->seg.ground.p, np, hipMemcpyDeviceToHost, p->stream));
-    if (label) SCHK(p, hipMemcpyAsync(label, p->seg.label.p, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (owner) HIPCHK(p, hipMemcpyAsync(owner, p->seg.owner.p, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (range) HIPCHK(p, hipMemcpyAsync(range, p->seg.range.p, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (ground) HIPCHK(p, hipMemcpyAsync(ground, p->seg.ground.p, np, hipMemcpyDeviceToHost, p->stream));
+    if (label) HIPCHK(p, hipMemcpyAsync(label, p->seg.label.p, np * 4, hipMemcpyDeviceToHost, p->stream));
   }
-  SCHK(p, hipStreamSynchronize(p->stream));
+  HIPCHK(p, hipStreamSynchronize(p->stream));
   return SVNICP_OK;
 }
 

@@ -41,7 +41,6 @@
 
 namespace {
 
-using svnicp_prep_detail::PBuf;
 
 __device__ __forceinline__ unsigned long long enc_f64(double v) {   // order-preserving double -> uint64
   const long long b = __double_as_longlong(v);
@@ -283,65 +282,87 @@ __global__ __launch_bounds__(256) void k_deskew_crop(const float* __restrict__ i
   }
 }
 
-std::string g_prep_error;
-
-}  // namespace
-
-namespace {
-
-int pfail(svnicp_prep* p, int code, const std::string& msg) { if (p) p->err = msg; else g_prep_error = msg; return code; }
-#define PCHK(p, expr)                                                                                                       \
-  do {                                                                                                                      \
-    const hipError_t _e = (expr);                                                                                           \
-    if (_e != hipSuccess)                                                                                                   \
-      return pfail((p), _e == hipErrorOutOfMemory ? SVNICP_ERR_NOMEM : SVNICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // out (+ out64) = UniformSampling(in[0..n), radius); *n_out = number of occupied leaves
-int downsample(svnicp_prep* p, const float* in, int64_t n, double radius, PBuf<float>& out, PBuf<double>* out64, int64_t* n_out) {
+int downsample(svnicp_prep* p, const float* in, int64_t n, double radius, GrowBuf<float>& out, GrowBuf<double>* out64, int64_t* n_out) {
   *n_out = 0;
   if (n <= 0) return SVNICP_OK;
   if (!(radius > 0.0)) {   // the host code returns the cloud unchanged
-    PCHK(p, out.ensure((size_t)n * 3));
-    PCHK(p, hipMemcpyAsync(out.p, in, (size_t)n * 12, hipMemcpyDeviceToDevice, p->stream));
+    HIPCHK(p, out.ensure((size_t)n * 3));
+    HIPCHK(p, hipMemcpyAsync(out.p, in, (size_t)n * 12, hipMemcpyDeviceToDevice, p->stream));
     *n_out = n;
     return SVNICP_OK;
   }
   const double inv = 1.0 / radius;
   const unsigned g = (unsigned)((n + 255) / 256);
-  PCHK(p, p->key.ensure((size_t)n)); PCHK(p, p->skey.ensure((size_t)n)); PCHK(p, p->d2bits.ensure((size_t)n));
-  PCHK(p, p->idx.ensure((size_t)n)); PCHK(p, p->sidx.ensure((size_t)n)); PCHK(p, p->flag.ensure((size_t)n)); PCHK(p, p->pre.ensure((size_t)n));
-  PCHK(p, p->run_min.ensure((size_t)n)); PCHK(p, p->run_pos.ensure((size_t)n));
+  HIPCHK(p, p->key.ensure((size_t)n)); HIPCHK(p, p->skey.ensure((size_t)n)); HIPCHK(p, p->d2bits.ensure((size_t)n));
+  HIPCHK(p, p->idx.ensure((size_t)n)); HIPCHK(p, p->sidx.ensure((size_t)n)); HIPCHK(p, p->flag.ensure((size_t)n)); HIPCHK(p, p->pre.ensure((size_t)n));
+  HIPCHK(p, p->run_min.ensure((size_t)n)); HIPCHK(p, p->run_pos.ensure((size_t)n));
   long long* bounds = reinterpret_cast<long long*>(p->scal.p + 1);
   const long long init_b[6] = {INT64_MAX, INT64_MAX, INT64_MAX, INT64_MIN, INT64_MIN, INT64_MIN};
-  PCHK(p, hipMemcpyAsync(bounds, init_b, sizeof init_b, hipMemcpyHostToDevice, p->stream));
+  HIPCHK(p, hipMemcpyAsync(bounds, init_b, sizeof init_b, hipMemcpyHostToDevice, p->stream));
   hipLaunchKernelGGL(k_ds_bounds, dim3(g), dim3(256), 0, p->stream, in, n, inv, bounds);
   hipLaunchKernelGGL(k_ds_keys, dim3(g), dim3(256), 0, p->stream, in, n, radius, inv, bounds, p->key.p, p->d2bits.p, p->idx.p);
-  PCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   size_t b1 = 0, b2 = 0;
-  PCHK(p, rocprim::radix_sort_pairs(nullptr, b1, p->key.p, p->skey.p, p->idx.p, p->sidx.p, (size_t)n, 0, 64, p->stream));
-  PCHK(p, rocprim::exclusive_scan(nullptr, b2, p->flag.p, p->pre.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  PCHK(p, p->tmp.ensure(b1 > b2 ? b1 : b2));
-  PCHK(p, rocprim::radix_sort_pairs(p->tmp.p, b1, p->key.p, p->skey.p, p->idx.p, p->sidx.p, (size_t)n, 0, 64, p->stream));   // stable
+  HIPCHK(p, rocprim::radix_sort_pairs(nullptr, b1, p->key.p, p->skey.p, p->idx.p, p->sidx.p, (size_t)n, 0, 64, p->stream));
+  HIPCHK(p, rocprim::exclusive_scan(nullptr, b2, p->flag.p, p->pre.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  HIPCHK(p, p->tmp.ensure(b1 > b2 ? b1 : b2));
+  HIPCHK(p, rocprim::radix_sort_pairs(p->tmp.p, b1, p->key.p, p->skey.p, p->idx.p, p->sidx.p, (size_t)n, 0, 64, p->stream));   // stable
   hipLaunchKernelGGL(k_ds_run_flags, dim3(g), dim3(256), 0, p->stream, p->skey.p, n, p->flag.p);
-  PCHK(p, hipGetLastError());
-  PCHK(p, rocprim::exclusive_scan(p->tmp.p, b2, p->flag.p, p->pre.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  PCHK(p, hipMemsetAsync(p->run_min.p, 0xff, (size_t)n * 8, p->stream));
-  PCHK(p, hipMemsetAsync(p->run_pos.p, 0x7f, (size_t)n * 4, p->stream));
+  HIPCHK(p, hipGetLastError());
+  HIPCHK(p, rocprim::exclusive_scan(p->tmp.p, b2, p->flag.p, p->pre.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  HIPCHK(p, hipMemsetAsync(p->run_min.p, 0xff, (size_t)n * 8, p->stream));
+  HIPCHK(p, hipMemsetAsync(p->run_pos.p, 0x7f, (size_t)n * 4, p->stream));
   hipLaunchKernelGGL(k_ds_min_d2, dim3(g), dim3(256), 0, p->stream, p->flag.p, p->pre.p, p->sidx.p, p->d2bits.p, n, p->run_min.p);
   hipLaunchKernelGGL(k_ds_min_pos, dim3(g), dim3(256), 0, p->stream, p->flag.p, p->pre.p, p->sidx.p, p->d2bits.p, n, p->run_min.p, p->run_pos.p);
-  PCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   int last[2] = {0, 0};
-  PCHK(p, hipMemcpyAsync(&last[0], p->pre.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipMemcpyAsync(&last[1], p->flag.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipStreamSynchronize(p->stream));
+  HIPCHK(p, hipMemcpyAsync(&last[0], p->pre.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipMemcpyAsync(&last[1], p->flag.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipStreamSynchronize(p->stream));
   const int runs = last[0] + last[1];
-  PCHK(p, out.ensure((size_t)runs * 3));
-  if (out64) PCHK(p, out64->ensure((size_t)runs * 3));
+  HIPCHK(p, out.ensure((size_t)runs * 3));
+  if (out64) HIPCHK(p, out64->ensure((size_t)runs * 3));
   hipLaunchKernelGGL(k_ds_gather, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, in, p->sidx.p, p->run_pos.p, runs, out.p,
                      out64 ? out64->p : (double*)nullptr);
-  PCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   *n_out = runs;
+  return SVNICP_OK;
+}
+
+// the common tail of svnicp_prep_scan and svnicp_prep_scan_deskew: compact the kept points of in[0..n) (p->keep, written by the
+// crop kernel, which also left the largest squared norm, encoded, in scal[0]) and run the two uniform samplings (:559-560)
+int compact_and_sample(svnicp_prep* p, const char* who, const float* in, int64_t n, const unsigned long long* scal, double voxel_size,
+                       double* scan_max_range, int64_t* n_cropped, int64_t* n_map, int64_t* n_source) {
+  size_t b = 0;
+  HIPCHK(p, rocprim::exclusive_scan(nullptr, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  HIPCHK(p, p->tmp.ensure(b));
+  HIPCHK(p, rocprim::exclusive_scan(p->tmp.p, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
+  int last[2] = {0, 0};
+  unsigned long long enc = 0;
+  HIPCHK(p, hipMemcpyAsync(&last[0], p->off.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipMemcpyAsync(&last[1], p->keep.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipMemcpyAsync(&enc, scal, 8, hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(p, hipStreamSynchronize(p->stream));   // the only host synchronisation before the samplings
+  if (enc) {
+    const unsigned long long bits = (enc & 0x8000000000000000ull) ? (enc & 0x7fffffffffffffffull) : ~enc;
+    double m;
+    std::memcpy(&m, &bits, 8);
+    if (m > *scan_max_range) *scan_max_range = m;       // :699 (a squared norm, kept as the reference keeps it; deskewed cloud: :556)
+  }
+  const int64_t nc = (int64_t)last[0] + last[1];
+  HIPCHK(p, p->cropped.ensure((size_t)(nc > 0 ? nc : 1) * 3));
+  hipLaunchKernelGGL(k_prep_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->stream, in, n, p->keep.p, p->off.p, p->cropped.p);
+  HIPCHK(p, hipGetLastError());
+  p->n_cropped = nc;
+  int rc = downsample(p, p->cropped.p, nc, 0.5 * voxel_size, p->map_cloud, nullptr, &p->n_map);
+  if (rc) return rc;
+  rc = downsample(p, p->map_cloud.p, p->n_map, 1.5 * voxel_size, p->source, &p->source64, &p->n_source);
+  if (rc) return rc;
+  if (!(1.5 * voxel_size > 0.0) && p->n_source > 0)   // unchanged cloud: still hand out float64 rows
+    return fail(p, SVNICP_ERR_INVALID, std::string(who) + ": voxel_size must be positive");
+  HIPCHK(p, hipStreamSynchronize(p->stream));   // the clouds are complete when the call returns (other streams read them)
+  *n_cropped = p->n_cropped; *n_map = p->n_map; *n_source = p->n_source;
   return SVNICP_OK;
 }
 
@@ -354,12 +375,12 @@ int svnicp_prep_create(int device, svnicp_prep** out) {
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
-    return pfail(nullptr, SVNICP_ERR_NO_DEVICE, "svnicp_prep_create: no HIP device visible (this library has no CPU path)");
+    return fail<svnicp_prep>(nullptr, SVNICP_ERR_NO_DEVICE, "svnicp_prep_create: no HIP device visible (this library has no CPU path)");
   svnicp_prep* p = new svnicp_prep();
   p->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&p->stream) != hipSuccess || p->scal.ensure(8) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || p->stream.create(hipStreamDefault) != hipSuccess || p->scal.ensure(8) != hipSuccess) {
     delete p;
-    return pfail(nullptr, SVNICP_ERR_HIP, "svnicp_prep_create: stream / allocation failed");
+    return fail<svnicp_prep>(nullptr, SVNICP_ERR_HIP, "svnicp_prep_create: stream / allocation failed");
   }
   *out = p;
   return SVNICP_OK;
@@ -369,69 +390,32 @@ void svnicp_prep_destroy(svnicp_prep* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  p->in.release(); p->cropped.release(); p->map_cloud.release(); p->source.release(); p->source64.release(); p->keep.release(); p->off.release();
-  p->idx.release(); p->sidx.release(); p->flag.release(); p->pre.release(); p->run_pos.release(); p->key.release(); p->skey.release();
-  p->d2bits.release(); p->run_min.release(); p->scal.release(); p->tmp.release();
-  p->deskewed.release(); p->kpts.release(); p->st.release(); p->stamps_in.release(); p->dscal.release();
-  p->seg.release();
-  if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
 
-const char* svnicp_prep_last_error(const svnicp_prep* p) { return p ? p->err.c_str() : g_prep_error.c_str(); }
+const char* svnicp_prep_last_error(const svnicp_prep* p) { return p ? p->err.c_str() : svnicp_prep::create_error().c_str(); }
 
 int svnicp_prep_scan(svnicp_prep* p, const float* xyz, int64_t n, int mem_kind, double min_range, double max_range, double voxel_size,
                      double* scan_max_range, int64_t* n_cropped, int64_t* n_map, int64_t* n_source) {
   if (!p || !scan_max_range || !n_cropped || !n_map || !n_source || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL)
-    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan: bad argument");
-  PCHK(p, hipSetDevice(p->device));
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan: bad argument");
+  HIPCHK(p, hipSetDevice(p->device));
   p->n_cropped = p->n_map = p->n_source = 0;
   *n_cropped = *n_map = *n_source = 0;
   if (n == 0) return SVNICP_OK;
   const float* din = xyz;
   if (mem_kind != SVNICP_MEM_DEVICE) {
-    PCHK(p, p->in.ensure((size_t)n * 3));
-    PCHK(p, hipMemcpyAsync(p->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(p, p->in.ensure((size_t)n * 3));
+    HIPCHK(p, hipMemcpyAsync(p->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
     din = p->in.p;
   }
   // ---- crop (:692-704)
-  PCHK(p, p->keep.ensure((size_t)n)); PCHK(p, p->off.ensure((size_t)n));
-  PCHK(p, hipMemsetAsync(p->scal.p, 0, 8, p->stream));   // encoded doubles are > 0 for every value >= -inf: 0 = nothing seen
+  HIPCHK(p, p->keep.ensure((size_t)n)); HIPCHK(p, p->off.ensure((size_t)n));
+  HIPCHK(p, hipMemsetAsync(p->scal.p, 0, 8, p->stream));   // encoded doubles are > 0 for every value >= -inf: 0 = nothing seen
   const unsigned g = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_prep_crop, dim3(g), dim3(256), 0, p->stream, din, n, min_range * min_range, max_range * max_range, p->keep.p, p->scal.p);
-  PCHK(p, hipGetLastError());
-  size_t b = 0;
-  PCHK(p, rocprim::exclusive_scan(nullptr, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  PCHK(p, p->tmp.ensure(b));
-  PCHK(p, rocprim::exclusive_scan(p->tmp.p, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  int last[2] = {0, 0};
-  unsigned long long enc = 0;
-  PCHK(p, hipMemcpyAsync(&last[0], p->off.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipMemcpyAsync(&last[1], p->keep.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipMemcpyAsync(&enc, p->scal.p, 8, hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipStreamSynchronize(p->stream));
-  if (enc) {
-    const unsigned long long bits = (enc & 0x8000000000000000ull) ? (enc & 0x7fffffffffffffffull) : ~enc;
-    double m;
-    std::memcpy(&m, &bits, 8);
-    if (m > *scan_max_range) *scan_max_range = m;       // :699 (a squared norm, kept as the reference keeps it)
-  }
-  const int64_t nc = (int64_t)last[0] + last[1];
-  PCHK(p, p->cropped.ensure((size_t)(nc > 0 ? nc : 1) * 3));
-  hipLaunchKernelGGL(k_prep_compact, dim3(g), dim3(256), 0, p->stream, din, n, p->keep.p, p->off.p, p->cropped.p);
-  PCHK(p, hipGetLastError());
-  p->n_cropped = nc;
-  // ---- the two uniform samplings (:559-560)
-  int rc = downsample(p, p->cropped.p, nc, 0.5 * voxel_size, p->map_cloud, nullptr, &p->n_map);
-  if (rc) return rc;
-  rc = downsample(p, p->map_cloud.p, p->n_map, 1.5 * voxel_size, p->source, &p->source64, &p->n_source);
-  if (rc) return rc;
-  if (!(1.5 * voxel_size > 0.0) && p->n_source > 0) {   // unchanged cloud: still hand out float64 rows
-    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan: voxel_size must be positive");
-  }
-  PCHK(p, hipStreamSynchronize(p->stream));   // the clouds are complete when the call returns (other streams read them)
-  *n_cropped = p->n_cropped; *n_map = p->n_map; *n_source = p->n_source;
-  return SVNICP_OK;
+  HIPCHK(p, hipGetLastError());
+  return compact_and_sample(p, "svnicp_prep_scan", din, n, p->scal.p, voxel_size, scan_max_range, n_cropped, n_map, n_source);
 }
 
 const float* svnicp_prep_cropped_devptr(svnicp_prep* p) { return p ? p->cropped.p : nullptr; }
@@ -443,14 +427,14 @@ int svnicp_prep_scan_deskew(svnicp_prep* p, const float* xyz, const void* stamps
                             const double delta_xi[6], int flags, double min_range, double max_range, double voxel_size,
                             double* scan_max_range, int64_t* n_cropped, int64_t* n_map, int64_t* n_source) {
   if (!p || !scan_max_range || !n_cropped || !n_map || !n_source || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL)
-    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: bad argument");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: bad argument");
   if (stamp_type != SVNICP_STAMP_F64 && stamp_type != SVNICP_STAMP_F32 && stamp_type != SVNICP_STAMP_U32)
-    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown stamp_type");
-  if (!delta_xi) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is NULL");
+    return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown stamp_type");
+  if (!delta_xi) return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is NULL");
   for (int k = 0; k < 6; ++k)
-    if (!std::isfinite(delta_xi[k])) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is not finite");
-  if (flags & ~SVNICP_DESKEW_KITTI) return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown flags");
-  PCHK(p, hipSetDevice(p->device));
+    if (!std::isfinite(delta_xi[k])) return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: delta_xi is not finite");
+  if (flags & ~SVNICP_DESKEW_KITTI) return fail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: unknown flags");
+  HIPCHK(p, hipSetDevice(p->device));
   p->n_cropped = p->n_map = p->n_source = p->n_deskewed = 0;
   *n_cropped = *n_map = *n_source = 0;
   if (n == 0) return SVNICP_OK;
@@ -458,94 +442,63 @@ int svnicp_prep_scan_deskew(svnicp_prep* p, const float* xyz, const void* stamps
   const float* din = xyz;
   const void* dst = kitti ? nullptr : stamps;   // KITTI derives its stamps from the points (:385-401)
   if (mem_kind != SVNICP_MEM_DEVICE) {
-    PCHK(p, p->in.ensure((size_t)n * 3));
-    PCHK(p, hipMemcpyAsync(p->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(p, p->in.ensure((size_t)n * 3));
+    HIPCHK(p, hipMemcpyAsync(p->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, p->stream));
     din = p->in.p;
     if (dst) {
       const size_t bytes = (size_t)n * (stamp_type == SVNICP_STAMP_F64 ? 8 : 4);
-      PCHK(p, p->stamps_in.ensure(bytes));
-      PCHK(p, hipMemcpyAsync(p->stamps_in.p, dst, bytes, hipMemcpyHostToDevice, p->stream));
+      HIPCHK(p, p->stamps_in.ensure(bytes));
+      HIPCHK(p, hipMemcpyAsync(p->stamps_in.p, dst, bytes, hipMemcpyHostToDevice, p->stream));
       dst = p->stamps_in.p;
     }
   }
   // ---- deskew (:357-447) fused with the crop (:692-704)
-  PCHK(p, p->deskewed.ensure((size_t)n * 3)); PCHK(p, p->keep.ensure((size_t)n)); PCHK(p, p->off.ensure((size_t)n));
-  PCHK(p, p->dscal.ensure(3));
-  if (kitti) PCHK(p, p->kpts.ensure((size_t)n * 3));
-  if (kitti || dst) PCHK(p, p->st.ensure((size_t)n));
-  PCHK(p, hipMemsetAsync(p->dscal.p, 0, 24, p->stream));   // 0 = nothing seen (max norm, max stamp, min stamp)
+  HIPCHK(p, p->deskewed.ensure((size_t)n * 3)); HIPCHK(p, p->keep.ensure((size_t)n)); HIPCHK(p, p->off.ensure((size_t)n));
+  HIPCHK(p, p->dscal.ensure(3));
+  if (kitti) HIPCHK(p, p->kpts.ensure((size_t)n * 3));
+  if (kitti || dst) HIPCHK(p, p->st.ensure((size_t)n));
+  HIPCHK(p, hipMemsetAsync(p->dscal.p, 0, 24, p->stream));   // 0 = nothing seen (max norm, max stamp, min stamp)
   const unsigned g = (unsigned)((n + 255) / 256);
   if (kitti || dst) {   // no stamp field: min == max == 0, the raw frame (:418); k_deskew_crop sees dscal[1] == 0
     constexpr double kVerticalAngleOffset = (0.205 * 3.14159265358979323846) / 180.0;   // :386
     hipLaunchKernelGGL(k_deskew_stamps, dim3(g), dim3(256), 0, p->stream, din, dst, stamp_type, kitti ? 1 : 0, std::sin(kVerticalAngleOffset),
                        std::cos(kVerticalAngleOffset), n, kitti ? p->kpts.p : (float*)nullptr, p->st.p, p->dscal.p);
-    PCHK(p, hipGetLastError());
+    HIPCHK(p, hipGetLastError());
   }
   Twist tw;
   for (int k = 0; k < 6; ++k) tw.v[k] = delta_xi[k];
   hipLaunchKernelGGL(k_deskew_crop, dim3(g), dim3(256), 0, p->stream, din, kitti ? (const float*)p->kpts.p : (const float*)nullptr,
                      (kitti || dst) ? (const double*)p->st.p : (const double*)nullptr, n, tw, min_range * min_range, max_range * max_range,
                      p->deskewed.p, p->keep.p, p->dscal.p);
-  PCHK(p, hipGetLastError());
+  HIPCHK(p, hipGetLastError());
   p->n_deskewed = n;
-  // ---- from here on svnicp_prep_scan's sequence, on the deskewed points
-  size_t b = 0;
-  PCHK(p, rocprim::exclusive_scan(nullptr, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  PCHK(p, p->tmp.ensure(b));
-  PCHK(p, rocprim::exclusive_scan(p->tmp.p, b, p->keep.p, p->off.p, 0, (size_t)n, rocprim::plus<int>(), p->stream));
-  int last[2] = {0, 0};
-  unsigned long long enc = 0;
-  PCHK(p, hipMemcpyAsync(&last[0], p->off.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipMemcpyAsync(&last[1], p->keep.p + (n - 1), sizeof(int), hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipMemcpyAsync(&enc, p->dscal.p, 8, hipMemcpyDeviceToHost, p->stream));
-  PCHK(p, hipStreamSynchronize(p->stream));   // the only host synchronisation before the samplings, as in svnicp_prep_scan
-  if (enc) {
-    const unsigned long long bits = (enc & 0x8000000000000000ull) ? (enc & 0x7fffffffffffffffull) : ~enc;
-    double m;
-    std::memcpy(&m, &bits, 8);
-    if (m > *scan_max_range) *scan_max_range = m;       // :699, on the deskewed cloud (:556)
-  }
-  const int64_t nc = (int64_t)last[0] + last[1];
-  PCHK(p, p->cropped.ensure((size_t)(nc > 0 ? nc : 1) * 3));
-  hipLaunchKernelGGL(k_prep_compact, dim3(g), dim3(256), 0, p->stream, p->deskewed.p, n, p->keep.p, p->off.p, p->cropped.p);
-  PCHK(p, hipGetLastError());
-  p->n_cropped = nc;
-  int rc = downsample(p, p->cropped.p, nc, 0.5 * voxel_size, p->map_cloud, nullptr, &p->n_map);   // :559
-  if (rc) return rc;
-  rc = downsample(p, p->map_cloud.p, p->n_map, 1.5 * voxel_size, p->source, &p->source64, &p->n_source);   // :560
-  if (rc) return rc;
-  if (!(1.5 * voxel_size > 0.0) && p->n_source > 0) {
-    return pfail(p, SVNICP_ERR_INVALID, "svnicp_prep_scan_deskew: voxel_size must be positive");
-  }
-  PCHK(p, hipStreamSynchronize(p->stream));
-  *n_cropped = p->n_cropped; *n_map = p->n_map; *n_source = p->n_source;
-  return SVNICP_OK;
+  return compact_and_sample(p, "svnicp_prep_scan_deskew", p->deskewed.p, n, p->dscal.p, voxel_size, scan_max_range, n_cropped, n_map, n_source);
 }
 
 const float* svnicp_prep_deskewed_devptr(svnicp_prep* p) { return p ? p->deskewed.p : nullptr; }
 
 int svnicp_prep_download_deskewed(svnicp_prep* p, float* out_xyz, int64_t cap_points, int64_t* n_out) {
   if (!p || !n_out) return SVNICP_ERR_INVALID;
-  PCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipSetDevice(p->device));
   *n_out = p->n_deskewed;
   const int64_t n = p->n_deskewed < cap_points ? p->n_deskewed : cap_points;
   if (n > 0 && out_xyz) {
-    PCHK(p, hipMemcpyAsync(out_xyz, p->deskewed.p, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
-    PCHK(p, hipStreamSynchronize(p->stream));
+    HIPCHK(p, hipMemcpyAsync(out_xyz, p->deskewed.p, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipStreamSynchronize(p->stream));
   }
   return SVNICP_OK;
 }
 
 int svnicp_prep_download(svnicp_prep* p, int which, float* out_xyz, int64_t cap_points, int64_t* n_out) {
   if (!p || !n_out || which < 0 || which > 2) return SVNICP_ERR_INVALID;
-  PCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipSetDevice(p->device));
   const int64_t n_all = which == 0 ? p->n_cropped : which == 1 ? p->n_map : p->n_source;
   const float* src = which == 0 ? p->cropped.p : which == 1 ? p->map_cloud.p : p->source.p;
   *n_out = n_all;
   const int64_t n = n_all < cap_points ? n_all : cap_points;
   if (n > 0 && out_xyz) {
-    PCHK(p, hipMemcpyAsync(out_xyz, src, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
-    PCHK(p, hipStreamSynchronize(p->stream));
+    HIPCHK(p, hipMemcpyAsync(out_xyz, src, (size_t)n * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipStreamSynchronize(p->stream));
   }
   return SVNICP_OK;
 }

@@ -23,12 +23,14 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "../../include/svnicp_hip.h"
+#include "device_buffer.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -238,82 +240,54 @@ __global__ __launch_bounds__(256) void k_map_rehash(const unsigned long long* __
   atomicOr(&stats[2], 2);
 }
 
-template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    // grow by half beyond the request: the map gains voxels with every scan, and a hipFree + hipMalloc per call cost more
-    // than the kernels of a query
-    if (cap > 0) n += n / 2;
-    p = nullptr; cap = 0;
-    if (n == 0) n = 1;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 }  // namespace
 
 struct svnicp_map {
   int device = 0;
-  hipStream_t stream = nullptr;
+  svnicp_host::Stream stream;   // before the buffers: destroyed after them
   double voxel = 1.0, max_range = 80.0;
   int max_points = 20;
   int64_t cap = 0;
-  Buf<unsigned long long> keys, sel_key, sel_key2;
-  Buf<int> counts, stats, sidx_in, sidx, sel_cnt, sel_off, nsel;
-  Buf<float> pts, q, in, out_f32;
-  Buf<unsigned int> slot, sslot, sel_slot, sel_slot2;
-  Buf<double> out;
-  Buf<unsigned char> tmp;
+  GrowBuf<unsigned long long> keys, sel_key, sel_key2;
+  GrowBuf<int> counts, stats, sidx_in, sidx, sel_cnt, sel_off, nsel;
+  GrowBuf<float> pts, q, in, out_f32;
+  GrowBuf<unsigned int> slot, sslot, sel_slot, sel_slot2;
+  GrowBuf<double> out;
+  GrowBuf<unsigned char> tmp;
   int64_t last_M = 0;
   int64_t skipped = 0;   // points svnicp_map_add_cloud did not store (outside the index range or NaN), since creation / clear
   int h_stats[4] = {0, 0, 0, 0};
   std::string err;
+  static std::string& create_error() { thread_local std::string s; return s; }   // svnicp_map_last_error(nullptr)
 };
 
 namespace {
-thread_local std::string g_map_error;
-int mfail(svnicp_map* m, int code, const std::string& msg) { if (m) m->err = msg; else g_map_error = msg; return code; }
-#define MCHK(m, expr)                                                                                      \
-  do {                                                                                                     \
-    hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess)                                                                                  \
-      return mfail((m), _e == hipErrorOutOfMemory ? SVNICP_ERR_NOMEM : SVNICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-int alloc_table(svnicp_map* m, int64_t cap, Buf<unsigned long long>& keys, Buf<int>& counts, Buf<float>& pts) {
-  MCHK(m, keys.ensure((size_t)cap));
-  MCHK(m, counts.ensure((size_t)cap));
-  MCHK(m, pts.ensure((size_t)cap * m->max_points * 3));
-  MCHK(m, hipMemsetAsync(keys.p, 0xff, (size_t)cap * 8, m->stream));
-  MCHK(m, hipMemsetAsync(counts.p, 0, (size_t)cap * 4, m->stream));
+int alloc_table(svnicp_map* m, int64_t cap, GrowBuf<unsigned long long>& keys, GrowBuf<int>& counts, GrowBuf<float>& pts) {
+  HIPCHK(m, keys.ensure((size_t)cap));
+  HIPCHK(m, counts.ensure((size_t)cap));
+  HIPCHK(m, pts.ensure((size_t)cap * m->max_points * 3));
+  HIPCHK(m, hipMemsetAsync(keys.p, 0xff, (size_t)cap * 8, m->stream));
+  HIPCHK(m, hipMemsetAsync(counts.p, 0, (size_t)cap * 4, m->stream));
   return 0;
 }
 
 int read_stats(svnicp_map* m) {
-  MCHK(m, hipMemcpyAsync(m->h_stats, m->stats.p, sizeof m->h_stats, hipMemcpyDeviceToHost, m->stream));
-  MCHK(m, hipStreamSynchronize(m->stream));
+  HIPCHK(m, hipMemcpyAsync(m->h_stats, m->stats.p, sizeof m->h_stats, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));
   return 0;
 }
 
 int rebuild(svnicp_map* m, int64_t new_cap) {
-  Buf<unsigned long long> nk; Buf<int> nc; Buf<float> np;
+  GrowBuf<unsigned long long> nk; GrowBuf<int> nc; GrowBuf<float> np;
   int rc = alloc_table(m, new_cap, nk, nc, np);
-  if (rc) { nk.release(); nc.release(); np.release(); return rc; }
+  if (rc) return rc;
   hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, m->stream, m->keys.p, m->counts.p, m->pts.p,
                      m->cap, m->max_points, nk.p, nc.p, np.p, new_cap, m->stats.p);
-  MCHK(m, hipGetLastError());
+  HIPCHK(m, hipGetLastError());
   const int zero = 0;
-  MCHK(m, hipMemcpyAsync(m->stats.p + 1, &zero, sizeof(int), hipMemcpyHostToDevice, m->stream));   // no tombstones left
-  MCHK(m, hipStreamSynchronize(m->stream));
-  m->keys.release(); m->counts.release(); m->pts.release();
-  m->keys = nk; m->counts = nc; m->pts = np;
+  HIPCHK(m, hipMemcpyAsync(m->stats.p + 1, &zero, sizeof(int), hipMemcpyHostToDevice, m->stream));   // no tombstones left
+  HIPCHK(m, hipStreamSynchronize(m->stream));
+  m->keys = std::move(nk); m->counts = std::move(nc); m->pts = std::move(np);
   m->cap = new_cap;
   return 0;
 }
@@ -321,28 +295,28 @@ int rebuild(svnicp_map* m, int64_t new_cap) {
 
 extern "C" {
 
-const char* svnicp_map_last_error(const svnicp_map* m) { return m ? m->err.c_str() : g_map_error.c_str(); }
+const char* svnicp_map_last_error(const svnicp_map* m) { return m ? m->err.c_str() : svnicp_map::create_error().c_str(); }
 
 int svnicp_map_create(int device, double voxel_size, double max_range, int max_points, int64_t capacity_voxels, svnicp_map** out) {
   if (!out || !(voxel_size > 0) || max_points < 1 || max_points > 256)
-    return mfail(nullptr, SVNICP_ERR_INVALID, "svnicp_map_create: need voxel_size > 0 and 1 <= max_points <= 256");
+    return fail<svnicp_map>(nullptr, SVNICP_ERR_INVALID, "svnicp_map_create: need voxel_size > 0 and 1 <= max_points <= 256");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return mfail(nullptr, SVNICP_ERR_NO_DEVICE, "svnicp_map_create: no HIP device visible (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return mfail(nullptr, SVNICP_ERR_INVALID, "svnicp_map_create: bad device ordinal");
-  if (hipSetDevice(device) != hipSuccess) return mfail(nullptr, SVNICP_ERR_HIP, "hipSetDevice failed");
+    return fail<svnicp_map>(nullptr, SVNICP_ERR_NO_DEVICE, "svnicp_map_create: no HIP device visible (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail<svnicp_map>(nullptr, SVNICP_ERR_INVALID, "svnicp_map_create: bad device ordinal");
+  if (hipSetDevice(device) != hipSuccess) return fail<svnicp_map>(nullptr, SVNICP_ERR_HIP, "hipSetDevice failed");
   svnicp_map* m = new svnicp_map();
   m->device = device; m->voxel = voxel_size; m->max_range = max_range; m->max_points = max_points;
   int64_t cap = 1 << 16;
   const int64_t want = capacity_voxels > 0 ? capacity_voxels : (int64_t)1 << 20;
   while (cap < want) cap <<= 1;
   m->cap = cap;
-  if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return mfail(nullptr, SVNICP_ERR_HIP, "hipStreamCreate failed"); }
+  if (m->stream.create(hipStreamNonBlocking) != hipSuccess) { delete m; return fail<svnicp_map>(nullptr, SVNICP_ERR_HIP, "hipStreamCreate failed"); }
   int rc = alloc_table(m, cap, m->keys, m->counts, m->pts);
   if (!rc && (m->stats.ensure(4) != hipSuccess || m->nsel.ensure(1) != hipSuccess)) rc = SVNICP_ERR_NOMEM;
   if (!rc && hipMemsetAsync(m->stats.p, 0, 16, m->stream) != hipSuccess) rc = SVNICP_ERR_HIP;
   if (!rc && hipStreamSynchronize(m->stream) != hipSuccess) rc = SVNICP_ERR_HIP;
-  if (rc) { g_map_error = m->err.empty() ? "svnicp_map_create: allocation failed" : m->err; svnicp_map_destroy(m); return rc; }
+  if (rc) { svnicp_map::create_error() = m->err.empty() ? "svnicp_map_create: allocation failed" : m->err; svnicp_map_destroy(m); return rc; }
   *out = m;
   return SVNICP_OK;
 }
@@ -351,20 +325,16 @@ void svnicp_map_destroy(svnicp_map* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  m->keys.release(); m->sel_key.release(); m->sel_key2.release(); m->counts.release(); m->stats.release(); m->sidx_in.release();
-  m->sidx.release(); m->sel_cnt.release(); m->sel_off.release(); m->nsel.release(); m->pts.release(); m->q.release(); m->in.release();
-  m->out_f32.release(); m->slot.release(); m->sslot.release(); m->sel_slot.release(); m->sel_slot2.release(); m->out.release(); m->tmp.release();
-  if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m;
 }
 
 int svnicp_map_clear(svnicp_map* m) {
   if (!m) return SVNICP_ERR_INVALID;
-  MCHK(m, hipSetDevice(m->device));
-  MCHK(m, hipMemsetAsync(m->keys.p, 0xff, (size_t)m->cap * 8, m->stream));
-  MCHK(m, hipMemsetAsync(m->counts.p, 0, (size_t)m->cap * 4, m->stream));
-  MCHK(m, hipMemsetAsync(m->stats.p, 0, 16, m->stream));
-  MCHK(m, hipStreamSynchronize(m->stream));
+  HIPCHK(m, hipSetDevice(m->device));
+  HIPCHK(m, hipMemsetAsync(m->keys.p, 0xff, (size_t)m->cap * 8, m->stream));
+  HIPCHK(m, hipMemsetAsync(m->counts.p, 0, (size_t)m->cap * 4, m->stream));
+  HIPCHK(m, hipMemsetAsync(m->stats.p, 0, 16, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));
   std::memset(m->h_stats, 0, sizeof m->h_stats);
   m->skipped = 0;
   return SVNICP_OK;
@@ -378,7 +348,7 @@ int svnicp_map_skipped_points(svnicp_map* m, int64_t* out) {
 
 int svnicp_map_size(svnicp_map* m, int64_t* voxels) {
   if (!m || !voxels) return SVNICP_ERR_INVALID;
-  MCHK(m, hipSetDevice(m->device));
+  HIPCHK(m, hipSetDevice(m->device));
   const int rc = read_stats(m);
   if (rc) return rc;
   *voxels = m->h_stats[0];
@@ -386,8 +356,8 @@ int svnicp_map_size(svnicp_map* m, int64_t* voxels) {
 }
 
 int svnicp_map_add_cloud(svnicp_map* m, const float* xyz, int64_t n, int mem_kind, const double R_rowmajor[9], const double t[3]) {
-  if (!m || !R_rowmajor || !t || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL) return mfail(m, SVNICP_ERR_INVALID, "svnicp_map_add_cloud: bad argument");
-  MCHK(m, hipSetDevice(m->device));
+  if (!m || !R_rowmajor || !t || n < 0 || (n > 0 && !xyz) || n > 0x7fffffffLL) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_add_cloud: bad argument");
+  HIPCHK(m, hipSetDevice(m->device));
   if (n > 0) {
     // room for this cloud in the worst case (every point a new voxel): keep the load factor below 1/2, clear tombstones
     int rc = read_stats(m);
@@ -397,51 +367,51 @@ int svnicp_map_add_cloud(svnicp_map* m, const float* xyz, int64_t n, int mem_kin
     if (need != m->cap || (int64_t)m->h_stats[1] * 4 > m->cap) { rc = rebuild(m, need); if (rc) return rc; }
     const float* din = xyz;
     if (mem_kind != SVNICP_MEM_DEVICE) {
-      MCHK(m, m->in.ensure((size_t)n * 3));
-      MCHK(m, hipMemcpyAsync(m->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, m->stream));
+      HIPCHK(m, m->in.ensure((size_t)n * 3));
+      HIPCHK(m, hipMemcpyAsync(m->in.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, m->stream));
       din = m->in.p;
     }
-    MCHK(m, m->q.ensure((size_t)n * 3)); MCHK(m, m->slot.ensure((size_t)n)); MCHK(m, m->sslot.ensure((size_t)n));
-    MCHK(m, m->sidx_in.ensure((size_t)n)); MCHK(m, m->sidx.ensure((size_t)n));
+    HIPCHK(m, m->q.ensure((size_t)n * 3)); HIPCHK(m, m->slot.ensure((size_t)n)); HIPCHK(m, m->sslot.ensure((size_t)n));
+    HIPCHK(m, m->sidx_in.ensure((size_t)n)); HIPCHK(m, m->sidx.ensure((size_t)n));
     MapPose ps;
     for (int i = 0; i < 9; ++i) ps.R[i] = R_rowmajor[i];
     for (int i = 0; i < 3; ++i) ps.t[i] = t[i];
     const unsigned g = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_map_locate, dim3(g), dim3(256), 0, m->stream, din, n, ps, (float)m->voxel, m->keys.p, m->cap, m->q.p, m->slot.p, m->stats.p);
-    MCHK(m, hipGetLastError());
+    HIPCHK(m, hipGetLastError());
     {  // stable sort of (slot, input index): a voxel's new points become a run in input order
       hipLaunchKernelGGL(k_map_iota, dim3(g), dim3(256), 0, m->stream, m->sidx_in.p, n);
-      MCHK(m, hipGetLastError());
+      HIPCHK(m, hipGetLastError());
       size_t bytes = 0;
-      MCHK(m, rocprim::radix_sort_pairs(nullptr, bytes, m->slot.p, m->sslot.p, m->sidx_in.p, m->sidx.p, (size_t)n, 0, 32, m->stream));
-      MCHK(m, m->tmp.ensure(bytes));
-      MCHK(m, rocprim::radix_sort_pairs(m->tmp.p, bytes, m->slot.p, m->sslot.p, m->sidx_in.p, m->sidx.p, (size_t)n, 0, 32, m->stream));
+      HIPCHK(m, rocprim::radix_sort_pairs(nullptr, bytes, m->slot.p, m->sslot.p, m->sidx_in.p, m->sidx.p, (size_t)n, 0, 32, m->stream));
+      HIPCHK(m, m->tmp.ensure(bytes));
+      HIPCHK(m, rocprim::radix_sort_pairs(m->tmp.p, bytes, m->slot.p, m->sslot.p, m->sidx_in.p, m->sidx.p, (size_t)n, 0, 32, m->stream));
     }
     hipLaunchKernelGGL(k_map_place, dim3(g), dim3(256), 0, m->stream, m->sslot.p, m->sidx.p, n, m->counts.p, m->max_points, m->q.p, m->pts.p);
-    MCHK(m, hipGetLastError());
+    HIPCHK(m, hipGetLastError());
     hipLaunchKernelGGL(k_map_count, dim3(g), dim3(256), 0, m->stream, m->sslot.p, n, m->counts.p, m->max_points, m->stats.p);
-    MCHK(m, hipGetLastError());
+    HIPCHK(m, hipGetLastError());
   }
   hipLaunchKernelGGL(k_map_remove_far, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, m->stream, m->keys.p, m->counts.p, m->pts.p,
                      m->cap, m->max_points, t[0], t[1], t[2], m->max_range * m->max_range, m->stats.p);
-  MCHK(m, hipGetLastError());
+  HIPCHK(m, hipGetLastError());
   const int rc = read_stats(m);
   if (rc) return rc;
   if (m->h_stats[2] || m->h_stats[3]) {
     const int flags = m->h_stats[2], zero2[2] = {0, 0};
     m->skipped += m->h_stats[3];    // points outside +-2^20 voxels or NaN: not stored, not an error — the map and its
                                     // counters are consistent, the caller's drive goes on (svnicp_map_skipped_points)
-    MCHK(m, hipMemcpyAsync(m->stats.p + 2, zero2, sizeof zero2, hipMemcpyHostToDevice, m->stream));
-    MCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpyAsync(m->stats.p + 2, zero2, sizeof zero2, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
     // cannot happen: the table is grown to twice the voxels this cloud could add before anything is inserted
-    if (flags & 2) return mfail(m, SVNICP_ERR_NOMEM, "svnicp_map_add_cloud: hash table full");
+    if (flags & 2) return fail(m, SVNICP_ERR_NOMEM, "svnicp_map_add_cloud: hash table full");
   }
   return SVNICP_OK;
 }
 
 int svnicp_map_query(svnicp_map* m, const double center[3], double max_range, int64_t* count_out) {
   if (!m || !count_out) return SVNICP_ERR_INVALID;
-  MCHK(m, hipSetDevice(m->device));
+  HIPCHK(m, hipSetDevice(m->device));
   const double r2 = (center && max_range >= 0.0) ? max_range * max_range : -1.0;
   const double c0 = center ? center[0] : 0.0, c1 = center ? center[1] : 0.0, c2 = center ? center[2] : 0.0;
   // Everything is sized by the number of live voxels the host already knows (every call that changes the map ends by
@@ -450,32 +420,32 @@ int svnicp_map_query(svnicp_map* m, const double center[3], double max_range, in
   const size_t live = (size_t)(m->h_stats[0] > 0 ? m->h_stats[0] : 0);
   *count_out = 0; m->last_M = 0;
   if (live == 0) return SVNICP_OK;
-  MCHK(m, m->sel_key.ensure(live)); MCHK(m, m->sel_key2.ensure(live)); MCHK(m, m->sel_slot.ensure(live)); MCHK(m, m->sel_slot2.ensure(live));
-  MCHK(m, m->sel_cnt.ensure(live)); MCHK(m, m->sel_off.ensure(live));
-  MCHK(m, m->out.ensure(live * (size_t)m->max_points * 3));
+  HIPCHK(m, m->sel_key.ensure(live)); HIPCHK(m, m->sel_key2.ensure(live)); HIPCHK(m, m->sel_slot.ensure(live)); HIPCHK(m, m->sel_slot2.ensure(live));
+  HIPCHK(m, m->sel_cnt.ensure(live)); HIPCHK(m, m->sel_off.ensure(live));
+  HIPCHK(m, m->out.ensure(live * (size_t)m->max_points * 3));
   size_t b1 = 0, b2 = 0;
-  MCHK(m, rocprim::radix_sort_pairs(nullptr, b1, m->sel_key.p, m->sel_key2.p, m->sel_slot.p, m->sel_slot2.p, live, 0, 64, m->stream));
-  MCHK(m, rocprim::exclusive_scan(nullptr, b2, m->sel_cnt.p, m->sel_off.p, 0, live, rocprim::plus<int>(), m->stream));
-  MCHK(m, m->tmp.ensure(b1 > b2 ? b1 : b2));
-  MCHK(m, hipMemsetAsync(m->nsel.p, 0, sizeof(int), m->stream));
-  MCHK(m, hipMemsetAsync(m->sel_key.p, 0xff, live * sizeof(unsigned long long), m->stream));
-  MCHK(m, hipMemsetAsync(m->sel_slot.p, 0, live * sizeof(unsigned int), m->stream));
+  HIPCHK(m, rocprim::radix_sort_pairs(nullptr, b1, m->sel_key.p, m->sel_key2.p, m->sel_slot.p, m->sel_slot2.p, live, 0, 64, m->stream));
+  HIPCHK(m, rocprim::exclusive_scan(nullptr, b2, m->sel_cnt.p, m->sel_off.p, 0, live, rocprim::plus<int>(), m->stream));
+  HIPCHK(m, m->tmp.ensure(b1 > b2 ? b1 : b2));
+  HIPCHK(m, hipMemsetAsync(m->nsel.p, 0, sizeof(int), m->stream));
+  HIPCHK(m, hipMemsetAsync(m->sel_key.p, 0xff, live * sizeof(unsigned long long), m->stream));
+  HIPCHK(m, hipMemsetAsync(m->sel_slot.p, 0, live * sizeof(unsigned int), m->stream));
   hipLaunchKernelGGL(k_map_select, dim3((unsigned)((m->cap + kSelChunk * 256 - 1) / (kSelChunk * 256))), dim3(256), 0, m->stream, m->keys.p, m->counts.p, m->pts.p, m->cap,
                      m->max_points, c0, c1, c2, r2, m->sel_key.p, m->sel_slot.p, m->nsel.p, (int)live);
-  MCHK(m, hipGetLastError());
-  MCHK(m, rocprim::radix_sort_pairs(m->tmp.p, b1, m->sel_key.p, m->sel_key2.p, m->sel_slot.p, m->sel_slot2.p, live, 0, 64, m->stream));
+  HIPCHK(m, hipGetLastError());
+  HIPCHK(m, rocprim::radix_sort_pairs(m->tmp.p, b1, m->sel_key.p, m->sel_key2.p, m->sel_slot.p, m->sel_slot2.p, live, 0, 64, m->stream));
   const int nl = (int)live;
   hipLaunchKernelGGL(k_map_sel_counts, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, m->stream, m->sel_key2.p, m->sel_slot2.p, nl, m->counts.p, m->sel_cnt.p);
-  MCHK(m, hipGetLastError());
-  MCHK(m, rocprim::exclusive_scan(m->tmp.p, b2, m->sel_cnt.p, m->sel_off.p, 0, live, rocprim::plus<int>(), m->stream));
+  HIPCHK(m, hipGetLastError());
+  HIPCHK(m, rocprim::exclusive_scan(m->tmp.p, b2, m->sel_cnt.p, m->sel_off.p, 0, live, rocprim::plus<int>(), m->stream));
   const int64_t work = (int64_t)live * m->max_points;
   hipLaunchKernelGGL(k_map_gather, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, m->stream, m->sel_slot2.p, m->sel_off.p, m->sel_cnt.p, nl,
                      m->max_points, m->pts.p, m->out.p, (float*)nullptr);
-  MCHK(m, hipGetLastError());
+  HIPCHK(m, hipGetLastError());
   int last[2] = {0, 0};
-  MCHK(m, hipMemcpyAsync(&last[0], m->sel_off.p + (live - 1), sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  MCHK(m, hipMemcpyAsync(&last[1], m->sel_cnt.p + (live - 1), sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  MCHK(m, hipStreamSynchronize(m->stream));   // the rows are complete when the call returns (another stream may read them)
+  HIPCHK(m, hipMemcpyAsync(&last[0], m->sel_off.p + (live - 1), sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(m, hipMemcpyAsync(&last[1], m->sel_cnt.p + (live - 1), sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));   // the rows are complete when the call returns (another stream may read them)
   const int64_t M = (int64_t)last[0] + last[1];
   m->last_M = M;
   *count_out = M;
@@ -486,12 +456,12 @@ void* svnicp_map_points_devptr(svnicp_map* m) { return m ? (void*)m->out.p : nul
 
 int svnicp_map_download(svnicp_map* m, double* out_xyz, int64_t cap_points, int64_t* n_out) {
   if (!m || !n_out) return SVNICP_ERR_INVALID;
-  MCHK(m, hipSetDevice(m->device));
+  HIPCHK(m, hipSetDevice(m->device));
   *n_out = m->last_M;
   const int64_t n = m->last_M < cap_points ? m->last_M : cap_points;
   if (n > 0 && out_xyz) {
-    MCHK(m, hipMemcpyAsync(out_xyz, m->out.p, (size_t)n * 24, hipMemcpyDeviceToHost, m->stream));
-    MCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpyAsync(out_xyz, m->out.p, (size_t)n * 24, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
   }
   return SVNICP_OK;
 }
