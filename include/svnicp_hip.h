@@ -168,6 +168,36 @@ int svnicp_get_minibatch_indices(svnicp_ctx *ctx, int32_t *outIxb);      /* the 
 int svnicp_get_minibatch_candidates(svnicp_ctx *ctx, int32_t *outIxbxK); /* candidate target indices per drawn position */
 int svnicp_get_minibatch_rows(svnicp_ctx *ctx, int64_t out2[2]);         /* {unique rows drawn U, queries stage A ran} */
 
+/* ---- point-to-plane residual (an extension: the reference computes point-to-point only) ----------
+ * svnicp_set_residual(SVNICP_RESIDUAL_PLANE, huber_delta, normal_k): from the next registration on, SVN mode minimises
+ * sum rho(r) over the accepted pairs with r = n . (T s - q), q the winner of the unchanged nearest-of-K search, n its unit
+ * normal and rho the Huber function: weight w = 1 for |r| <= huber_delta, huber_delta / |r| beyond (huber_delta > 0; +inf =
+ * unweighted).  A pair is accepted iff its squared distance is below max_dist (the gate of point mode, quirk included) and
+ * q has a normal; a rejected pair contributes nothing.  Per particle, with Rt | tt its total pose, m = Rt^T n, j = [m ; s x m]:
+ * H = sum w j j^T + 1e-6 I, b = sum w r j; the Stein step, early stop, history, outputs and trace taps are unchanged.
+ * Normals: those of svnicp_set_target_normals, else estimated on the device when the registration begins — per target point
+ * from its normal_k nearest target points, itself included (4..64; 0 = 16; stage A's exact search with the target as the
+ * query cloud): covariance of the offsets, eigenvector of the smallest eigenvalue, sign unspecified (the residual does not
+ * depend on it).  A point has NO normal when a neighbour is non-finite, when the largest eigenvalue l2 is 0 or when the
+ * middle one l1 < 0.01 * l2 (collinear neighbourhoods: the same-ring neighbours of a sparse scan).  Estimated normals are
+ * kept until the target or normal_k changes: a second registration against the same target pays nothing.
+ * SVNICP_RESIDUAL_POINT (the default) runs exactly the launches of a context that never called this.
+ * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID in plane mode: SVGD mode, a partial particle shard, a
+ * source-row shard, mini-batch mode, the options correspondence=full, chain=persistent and accum=f64|valu, knn_count > 128,
+ * and a target of fewer than normal_k points without supplied normals. */
+#define SVNICP_RESIDUAL_POINT 0   /* today's behaviour, the default */
+#define SVNICP_RESIDUAL_PLANE 1
+int svnicp_set_residual(svnicp_ctx *ctx, int residual, double huber_delta, int normal_k);
+/* optional: normals of the current target, double [M][3], host or device (copied).  Must follow the svnicp_set_target /
+ * svnicp_set_clouds it belongs to, with the same M; rows are normalised on upload, a zero or non-finite row means "no normal
+ * here"; a later svnicp_set_target drops them. */
+int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, int mem_kind);
+/* taps: the supplied or estimated unit normals, rows without a normal are 0 (SVNICP_ERR_INVALID before there are any);
+ * per particle {accepted pairs, sum w r^2} of the last iteration run, and the count of normal passes run so far
+ * (either pointer may be NULL; outPx2 needs a finished registration in plane mode) */
+int svnicp_get_target_normals(svnicp_ctx *ctx, double *outMx3);
+int svnicp_get_plane_stats(svnicp_ctx *ctx, double *outPx2, int64_t *normal_passes);
+
 /* ---- split-phase entry points: one process per GPU, particles sharded across ranks ----------
  * (new functionality; the reference is single-GPU).  Sequence per registration:
  *   svnicp_set_shard -> svnicp_stage_candidates(b_lo,b_hi) -> [host all-gathers rows of
@@ -259,7 +289,8 @@ int svnicp_get_ambiguous_pairs(svnicp_ctx *ctx, int64_t *out);
  * per kernel class of the LAST align, SVNICP_KERNEL_CLASSES entries in this order:
  *   0 stage A (ordering + k_knn_tiles/k_knn_scan + fallback)   1 k_build_table*
  *   2 k_stein_search_bf16 (split stage B only)                 3 k_stein_accumulate* (fused variants: whole stage B)
- *   4 k_reduce_partials                                        5 k_particle_update / k_upd_* */
+ *   4 k_reduce_partials                                        5 k_particle_update / k_upd_*
+ * (plane residual: 3 = k_plane_accumulate, 4 = k_plane_finalize) */
 #define SVNICP_KERNEL_CLASSES 6
 /* on: 0 = off, 1 = every class, otherwise a mask with bit (class + 1) set for each class to bracket (the event
  * pairs cost ~5 us of stream time each, so a timed run brackets only what it reports) */

@@ -139,6 +139,23 @@ struct MiniBatch {
   DevBuf<double> src_u, src;
 };
 
+// point-to-plane residual (svnicp_set_residual; csrc/plane_icp.hip).  residual 0 = the reference's point-to-point
+struct PlaneState {
+  int residual = SVNICP_RESIDUAL_POINT;
+  double delta = 0.1;
+  int normal_k = 16;
+  bool supplied = false;      // rec holds normals the caller gave for the current target (dropped by svnicp_set_target)
+  bool estimated = false;     // rec holds normals estimated from the current target with est_k neighbours
+  int est_k = 0;
+  int64_t passes = 0;         // normal passes run since creation
+  bool on = false;            // the registration begun last runs the plane residual
+  DevBuf<double> rec;         // [M][6] xyz | unit normal, 0 = no normal here
+  DevBuf<double> nsup;        // upload staging of supplied normals
+  DevBuf<int32_t> nbr;        // [rows of one pass block][normal_k] neighbour indices
+  DevBuf<double> nbr_d2;
+  DevBuf<double> partial, Hb, stats;   // [grid_x][Ppad][kPlaneSums], [P][42], [P][2]
+};
+
 struct Trace { DevBuf<double> H, b, N, phi, h; DevBuf<int32_t> corr; };   // record_trace
 
 struct Profiling {   // timing events
@@ -176,7 +193,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb;
+  Sharding shard; MiniBatch mb; PlaneState pl;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -231,7 +248,7 @@ static void choose_step_chain(svnicp_ctx* c) {
   else if (P <= kMedianInlineMaxP && P <= t.fused_update_max_p && t.median_inline != 0) c->st.chain = StepChain::InlineMedian;
   else c->st.chain = StepChain::SideStream;
   c->st.single_fused = P == 1 && c->prm.mode == SVNICP_MODE_SVN && c->shard.row_world == 1 && c->shard.p_lo == 0 && c->shard.p_hi == 1 &&
-                       !t.full_corr && t.single_fused && accumulate_can_fuse_single(pl);
+                       !t.full_corr && t.single_fused && accumulate_can_fuse_single(pl) && !c->pl.on;
 }
 
 extern "C" {
@@ -356,6 +373,7 @@ int svnicp_set_target(svnicp_ctx* c, const double* tgt, int64_t M, int mem_kind)
   c->M = M; c->Mp = knn_padded_targets(M);
   c->cloud.target_layout = -1;  // the SoA copies are (re)built in svnicp_align_begin, once K is final
   c->cloud.tgt_set = true;
+  c->pl.supplied = false; c->pl.estimated = false;   // normals belong to the target they were given or estimated for
   return SVNICP_OK;
 }
 
@@ -532,6 +550,7 @@ static int ensure_target_layout(svnicp_ctx* c) {
   return 0;
 }
 
+static int prepare_plane(svnicp_ctx* c);
 int svnicp_align_begin(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (!c->cloud.src_set || !c->cloud.tgt_set || !c->run.particles_set)
@@ -559,6 +578,22 @@ int svnicp_align_begin(svnicp_ctx* c) {
     }
     mb = I > 0;
   }
+  // point-to-plane residual: what it is not combined with (all left for later)
+  const bool plane = c->pl.residual == SVNICP_RESIDUAL_PLANE;
+  if (plane) {
+    const char* why = nullptr;
+    if (c->prm.mode == SVNICP_MODE_SVGD) why = "SVGD mode has no Hessian to put the plane residual in";
+    else if (c->shard.set && (c->shard.p_lo != 0 || c->shard.p_hi != P)) why = "a partial particle shard (svnicp_set_shard) is set";
+    else if (c->shard.row_world > 1) why = "a source-row shard (svnicp_set_row_shard) is set: the rank exchange carries the 22 point-to-point sums";
+    else if (c->mb.batch != 0) why = "mini-batch mode (svnicp_set_minibatch) is set";
+    else if (c->tune.full_corr) why = "option correspondence=full is set";
+    else if (c->tune.persistent) why = "option chain=persistent is set";
+    else if (c->tune.accum != 3) why = "option accum is not split: the plane kernel consumes the search kernel's winner index";
+    else if (c->K > 128) why = "knn_count exceeds 128: the plane kernel consumes the matrix-pipe search kernel's winner index";
+    else if (!c->pl.supplied && c->M < c->pl.normal_k) why = "the target has fewer points than normal_k and no normals were supplied";
+    if (why) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ") + why);
+  }
+  c->pl.on = plane;
   c->mb.on = mb; c->mb.have = false; c->mb.check = false;
   c->mb.rows = mb ? (int64_t)I * c->mb.batch : 0;
   c->mb.nq = mb ? std::min<int64_t>(B, c->mb.rows) : 0;
@@ -617,7 +652,8 @@ int svnicp_align_begin(svnicp_ctx* c) {
     // small chain (few pairs, one context holds everything, 2 <= P <= 128): decided here, carried by the plan
     Tuning tn = c->tune;
     tn.small_chain = tn.small_chain && P >= 2 && P <= 128 && P <= tn.fused_update_max_p && !tn.update_fused && c->shard.row_world == 1 &&
-                     c->shard.p_lo == 0 && c->shard.p_hi == P && !tn.full_corr;
+                     c->shard.p_lo == 0 && c->shard.p_hi == P && !tn.full_corr && !plane;
+    tn.force_split = plane ? 1 : 0;   // plane mode: the split kernels for any particle count, and never the small chain
     c->sb.plan = plan_accumulate(nshard, Bi, c->K, c->num_cus, c->sb.accum_mode, tn);
     if (c->tune.debug)
       fprintf(stderr, "[svnicp] stage-B plan: mode=%d PW=%d WP=%d TP=%d grid=%dx%d tiles/block=%d smem=%zu sgrid=%d pts/block=%d/%d\n", c->sb.plan.f32,
@@ -680,6 +716,8 @@ int svnicp_align_begin(svnicp_ctx* c) {
     c->mb.base = minibatch_stream_base(c->mb.seed, c->mb.n);
     c->mb.n += 1;
   }
+  if (plane)
+    if (const int rc = prepare_plane(c)) return rc;
   choose_step_chain(c);
   c->run.began = true;
   c->st.finish_seen = false;
@@ -834,6 +872,41 @@ static int stage_a(svnicp_ctx* c, const double* qsrc, const Pose0& pose, int K, 
   return SVNICP_OK;
 }
 
+// plane mode, end of svnicp_align_begin: the per-registration buffers, and the target's normals when none were supplied and
+// the ones at hand were not estimated from this target with this normal_k.  The neighbours come from stage A itself (target
+// as the query cloud, identity pose, K = normal_k) in blocks of the rows its scratch is sized for.
+static int prepare_plane(svnicp_ctx* c) {
+  if (c->sb.plan.f32 != 3)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the point-to-plane residual needs the split stage B (option accum=split, knn_count <= 128)");
+  HIPCHK(c, c->pl.partial.ensure((size_t)c->sb.plan.grid_x * c->sb.plan.Ppad * kPlaneSums));
+  HIPCHK(c, c->pl.Hb.ensure((size_t)c->P * 42));
+  HIPCHK(c, c->pl.stats.ensure((size_t)c->P * 2));
+  HIPCHK(c, hipMemsetAsync(c->pl.stats.p, 0, (size_t)c->P * 2 * sizeof(double), c->stream));
+  const int kn = c->pl.normal_k;
+  if (c->pl.supplied || (c->pl.estimated && c->pl.est_k == kn)) return SVNICP_OK;
+  if (c->sa.knn_variant == 1)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the seeded-scan stage A (option knn=v2, or a target beyond the tile kernel's range) cannot "
+                                       "search with normal_k neighbours: supply the normals (svnicp_set_target_normals)");
+  const int64_t M = c->M, rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.qrows, M));
+  HIPCHK(c, c->pl.rec.ensure((size_t)M * 6));
+  HIPCHK(c, c->pl.nbr.ensure((size_t)rows * kn));
+  HIPCHK(c, c->pl.nbr_d2.ensure((size_t)rows * kn));
+  if (c->sa.knn_variant != 3 && c->sa.knn_variant != 0 && c->sa.sliced_max > 0) {   // the sliced fallback's lists are sized by K
+    HIPCHK(c, c->sa.sl_d.ensure((size_t)c->sa.sliced_max * knn_slice_count(kn) * kn));
+    HIPCHK(c, c->sa.sl_i.ensure((size_t)c->sa.sliced_max * knn_slice_count(kn) * kn));
+  }
+  Pose0 ident{};
+  ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
+  for (int64_t lo = 0; lo < M; lo += rows) {
+    const int64_t n = std::min<int64_t>(rows, M - lo);
+    if (const int rc = stage_a(c, c->cloud.tgt.p + 3 * lo, ident, kn, c->pl.nbr.p, c->pl.nbr_d2.p, 0, n)) return rc;
+    HIPCHK(c, launch_target_normals(c->cloud.tgt.p, M, c->pl.nbr.p, lo, n, kn, c->pl.rec.p, c->stream));
+  }
+  c->pl.estimated = true; c->pl.est_k = kn;
+  c->pl.passes += 1;
+  return SVNICP_OK;
+}
+
 int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
   CTX_CHECK(c);
   if (!c->run.began) return fail(c, SVNICP_ERR_INVALID, "svnicp_stage_candidates: call svnicp_align_begin first");
@@ -906,6 +979,7 @@ static UpdateArgs update_args(svnicp_ctx* c, int it) {
   u.uctl = c->st.uctl.p;
   u.dbg = c->tune.debug ? c->dbg.upd.p : nullptr;
   u.svgd = c->prm.mode == SVNICP_MODE_SVGD ? 1 : 0;
+  u.plane_Hb = c->pl.on ? c->pl.Hb.p : nullptr;
   return u;
 }
 // argument block of the stage-B kernels for iteration `it` (full_idx: set by the correspondence = full search)
@@ -984,6 +1058,20 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
     HIPCHK(c, prof_begin(c, KC_SEARCH));
     HIPCHK(c, launch_search_split(c->sb.plan, a, c->stream));
     HIPCHK(c, prof_end(c));
+  }
+  if (c->pl.on) {   // point-to-plane: the winner's record, Huber weight, H and b directly ([P][42] for the Stein step)
+    PlaneArgs pa{};
+    pa.src = c->cloud.src.p; pa.rec = c->pl.rec.p; pa.Rtot = c->st.Rtot.p; pa.B = c->B; pa.M = c->M; pa.p_lo = c->shard.p_lo; pa.p_hi = c->shard.p_hi;
+    pa.max_dist = c->prm.max_dist; pa.delta = c->pl.delta; pa.partial = c->pl.partial.p; pa.ctl = c->st.ctl.p;
+    pa.kidx = c->sb.kidx.p; pa.kbest = c->sb.kbest.p; pa.corr = a.corr;
+    HIPCHK(c, prof_begin(c, KC_ACCUM));
+    HIPCHK(c, launch_plane_accumulate(c->sb.plan, pa, c->stream));
+    HIPCHK(c, prof_end(c));
+    HIPCHK(c, prof_begin(c, KC_REDUCE));
+    HIPCHK(c, launch_plane_finalize(c->pl.partial.p, c->sb.plan.grid_x, c->sb.plan.Ppad, c->shard.p_lo, nshard, c->pl.Hb.p, c->pl.stats.p,
+                                    c->st.ctl.p, c->stream));
+    HIPCHK(c, prof_end(c));
+    return SVNICP_OK;
   }
   const bool single = c->st.single_fused;   // the iteration is this one launch
   const UpdateArgs us = update_args(c, it);
@@ -1366,6 +1454,51 @@ int svnicp_get_minibatch_rows(svnicp_ctx* c, int64_t out2[2]) {
   if (rc) return rc;
   out2[0] = w[1]; out2[1] = c->mb.nq;
   return SVNICP_OK;
+}
+
+// ---- point-to-plane residual ----
+int svnicp_set_residual(svnicp_ctx* c, int residual, double huber_delta, int normal_k) {
+  CTX_CHECK(c);
+  if (residual != SVNICP_RESIDUAL_POINT && residual != SVNICP_RESIDUAL_PLANE) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual: unknown residual");
+  if (!(huber_delta > 0.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual: huber_delta must be positive (+inf: no down-weighting)");
+  if (normal_k != 0 && (normal_k < 4 || normal_k > 64)) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual: normal_k must be 0 (= 16) or in 4..64");
+  c->pl.residual = residual; c->pl.delta = huber_delta; c->pl.normal_k = normal_k ? normal_k : 16;
+  c->run.have_candidates = false;   // the stage-B plan follows the residual: svnicp_iter_accumulate refuses until the next svnicp_align_begin
+  return SVNICP_OK;
+}
+
+int svnicp_set_target_normals(svnicp_ctx* c, const double* n_xyz, int64_t M, int mem_kind) {
+  CTX_CHECK(c);
+  if (!n_xyz) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target_normals: null argument");
+  if (!c->cloud.tgt_set || M != c->M)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target_normals: must follow the svnicp_set_target it belongs to, with the same point count");
+  if (bind(c)) return SVNICP_ERR_HIP;
+  HIPCHK(c, c->pl.nsup.ensure((size_t)M * 3));
+  HIPCHK(c, c->pl.rec.ensure((size_t)M * 6));
+  HIPCHK(c, hipMemcpyAsync(c->pl.nsup.p, n_xyz, (size_t)M * 24, mem_kind == SVNICP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_pack_normals(c->cloud.tgt.p, c->pl.nsup.p, M, c->pl.rec.p, c->stream));
+  if (mem_kind != SVNICP_MEM_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may reuse its host buffer
+  c->pl.supplied = true; c->pl.estimated = false;
+  return SVNICP_OK;
+}
+
+int svnicp_get_target_normals(svnicp_ctx* c, double* outMx3) {
+  CTX_CHECK(c);
+  if (!outMx3) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_target_normals: null argument");
+  if (!c->pl.supplied && !c->pl.estimated) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_target_normals: no normals supplied or estimated for this target yet");
+  std::vector<double> rec((size_t)c->M * 6);
+  if (const int rc = fetch(c, rec.data(), c->pl.rec.p, rec.size() * 8)) return rc;
+  for (int64_t i = 0; i < c->M; ++i)
+    for (int d = 0; d < 3; ++d) outMx3[3 * i + d] = rec[6 * i + 3 + d];
+  return SVNICP_OK;
+}
+
+int svnicp_get_plane_stats(svnicp_ctx* c, double* outPx2, int64_t* normal_passes) {
+  CTX_CHECK(c);
+  if (normal_passes) *normal_passes = c->pl.passes;
+  if (!outPx2) return SVNICP_OK;
+  if (!c->run.have_result || !c->pl.on) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_plane_stats: no registration with the point-to-plane residual yet");
+  return fetch(c, outPx2, c->pl.stats.p, (size_t)c->P * 16);
 }
 
 int svnicp_get_trace(svnicp_ctx* c, int32_t* corr, double* H, double* b, double* N, double* phi, double* h) {

@@ -186,6 +186,8 @@ struct Tuning {
   int median_inline = -1;        // pair statistics in the prepare kernel's launch on the main stream also in the general chain: -1 automatic (P <= 128), 0 never (second stream), 1 the same as automatic
   int brute_qb = 0;              // brute-force stage A: queries per workgroup, 0 automatic (knn_brute_queries_per_block)
   int full_corr = 0;             // 1: correspondence = full — per-particle exact NN over the whole target (SVGDICP.cpp:274-298)
+  int force_split = 0;           // plan only (never an option): the split stage B for any particle count — the point-to-plane
+                                 // accumulate kernel consumes the search kernel's winner index (api.hip, plane mode)
 };
 AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f32, const Tuning& tune);
 hipError_t launch_search_split(const AccumPlan& plan, AccumArgs a, hipStream_t st);         // split variant, kernel 1
@@ -225,6 +227,8 @@ struct UpdateArgs {
   double n_src;        // gradient_scaling_factor_ = B (SVGDICP.cpp:58)
   double* uctl;        // multi-workgroup update path: small control / norm area
   unsigned long long* dbg;  // optional [8]: cycle stamps of the fused kernel's phases (SVNICP_DEBUG)
+  const double* plane_Hb;   // point-to-plane mode: [P][42] = H | b as k_plane_finalize left them — the kernels then skip load_sums +
+                            // finalize_Hb (wave-uniform; nullptr in point mode)
 };
 size_t update_workspace_doubles(int P);
 // areas k_init_particles clears at the start of a registration (whole 32-bit words), and the control words it resets
@@ -251,6 +255,31 @@ const double* update_step_norms(const UpdateArgs& a);   // [P] norms the early-s
 hipError_t launch_reduce_partials(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* sums, const int* ctl,
                                   hipStream_t st);
 size_t update_uctl_doubles(int P);
+// ---------------- point-to-plane residual (plane_icp.hip) ----------------
+constexpr int kPlaneSums = 29;             // per (workgroup, particle): H upper triangle (21) | b (6) | accepted pairs | Σ w·r²
+constexpr double kPlaneMinRatio = 0.01;    // a normal is valid iff λ1 >= kPlaneMinRatio · λ2 (collinear neighbourhoods have none)
+struct PlaneArgs {
+  const double* src;    // [B][3]
+  const double* rec;    // [M][6] target xyz | unit normal (0 = no normal here)
+  const double* Rtot;   // [P][12]
+  int64_t B, M;
+  int p_lo, p_hi;
+  int Ppad;             // set by the launcher from the plan, like pts_per_block
+  int pts_per_block;
+  double max_dist, delta;
+  double* partial;      // [plan.grid_x][Ppad][kPlaneSums]
+  const int* ctl;       // ctl[0] = stop flag
+  const int32_t* kidx;  // [B][Ppad] the search kernel's winner (target index)
+  const uint8_t* kbest; // [B][Ppad] … and its slot among the K candidates (read for the trace only)
+  int32_t* corr;        // optional trace [P][B] (this iteration), or nullptr
+};
+// normals of target rows [row_lo, row_lo + rows) from their kn nearest target points nbr [rows][kn] into rec [M][6]
+hipError_t launch_target_normals(const double* tgt, int64_t M, const int32_t* nbr, int64_t row_lo, int64_t rows, int kn, double* rec,
+                                 hipStream_t st);
+hipError_t launch_pack_normals(const double* tgt, const double* nrm, int64_t M, double* rec, hipStream_t st);
+hipError_t launch_plane_accumulate(const AccumPlan& plan, PlaneArgs a, hipStream_t st);
+hipError_t launch_plane_finalize(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* Hb, double* stats,
+                                 const int* ctl, hipStream_t st);
 // ---------------- mini-batch tables (minibatch.hip) ----------------
 struct MinibatchArgs {
   const int32_t* explicit_idx;  // [n] a caller's table (validated by the draw kernel), or nullptr: generated from `base`

@@ -181,7 +181,8 @@ __global__ __launch_bounds__(UT) void k_particle_update(UpdateArgs a) {
     double Rc[9], H[36], b[6], LU[36], x6[6];
     int piv[6];
     mat3_mul(a.pose.R0, a.R + 9 * p, Rc);
-    { double sm[kNSums]; load_sums(a, p, sm); finalize_Hb(sm, Rc, H, b); }
+    if (a.plane_Hb) load_plane_Hb(a.plane_Hb + (size_t)p * 42, H, b);   // wave-uniform; never taken in point mode
+    else { double sm[kNSums]; load_sums(a, p, sm); finalize_Hb(sm, Rc, H, b); }
 #pragma unroll
     for (int i = 0; i < 36; ++i) { LU[i] = H[i]; if (lH) lH[p * 36 + i] = H[i]; }
     if (!lH || a.trH) {
@@ -463,12 +464,16 @@ __device__ __forceinline__ void prepare_body(const UpdateArgs& a, int bx) {
     double Rc[9], H[36], b[6], LU[36], x6[6], sm[kNSums];
     int piv[6];
     mat3_mul(a.pose.R0, a.R + 9 * p, Rc);
-    load_sums(a, p, sm);
-    if (a.sums_out) {   // small chain: the reduced record, where k_reduce_partials would have left it (svnicp_sums_devptr)
+    if (a.plane_Hb) {   // point-to-plane mode (wave-uniform; never taken in point mode)
+      load_plane_Hb(a.plane_Hb + (size_t)p * 42, H, b);
+    } else {
+      load_sums(a, p, sm);
+      if (a.sums_out) {   // small chain: the reduced record, where k_reduce_partials would have left it (svnicp_sums_devptr)
 #pragma unroll
-      for (int i = 0; i < kNSums; ++i) a.sums_out[(size_t)p * kNSums + i] = sm[i];
+        for (int i = 0; i < kNSums; ++i) a.sums_out[(size_t)p * kNSums + i] = sm[i];
+      }
+      finalize_Hb(sm, Rc, H, b);
     }
-    finalize_Hb(sm, Rc, H, b);
 #pragma unroll
     for (int i = 0; i < 36; ++i) { w.H[(size_t)p * 36 + i] = H[i]; LU[i] = H[i]; }
     const bool ok = lu6(LU, piv);
@@ -486,8 +491,8 @@ __device__ __forceinline__ void prepare_body(const UpdateArgs& a, int bx) {
     if (tid < PREP_CH && p < P) {
       double Rc[9], H[36], b[6], sm[kNSums];
       mat3_mul(a.pose.R0, a.R + 9 * p, Rc);
-      load_sums(a, p, sm);
-      finalize_Hb(sm, Rc, H, b);
+      if (a.plane_Hb) load_plane_Hb(a.plane_Hb + (size_t)p * 42, H, b);
+      else { load_sums(a, p, sm); finalize_Hb(sm, Rc, H, b); }
 #pragma unroll
       for (int i = 0; i < 36; ++i) sh.H[tid][i] = H[i];
     }

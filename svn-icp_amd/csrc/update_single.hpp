@@ -42,6 +42,13 @@ __device__ inline void finalize_Hb(const double* s, const double* Rc, double* H,
   b[5] = G[3] - G[1];
 }
 
+// point-to-plane mode: H and b come finished from k_plane_finalize (UpdateArgs::plane_Hb)
+__device__ __forceinline__ void load_plane_Hb(const double* rec, double* H, double* b) {
+#pragma unroll
+  for (int i = 0; i < 36; ++i) H[i] = rec[i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) b[i] = rec[36 + i];
+}
 
 // P = 1 (SVNICP.cpp:81-89: no kernel, no repulsion — the Stein direction is the Newton step itself, phi = −H⁻¹b): finalise
 // H, b, solve, update the pose (SVNICP.cpp:268-279), early-stop test, history and traces — the body of k_particle_update
@@ -50,7 +57,8 @@ __device__ inline void update_single_particle(const UpdateArgs& a, const double*
   double Rc[9], H[36], b[6], LU[36], x6[6], phi[6];
   int piv[6];
   mat3_mul(a.pose.R0, a.R, Rc);
-  finalize_Hb(s, Rc, H, b);
+  if (a.plane_Hb) load_plane_Hb(a.plane_Hb, H, b);
+  else finalize_Hb(s, Rc, H, b);
 #pragma unroll
   for (int i = 0; i < 36; ++i) LU[i] = H[i];
   const bool ok = lu6(LU, piv);

@@ -30,6 +30,9 @@ struct SteinICPParam {  // SVGDICP.h:41-57 (same names and defaults; solver-rele
   double convergence_threshold = 1e-5;
   int KNN_count = 100;
   bool SVN_full_grad = true;
+  std::string residual = "point";   // "point" (the reference) | "plane": Huber-weighted point-to-plane (svnicp_hip.h, not in the reference)
+  double huber_delta = 0.1;         // plane residual: weight 1 up to this |r|, huber_delta / |r| beyond
+  int normal_k = 16;                // plane residual: neighbours a target normal is estimated from (4..64)
 };
 
 struct ParticleWeightOpt { bool use_weight_mean = false; };  // SVNICP.h:25-27
@@ -49,6 +52,7 @@ class SVGDICP {
                 : p.optimizer == "SGD" ? SVNICP_OPT_SGD : p.optimizer == "Adagrad" ? SVNICP_OPT_ADAGRAD : SVNICP_OPT_NONE;
     if (svnicp_create(&q, device, init_pose.data(), P_, &h_) != 0) throw std::runtime_error(svnicp_last_error(nullptr));
     if (p.use_minibatch) { batch_ = p.batch_size; chk(svnicp_set_minibatch(h_, p.batch_size, p.minibatch_seed)); }
+    if (p.residual != "point") set_residual(p.residual, p.huber_delta, p.normal_k);
   }
   virtual ~SVGDICP() { svnicp_destroy(h_); }
   SVGDICP(const SVGDICP&) = delete;
@@ -111,6 +115,20 @@ class SVGDICP {
     return o;
   }
   std::array<int64_t, 2> get_minibatch_rows() { std::array<int64_t, 2> o{}; chk(svnicp_get_minibatch_rows(h_, o.data())); return o; }
+  // point-to-plane residual (svnicp_hip.h "point-to-plane residual")
+  void set_residual(const std::string& residual, double huber_delta = 0.1, int normal_k = 16) {
+    if (residual != "point" && residual != "plane") throw std::runtime_error("set_residual: \"point\" or \"plane\"");
+    chk(svnicp_set_residual(h_, residual == "plane" ? SVNICP_RESIDUAL_PLANE : SVNICP_RESIDUAL_POINT, huber_delta, normal_k));
+  }
+  // normals of the current target, [M][3] in host memory; call after add_cloud
+  void set_target_normals(const double* n_xyz, int64_t M) { chk(svnicp_set_target_normals(h_, n_xyz, M, SVNICP_MEM_HOST)); }
+  std::vector<double> get_target_normals(int64_t M) { std::vector<double> o((size_t)M * 3); chk(svnicp_get_target_normals(h_, o.data())); return o; }
+  // {accepted pairs, sum w r^2} per particle of the last iteration run; *normal_passes = normal passes run so far
+  std::vector<double> get_plane_stats(int64_t* normal_passes = nullptr) {
+    std::vector<double> o((size_t)2 * P_);
+    chk(svnicp_get_plane_stats(h_, o.data(), normal_passes));
+    return o;
+  }
   svnicp_ctx* handle() { return h_; }
 
  protected:

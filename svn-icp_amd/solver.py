@@ -53,6 +53,9 @@ class SteinICPParam:  # include/core/SVGDICP.h:41-57 (same field names and defau
     SVN_full_grad: bool = True
     record_trace: bool = False       # test hook (not in the reference)
     minibatch_seed: int = 0          # seed of the generated mini-batch tables (not in the reference: see minibatch_indices)
+    residual: str = "point"          # "point" (the reference) | "plane": Huber-weighted point-to-plane (not in the reference)
+    huber_delta: float = 0.1         # plane residual: weight 1 up to this |r|, huber_delta / |r| beyond (inf = unweighted)
+    normal_k: int = 16               # plane residual: neighbours of a target point its normal is estimated from (4..64)
 
 
 @dataclass
@@ -128,6 +131,8 @@ class _SolverBase:
         self._mb = 0      # rows per iteration in mini-batch mode, 0 = full batch
         if parameters.use_minibatch:
             self.set_minibatch(int(parameters.batch_size), int(parameters.minibatch_seed))
+        if parameters.residual != "point":
+            self.set_residual(parameters.residual, float(parameters.huber_delta), int(parameters.normal_k))
 
     # -- plumbing -------------------------------------------------------------------------
     @staticmethod
@@ -280,6 +285,50 @@ class _SolverBase:
         out = (C.c_int64 * 2)()
         self._check(self._L.svnicp_get_minibatch_rows(self._h, out), "svnicp_get_minibatch_rows")
         return int(out[0]), int(out[1])
+
+    # -- point-to-plane residual (include/svnicp_hip.h "point-to-plane residual") ---------------------------------------------
+    _RESIDUAL = {"point": 0, "plane": 1}
+
+    def set_residual(self, residual: str = "plane", huber_delta: float = 0.1, normal_k: int = 16) -> None:
+        """"point" (the reference's residual) or "plane" (Huber-weighted point-to-plane) from the next registration on."""
+        if residual not in self._RESIDUAL:
+            raise ValueError('residual must be "point" or "plane"')
+        self._check(self._L.svnicp_set_residual(self._h, self._RESIDUAL[residual], float(huber_delta), int(normal_k)),
+                    "svnicp_set_residual")
+
+    def set_target_normals(self, normals) -> None:
+        """Normals of the current target, [M, 3] (numpy, or a float64 CUDA torch tensor); call after ``add_cloud``.  Rows are
+        normalised on upload; a zero or non-finite row means "no normal here"."""
+        if _is_torch_cuda(normals):
+            import torch
+            n = normals.to(torch.float64).contiguous()
+            if n.dim() != 2 or n.shape[1] != 3:
+                raise ValueError("normals must be [M, 3]")
+            torch.cuda.current_stream(n.device).synchronize()
+            self._keep_normals = n
+            ptr, M, kind = C.c_void_p(n.data_ptr()), int(n.shape[0]), 1
+        else:
+            n = np.ascontiguousarray(np.asarray(normals, np.float64))
+            if n.ndim != 2 or n.shape[1] != 3:
+                raise ValueError("normals must be [M, 3]")
+            ptr, M, kind = n.ctypes.data_as(C.c_void_p), int(n.shape[0]), 0
+        self._check(self._L.svnicp_set_target_normals(self._h, ptr, M, kind), "svnicp_set_target_normals")
+
+    def get_target_normals(self) -> np.ndarray:
+        """The supplied or estimated unit normals of the target, [M, 3]; rows without a normal are 0."""
+        out = np.zeros((self._M, 3), np.float64)
+        self._check(self._L.svnicp_get_target_normals(self._h, out.ctypes.data_as(C.POINTER(C.c_double))),
+                    "svnicp_get_target_normals")
+        return out
+
+    def get_plane_stats(self, with_sums: bool = True) -> tuple:
+        """(per particle [P, 2] = {accepted pairs, sum w r^2} of the last iteration run, normal passes run so far);
+        ``with_sums=False`` returns (None, passes) and needs no registration."""
+        out = np.zeros((self._P, 2), np.float64) if with_sums else None
+        n = C.c_int64(0)
+        self._check(self._L.svnicp_get_plane_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_double)) if with_sums else None,
+                                                   C.byref(n)), "svnicp_get_plane_stats")
+        return out, int(n.value)
 
     def set_threshold(self, max_dist: float):
         self._check(self._L.svnicp_set_max_dist(self._h, float(max_dist)), "svnicp_set_max_dist")
