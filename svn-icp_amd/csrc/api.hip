@@ -1166,7 +1166,7 @@ static int align_enqueue(svnicp_ctx* c, bool follow_stop) {
   c->st.small_launched = false;
   if (c->st.chain == StepChain::SmallChain && c->tune.persistent && !c->prm.record_trace && !c->prof.on && c->prm.iterations > 0 &&
       small_registration_supported(c->sb.plan.PW, c->sb.plan.WP, c->K)) {
-    // all iterations in ONE cooperative launch (particle_update.hip: k_small_registration); anything the runtime refuses
+    // all iterations in ONE cooperative launch (small_registration.hip: k_small_registration); anything the runtime refuses
     // (no cooperative launch, grid not resident) falls back to the four launches per iteration
     const AccumArgs a = accum_args(c, 0);   // defer_fin is off here: fin_iteration = -1, the search body decides nothing
     if ((rc = ensure_dbg_upd(c))) return rc;

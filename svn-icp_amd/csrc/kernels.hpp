@@ -200,7 +200,7 @@ hipError_t launch_build_table2(const int32_t* idx, int64_t B, int K, const doubl
                                float4* tablef, float* cmax, hipStream_t st);
 // q[b] = (s·R^T) + t with the stage-B expression (SVNICP.cpp:62-64); pose12 = device [R row-major | t]
 hipError_t launch_transform_cloud(const double* src, int64_t B, const double* pose12, double* q, const int* ctl, hipStream_t st);
-// ---------------- particle update (particle_update.hip) ----------------
+// ---------------- particle update (particle_update.hip, small_registration.hip, particle_state.hip, reduce_partials.hip) ----------------
 struct UpdateArgs {
   const double* sums;  // [P][kNSums] (all particles); source-row sharding: [n_ranks][P][kNSums], summed in rank order on load
   int n_ranks;         // 1, or the number of row-shard records behind `sums`
@@ -246,7 +246,7 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
 hipError_t launch_update_median(const UpdateArgs& a, int num_cus, int max_p_one_workgroup, hipStream_t st);
 hipError_t launch_update_prepare(const UpdateArgs& a, hipStream_t st);
 hipError_t launch_update_prepare_median(const UpdateArgs& a, hipStream_t st);   // small chain: both in one launch (2 <= P <= 128)
-// small chain, all iterations in one cooperative launch (particle_update.hip: k_small_registration)
+// small chain, all iterations in one cooperative launch (small_registration.hip: k_small_registration)
 bool small_registration_supported(int PW, int WP, int K);
 hipError_t launch_small_registration(const AccumPlan& plan, AccumArgs a, const UpdateArgs& u, int iterations, unsigned int* bar,
                                      int num_cus, hipStream_t st);

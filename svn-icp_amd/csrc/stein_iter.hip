@@ -31,7 +31,7 @@
 
 #include "kernels.hpp"
 #include "stein_common.hpp"
-#include "update_single.hpp"
+#include "stein_step_device.hpp"
 
 namespace svnicp {
 
@@ -39,7 +39,7 @@ namespace {
 
 // ONE particle and nothing between the sums and the update (no exchange between ranks): the workgroup that finishes last —
 // one __threadfence and one atomic ticket per workgroup, nobody waits — adds the workgroups' partial sums in block order
-// and runs the whole Stein step (update_single.hpp: for P = 1 it is the Newton step and the pose update, a few
+// and runs the whole Stein step (stein_step_device.hpp: for P = 1 it is the Newton step and the pose update, a few
 // microseconds on one thread).  An iteration of a plain-ICP registration is then ONE launch instead of three
 // (accumulate, k_reduce_partials, k_particle_update).  Block-wide call; `lds` = the kernel's dynamic LDS (free by now).
 __device__ inline void single_particle_tail(const AccumArgs& a, const UpdateArgs& u, double* lds) {
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(NT) void k_icp_single(AccumArgs a, UpdateArgs u) {
 }
 
 template <int PW, int WP>
-__global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a, UpdateArgs u, int fuse_single) {
+__global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a) {
   if (a.ctl[0]) return;  // early stop already signalled (SVNICP.cpp:95-101)
   constexpr int BW = kWave / PW;  // source points per wave pass
   constexpr int WB = 4 / WP;      // waves along the source-point axis
@@ -254,29 +254,10 @@ __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a, UpdateArgs
       }
       if (valid) {
         if (a.corr) a.corr[(size_t)p * a.B + (b0 + pt)] = kb;
-        double w = 1.0, e0 = 0.0, e1 = 0.0, e2 = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0;
-        if (best < a.max_dist) {  // point_filter, SVGDICP.cpp:331-333
-          const double n = sqrt(best);                      // ‖Ts − q‖, SVNICP.cpp:120
-          const double wq = a.max_dist / (a.max_dist + 3 * n);
-          w = wq * wq;                                      // SVNICP.cpp:122
-          e0 = w * (T0 - row[3 * kb]);                      // SVNICP.cpp:119,123
-          e1 = w * (T1 - row[3 * kb + 1]);
-          e2 = w * (T2 - row[3 * kb + 2]);
-          m0 = s0; m1 = s1; m2 = s2;
-        } else if (best != best) {   // masking is a multiplication in the reference: a NaN row stays NaN (see k_icp_single)
-          w = best; e0 = best; e1 = best; e2 = best;
-        }
-        const double w0 = w * m0, w1 = w * m1, w2 = w * m2;
-        acc[0] += w;
-        acc[1] += w0; acc[2] += w1; acc[3] += w2;
-        // SVGD mode needs count_nonzero(mask·Ts summed over xyz) (SVGDICP.cpp:404) instead of Σw·s_x²
-        acc[4] = a.svgd ? acc[4] + ((best < a.max_dist && ((T0 + T1) + T2) != 0.0) ? 1.0 : 0.0) : fma(w0, m0, acc[4]);
-        acc[5] = fma(w0, m1, acc[5]); acc[6] = fma(w0, m2, acc[6]);
-        acc[7] = fma(w1, m1, acc[7]); acc[8] = fma(w1, m2, acc[8]); acc[9] = fma(w2, m2, acc[9]);
-        acc[10] += e0; acc[11] += e1; acc[12] += e2;
-        acc[13] = fma(e0, m0, acc[13]); acc[14] = fma(e0, m1, acc[14]); acc[15] = fma(e0, m2, acc[15]);
-        acc[16] = fma(e1, m0, acc[16]); acc[17] = fma(e1, m1, acc[17]); acc[18] = fma(e1, m2, acc[18]);
-        acc[19] = fma(e2, m0, acc[19]); acc[20] = fma(e2, m1, acc[20]); acc[21] = fma(e2, m2, acc[21]);
+        Pending pd;   // the winner's coordinates are at hand in LDS: nothing is pending here
+        pd.T0 = T0; pd.T1 = T1; pd.T2 = T2; pd.pt = pt;
+        pd.q0 = row[3 * kb]; pd.q1 = row[3 * kb + 1]; pd.q2 = row[3 * kb + 2];
+        accumulate_point(pd, spts, a.max_dist, a.svgd, acc);
       }
     }
   }
@@ -329,7 +310,7 @@ __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a, UpdateArgs
 // kernel, so correspondences and sums are bit-identical to it.
 // ---------------------------------------------------------------------------------------------
 template <int PW, int WP>
-__global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a, UpdateArgs u, int fuse_single) {
+__global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a) {
   if (a.ctl[0]) return;
   constexpr int BW = kWave / PW;
   constexpr int WB = 4 / WP;
@@ -492,7 +473,6 @@ __global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a, Upd
 #pragma unroll
     for (int i = 0; i < kNSums; ++i) out[i] = acc[i];
   }
-  if (fuse_single) single_particle_tail(a, u, lds);
 }
 
 // candidate table: f64 absolute coordinates (target_batch = index_select(target, sourceKNN_idx),
@@ -523,19 +503,17 @@ __global__ __launch_bounds__(256) void k_build_table2(const int32_t* __restrict_
   if (lane == 0) cmax[b] = cm;   // NaN coordinates give NaN scores => every step takes the exact path
 }
 
-// (k_reduce_partials lives in particle_update.hip: its last workgroup goes on with the sums-dependent half of the Stein step)
+// (k_reduce_partials, which adds the workgroups' partial rows per particle, lives in reduce_partials.hip)
 
 template <int PW, int WP>
-hipError_t launch_t(const AccumPlan& plan, const AccumArgs& a, const UpdateArgs* single, hipStream_t st) {
+hipError_t launch_t(const AccumPlan& plan, const AccumArgs& a, hipStream_t st) {
   auto kern = plan.f32 ? k_stein_accumulate_f32<PW, WP> : k_stein_accumulate<PW, WP>;
   if (plan.smem > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.smem);
     if (e != hipSuccess) return e;
   }
-  UpdateArgs u{};
-  if (single) u = *single;
-  hipLaunchKernelGGL(kern, dim3(plan.grid_x, plan.grid_y), dim3(NT), plan.smem, st, a, u, (single && plan.f32 == 1) ? 1 : 0);
+  hipLaunchKernelGGL(kern, dim3(plan.grid_x, plan.grid_y), dim3(NT), plan.smem, st, a);
   return hipGetLastError();
 }
 
@@ -637,8 +615,9 @@ AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f3
   return pl;
 }
 
-// single != nullptr (one particle, fused f32 kernel, no exchange between ranks): the kernel's last workgroup also reduces
-// the partial sums and runs the Stein step — the caller launches neither k_reduce_partials nor an update kernel
+// single != nullptr (one particle, fused f32 plan, no exchange between ranks): k_icp_single runs the whole iteration — its
+// last workgroup also reduces the partial sums and runs the Stein step, the caller launches neither k_reduce_partials nor an
+// update kernel
 bool accumulate_can_fuse_single(const AccumPlan& plan) { return plan.f32 == 1; }
 int single_particle_grid(int64_t B) { return (int)((B + 63) / 64); }
 hipError_t launch_accumulate(const AccumPlan& plan, AccumArgs a, const UpdateArgs* single, hipStream_t st) {
@@ -651,13 +630,13 @@ hipError_t launch_accumulate(const AccumPlan& plan, AccumArgs a, const UpdateArg
     return hipGetLastError();
   }
   switch (plan.PW) {
-    case 8: return launch_t<8, 1>(plan, a, single, st);
-    case 16: return launch_t<16, 1>(plan, a, single, st);
-    case 32: return launch_t<32, 1>(plan, a, single, st);
+    case 8: return launch_t<8, 1>(plan, a, st);
+    case 16: return launch_t<16, 1>(plan, a, st);
+    case 32: return launch_t<32, 1>(plan, a, st);
     default:
-      if (plan.WP == 1) return launch_t<64, 1>(plan, a, single, st);
-      if (plan.WP == 2) return launch_t<64, 2>(plan, a, single, st);
-      return launch_t<64, 4>(plan, a, single, st);
+      if (plan.WP == 1) return launch_t<64, 1>(plan, a, st);
+      if (plan.WP == 2) return launch_t<64, 2>(plan, a, st);
+      return launch_t<64, 4>(plan, a, st);
   }
 }
 

@@ -1,5 +1,5 @@
 // stein_split_device.hpp — device bodies of stage B's two kernels (k_stein_search_bf16, k_stein_accumulate_w) and their
-// helpers.  Included by stein_split.hip (the kernels and their launchers) and by particle_update.hip (the persistent
+// helpers.  Included by stein_split.hip (the kernels and their launchers) and by small_registration.hip (the persistent
 // small-registration kernel runs the same bodies on virtual blocks).  See stein_split.hip for the overview.
 #pragma once
 #include <cstdlib>
@@ -187,7 +187,7 @@ constexpr float kEpsBf16 = (float)SVNICP_SEARCH_EPS_U * 5.9604644775390625e-08f;
 #define SVNICP_SEARCH_WAVES 4
 #endif
 // (bx, by): the workgroup's place in the launch geometry — blockIdx for k_stein_search_bf16, a virtual block for the
-// persistent small-registration kernel (particle_update.hip)
+// persistent small-registration kernel (small_registration.hip)
 template <int PW, int WP, int NRB, bool TAIL>
 __device__ __forceinline__ void search_body(const AccumArgs& a, int bx, int by) {
   if (a.ctl[0]) return;

@@ -627,6 +627,56 @@ def test_small_chain_equals_general_chain(hip, orc, P, full, mode):
 
 
 @pytest.mark.parametrize("P,full,mode,es", [(30, False, "svn", False), (128, False, "svn", False), (17, True, "svn", False), (9, False, "svn", True),
+                                             (64, False, "svgd", False), (33, False, "svgd", True), (130, False, "svn", False)])
+def test_step_shapes_equal_default_chain(hip, orc, P, full, mode, es):
+    """Every launch shape of the Stein step composes the same device functions (stein_step_device.hpp); the options reach
+    them: update=fused the one-workgroup kernels (k_particle_update, k_particle_update_svgd), chain=general the prepare
+    kernel with the pair statistics inline and k_reduce_partials, chain=general + median=stream the pair statistics on
+    the second stream (k_upd_median); median=stream alone leaves a small registration on the small chain.  Above 128
+    particles the default is already the second-stream chain (k_upd_hist -> collect -> select) whatever median= says, so
+    that case compares it with the one-workgroup kernel alone (fused_update_max_p raised to P).  Same correspondences, each
+    shape equal to the oracle, the shapes equal to one another to rounding: they differ in how the sums over the source
+    points are grouped, in the order of the mean-Hessian and early-stop sums and in the route to the (exact) median."""
+    B, M, K, I = 1100, 9000, 100, 12
+    src, tgt = hip.scans.random_clouds(B, M, seed=P + 11, extent=20.0)
+    init = hip.scans.make_particles(P, seed=P) * 0.2
+    cfg = dict(iterations=I, lr=1.0, max_dist=1.0, check_early_stop=es, convergence_threshold=(3e-2 if es else 1e-5), knn_count=K, svn_full_grad=full)
+    if mode == "svgd":
+        cfg = dict(cfg, lr=0.01, optimizer="Adam", convergence_threshold=(8e-3 if es else 1e-5)); cfg.pop("svn_full_grad")
+        o = orc.Solver(init, mode=orc.MODE_SVGD, svn_full_grad=False, **cfg)
+        mk = lambda: _hip_svgd(hip, init, cfg)
+    else:
+        o = orc.Solver(init, **cfg)
+        mk = lambda: _hip_solver(hip, init, **cfg)
+    o.add_cloud(src, tgt, init); tro = o.enable_trace(); o.stein_align()
+    shapes = {"default": (), "fused": (("update", "fused"),) + ((("fused_update_max_p", P),) if P > 128 else ())}
+    if P <= 128:
+        shapes.update({"stream": (("median", "stream"),), "general": (("chain", "general"),),
+                       "general+stream": (("chain", "general"), ("median", "stream"))})
+    out = {}
+    for name, options in shapes.items():
+        s = mk()
+        for k, v in options:
+            s.set_option(k, v)
+        s.add_cloud(src, tgt, init)
+        assert s.stein_align() == hip.SteinICPState.ALIGN_SUCCESS, name
+        assert s.get_iterations_run() == o.iterations_run() and int(s.get_runtime()[2]) == o.finish_iter(), name
+        if mode == "svgd":
+            assert np.allclose(s.get_particles(), o.get_particles(), rtol=0, atol=TIGHT), name
+        else:
+            _compare(s, o, tro, P)
+        out[name] = (s.get_particles(), s.get_trace()["corr"], s.get_particle_history(), s.get_transformation(), s.get_cov_matrix())
+    for name, got in out.items():
+        assert np.array_equal(got[1], out["default"][1]), name
+        for x, y in zip(got, out["default"]):
+            print(f"step shape {name} vs default: max |difference| = {np.abs(np.asarray(x, dtype=np.float64) - y).max():.3e}")
+        assert np.allclose(got[0], out["default"][0], rtol=0, atol=1e-10), name
+        assert np.allclose(got[3], out["default"][3], rtol=0, atol=1e-10) and np.allclose(got[4], out["default"][4], rtol=0, atol=1e-10), name
+    if es and mode == "svn":
+        assert o.iterations_run() < I
+
+
+@pytest.mark.parametrize("P,full,mode,es", [(30, False, "svn", False), (128, False, "svn", False), (17, True, "svn", False), (9, False, "svn", True),
                                              (64, False, "svgd", False), (33, False, "svgd", True)])
 def test_small_registration_persistent_kernel(hip, orc, P, full, mode, es):
     """Option chain=persistent: svnicp_align of a small registration (K = 97…100, no traces) runs ALL iterations in one
