@@ -189,8 +189,11 @@ int svnicp_get_minibatch_rows(svnicp_ctx *ctx, int64_t out2[2]);         /* {uni
 #define SVNICP_RESIDUAL_PLANE 1
 int svnicp_set_residual(svnicp_ctx *ctx, int residual, double huber_delta, int normal_k);
 /* optional: normals of the current target, double [M][3], host or device (copied).  Must follow the svnicp_set_target /
- * svnicp_set_clouds it belongs to, with the same M; rows are normalised on upload, a zero or non-finite row means "no normal
- * here"; a later svnicp_set_target drops them. */
+ * svnicp_set_clouds it belongs to, with the same M; rows are normalised on upload (n / |n| in float64: a row that is already
+ * unit comes back from svnicp_get_target_normals within 2 ulp, not necessarily bit for bit), a zero or non-finite row means "no
+ * normal here" and stays zero; a later svnicp_set_target drops them.  SVNICP_MEM_HOST: copied when the call returns.
+ * SVNICP_MEM_DEVICE: the device-to-device copy is QUEUED on the context's stream, as svnicp_set_target's is: the rows must stay
+ * unchanged until a call that synchronises that stream (svnicp_align, svnicp_synchronize) has returned. */
 int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, int mem_kind);
 /* taps: the supplied or estimated unit normals, rows without a normal are 0 (SVNICP_ERR_INVALID before there are any);
  * per particle {accepted pairs, sum w r^2} of the last iteration run, and the count of normal passes run so far
@@ -254,6 +257,22 @@ int svnicp_map_skipped_points(svnicp_map *map, int64_t *out);
 int svnicp_map_query(svnicp_map *map, const double center[3], double max_range, int64_t *count_out);
 void *svnicp_map_points_devptr(svnicp_map *map);              /* double [count][3] of the last query */
 int svnicp_map_download(svnicp_map *map, double *out_xyz, int64_t cap_points, int64_t *n_out); /* test tap */
+/* normals of the rows of the LAST svnicp_map_query, from the 27-voxel neighbourhoods of the map: the candidates of a row are
+ * all points the map stores in the 3 x 3 x 3 block of voxels around the row's own voxel (selected by the query or not; voxel
+ * indices outside +-2^20 do not exist), enumerated in ascending (x, y, z) voxel index and slot; its neighbours are the
+ * normal_k candidates smallest by (d2, enumeration order), d2 = ((dx*dx)+dy*dy)+dz*dz in float64 of the widened float32
+ * coordinates; normal and validity from them exactly as for svnicp_set_residual's own pass (two-pass scatter matrix of the
+ * offsets to the point, 8 Jacobi sweeps, lambda1 >= 0.01 * lambda2).  Fewer than normal_k candidates: no normal (a zero row).
+ * Nothing is stored in the map, and the same map gives bit-identical normals on every call.
+ * normal_k 4..64, 0 = 16.  SVNICP_ERR_INVALID: no query yet, or the map changed (add_cloud / clear) since the last query,
+ * or normal_k out of range.  Complete when the call returns, like the query.  with_normal_out may be NULL.  An empty
+ * selection is not an error: nothing is written and *with_normal_out = 0. */
+int svnicp_map_query_normals(svnicp_map *map, int normal_k, int64_t *with_normal_out);
+void *svnicp_map_normals_devptr(svnicp_map *map);      /* double [count][3], rows as svnicp_map_points_devptr's; feeds
+                                                          svnicp_set_target_normals(..., SVNICP_MEM_DEVICE), whose copy is
+                                                          stream-ordered: synchronise the context (svnicp_align does) before the
+                                                          next query / add_cloud / clear, which invalidate the rows (NULL then) */
+int svnicp_map_download_normals(svnicp_map *map, double *out_xyz, int64_t cap_points, int64_t *n_out);   /* test tap */
 
 /* ---- test-only taps (parity tests; not part of the reference interface) -------------------- */
 int svnicp_get_candidates(svnicp_ctx *ctx, int32_t *outBK);          /* sourceKNN_idx_  SVGDICP.cpp:214 */

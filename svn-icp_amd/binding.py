@@ -91,6 +91,10 @@ def load_library():
     L.svnicp_map_points_devptr.argtypes = [vp]
     L.svnicp_map_points_devptr.restype = vp
     L.svnicp_map_download.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64)]
+    L.svnicp_map_query_normals.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
+    L.svnicp_map_normals_devptr.argtypes = [vp]
+    L.svnicp_map_normals_devptr.restype = vp
+    L.svnicp_map_download_normals.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64)]
     L.svnicp_prep_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.svnicp_prep_destroy.argtypes = [vp]
     L.svnicp_prep_destroy.restype = None

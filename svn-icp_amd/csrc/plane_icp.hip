@@ -11,6 +11,7 @@
 //   k_plane_finalize    adds the workgroups' records in a fixed order, mirrors H, adds the 1e-6 damping: [P][42] = H | b,
 //                       which the Stein-step kernels read in place of finalize_Hb's output (UpdateArgs::plane_Hb).
 #include "kernels.hpp"
+#include "plane_normal_device.hpp"
 #include "stein_common.hpp"
 
 namespace svnicp {
@@ -22,29 +23,6 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // normals
 // ---------------------------------------------------------------------------------------------
-constexpr int kJacobiSweeps = 8;   // cyclic Jacobi on a symmetric 3x3 converges quadratically: 4-5 sweeps reach f64 round-off
-
-// one Jacobi rotation of the (P, Q) plane; R is the remaining index.  A = [a00 a11 a22 a01 a02 a12], V row-major.
-template <int P, int Q, int R>
-__device__ __forceinline__ void jacobi_rot(double* d, double& apq, double& apr, double& aqr, double* V) {
-  if (apq == 0.0) return;
-  const double theta = (d[Q] - d[P]) / (2.0 * apq);
-  const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // |theta| huge: t = 0
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  d[P] -= t * apq;
-  d[Q] += t * apq;
-  apq = 0.0;
-  const double rp = apr, rq = aqr;
-  apr = c * rp - s * rq;
-  aqr = s * rp + c * rq;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double vp = V[3 * i + P], vq = V[3 * i + Q];
-    V[3 * i + P] = c * vp - s * vq;
-    V[3 * i + Q] = s * vp + c * vq;
-  }
-}
-
 // nbr: [rows][kn] target indices of the rows' neighbours (row r = target point row_lo + r), nearest first, itself included
 __global__ __launch_bounds__(256) void k_target_normals(const double* __restrict__ tgt, int64_t M, const int32_t* __restrict__ nbr,
                                                         int64_t row_lo, int64_t rows, int kn, double* __restrict__ rec) {
@@ -72,31 +50,8 @@ __global__ __launch_bounds__(256) void k_target_normals(const double* __restrict
     d[0] += c0 * c0; d[1] += c1 * c1; d[2] += c2 * c2;
     a01 += c0 * c1; a02 += c0 * c2; a12 += c1 * c2;
   }
-  double V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  if (finite) {
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-      jacobi_rot<0, 1, 2>(d, a01, a02, a12, V);
-      // in the (0, 2) plane the third index is 1: its couplings are a01 (with 0) and a12 (with 2)
-      jacobi_rot<0, 2, 1>(d, a02, a01, a12, V);
-      // in the (1, 2) plane the third index is 0: a01 (with 1) and a02 (with 2)
-      jacobi_rot<1, 2, 0>(d, a12, a01, a02, V);
-    }
-  }
-  // λ0 <= λ1 <= λ2 and the column of λ0
-  int lo = 0;
-  if (d[1] < d[lo]) lo = 1;
-  if (d[2] < d[lo]) lo = 2;
-  const double l0 = lo == 0 ? d[0] : (lo == 1 ? d[1] : d[2]);
-  const double oa = lo == 0 ? d[1] : d[0], ob = lo == 2 ? d[1] : d[2];
-  const double l1 = oa < ob ? oa : ob, l2 = oa < ob ? ob : oa;
-  (void)l0;
-  double n0 = lo == 0 ? V[0] : (lo == 1 ? V[1] : V[2]);
-  double n1 = lo == 0 ? V[3] : (lo == 1 ? V[4] : V[5]);
-  double n2 = lo == 0 ? V[6] : (lo == 1 ? V[7] : V[8]);
-  const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-  // valid: every neighbour finite, a neighbourhood with extent, and not collinear (kPlaneMinRatio)
-  const bool valid = finite && l2 > 0.0 && l1 >= kPlaneMinRatio * l2 && nn > 0.0;
-  n0 = valid ? n0 / nn : 0.0; n1 = valid ? n1 / nn : 0.0; n2 = valid ? n2 / nn : 0.0;
+  double n0, n1, n2;
+  normal_from_scatter(d[0], d[1], d[2], a01, a02, a12, finite, n0, n1, n2);   // plane_normal_device.hpp
   double* o = rec + 6 * i;
   o[0] = x0; o[1] = x1; o[2] = x2; o[3] = n0; o[4] = n1; o[5] = n2;
 }

@@ -2,12 +2,14 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1]
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1]
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
-//      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355)
+//      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
+//      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
+//             — with map_normals 1 followed, for a registered scan, by int64 with_normal
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
   cfg.gpu_prep = argc > 8 && atoi(argv[8]) >= 2;
   cfg.deskew = argc > 9 && atoi(argv[9]) != 0;
   cfg.segmentation = argc > 10 && atoi(argv[10]) != 0;
+  cfg.plane = cfg.map_normals = argc > 11 && atoi(argv[11]) != 0;
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;
@@ -64,6 +67,7 @@ int main(int argc, char** argv) {
       wr(fo, tap.source.data(), tap.source.size()); wr(fo, tap.target.data(), tap.target.size());
       tap.particles.resize((size_t)6 * cfg.particle_count, 0.0);
       wr(fo, tap.particles.data(), tap.particles.size());
+      if (cfg.map_normals && r.aligned) wr(fo, &r.with_normal, 1);
       printf("scan %d: aligned %d  B %lld  M %lld  voxels %zu  h2d bytes so far %zu  pose t = %.4f %.4f %.4f\n", s, aligned, (long long)B,
              (long long)M, pipe.map_voxels(), pipe.bytes_h2d(), r.pose.t[0], r.pose.t[1], r.pose.t[2]);
     }

@@ -469,6 +469,17 @@ class DeviceVoxelMap {
     if (n) chk(svnicp_map_download(m_, o.data(), n, &n));
     return o;
   }
+  // normals of the rows of the last GetMap from the 27-voxel neighbourhoods of the map (svnicp_map_query_normals)
+  // -> rows with a normal; the rows ([count][3], 0 = no normal) are at normals_devptr()
+  int64_t QueryNormals(int normal_k) { int64_t n = 0; chk(svnicp_map_query_normals(m_, normal_k, &n)); return n; }
+  const double* normals_devptr() { return static_cast<const double*>(svnicp_map_normals_devptr(m_)); }
+  std::vector<double> download_normals() {   // test tap
+    int64_t n = 0;
+    chk(svnicp_map_download_normals(m_, nullptr, 0, &n));
+    std::vector<double> o((size_t)3 * n);
+    if (n) chk(svnicp_map_download_normals(m_, o.data(), n, &n));
+    return o;
+  }
 
  private:
   void chk(int rc) { if (rc != 0) throw std::runtime_error(svnicp_map_last_error(m_)); }
@@ -569,6 +580,11 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   bool segmentation = false;   // USE_Segmentation (:180, :328-355): range-image segmentation of the raw scan first; the segmented
                                // cloud has no time field (:363-381), so per-point stamps are dropped (KITTI deskew still runs)
   svnicp_seg_params seg_params = seg_hdl64e_params();
+  bool plane = false;          // the Huber-weighted point-to-plane residual (svnicp_set_residual; not in the reference)
+  double huber_delta = 0.1;    // with plane: weight 1 up to this |r|, huber_delta / |r| beyond
+  int normal_k = 16;           // with plane: neighbours a target normal is estimated from (4..64)
+  bool map_normals = false;    // with plane and gpu_map: the target's normals come from the map's own voxels
+                               // (DeviceVoxelMap::QueryNormals) instead of the solver's pass over the target
 };
 
 struct ScanResult {
@@ -578,6 +594,7 @@ struct ScanResult {
   int state = 0;
   std::array<double, 6> correction{}, variance{};
   std::vector<double> cov, particles, weights;
+  int64_t with_normal = -1;   // cfg.map_normals: target rows the map gave a normal
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -593,6 +610,9 @@ class RegistrationPipeline {
  public:
   explicit RegistrationPipeline(const PipelineConfig& cfg)
       : cfg_(cfg), map_(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points), rng_(cfg.seed * 0x9e3779b97f4a7c15ull + 0x2545f4914f6cdd1dull) {
+    if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
+    if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
+    if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
     if (cfg.gpu_map) dmap_ = std::make_unique<DeviceVoxelMap>(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points, cfg.device);
     if (cfg.gpu_map && cfg.gpu_prep) dprep_ = std::make_unique<DevicePrep>(cfg.device);
   }
@@ -664,6 +684,7 @@ class RegistrationPipeline {
     if (dmap_) {
       int64_t M = dmap_->GetMap(guess, scan_max_range_ + 10.0);                                        // :577-578
       if (M == 0) M = dmap_->GetMap();                                                                 // :579-581
+      if (cfg_.map_normals) res.with_normal = dmap_->QueryNormals(cfg_.normal_k);
       if (dprep_) {
         solver_->add_cloud_device(dprep_->source(), dprep_->n_source, dmap_->points_devptr(), M, init.data(), cfg_.particle_count);
         if (tap_) src64 = dprep_->download_source();
@@ -671,6 +692,7 @@ class RegistrationPipeline {
         solver_->add_cloud_device_target(src64.data(), (int64_t)source.size(), dmap_->points_devptr(), M, init.data(), cfg_.particle_count);
         bytes_h2d_ += src64.size() * 8;
       }
+      if (cfg_.map_normals) solver_->set_target_normals_device(dmap_->normals_devptr(), M);   // right after the target they belong to
       if (tap_) tgt64 = dmap_->download();
     } else {
       Cloud target = map_.GetMap(guess, scan_max_range_ + 10.0);                                       // :577-578

@@ -122,6 +122,8 @@ class SVGDICP {
   }
   // normals of the current target, [M][3] in host memory; call after add_cloud
   void set_target_normals(const double* n_xyz, int64_t M) { chk(svnicp_set_target_normals(h_, n_xyz, M, SVNICP_MEM_HOST)); }
+  // ... [M][3] float64 rows already in HBM (svnicp_map_normals_devptr): one device-to-device copy
+  void set_target_normals_device(const double* n_dev_xyz, int64_t M) { chk(svnicp_set_target_normals(h_, n_dev_xyz, M, SVNICP_MEM_DEVICE)); }
   std::vector<double> get_target_normals(int64_t M) { std::vector<double> o((size_t)M * 3); chk(svnicp_get_target_normals(h_, o.data())); return o; }
   // {accepted pairs, sum w r^2} per particle of the last iteration run; *normal_passes = normal passes run so far
   std::vector<double> get_plane_stats(int64_t* normal_passes = nullptr) {

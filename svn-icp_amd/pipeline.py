@@ -532,6 +532,25 @@ class DeviceVoxelHashMap:
                       "svnicp_map_query")
         return int(self._L.svnicp_map_points_devptr(self._h) or 0), int(n.value)
 
+    def get_map_normals(self, normal_k: int = 16):
+        """Normals of the rows of the last get_map, from the 27-voxel neighbourhoods of the map (svnicp_map_query_normals)
+        -> (device pointer of float64 [M][3], rows with a normal).  A zero row means no normal."""
+        C = self._C
+        n = C.c_int64(0)
+        self._chk(self._L.svnicp_map_query_normals(self._h, int(normal_k), C.byref(n)), "svnicp_map_query_normals")
+        return int(self._L.svnicp_map_normals_devptr(self._h) or 0), int(n.value)
+
+    def download_normals(self) -> np.ndarray:
+        """The rows of the last get_map_normals as a host array (test tap)."""
+        C = self._C
+        n = C.c_int64(0)
+        self._chk(self._L.svnicp_map_download_normals(self._h, None, 0, C.byref(n)), "svnicp_map_download_normals")
+        out = np.zeros((int(n.value), 3))
+        if out.size:
+            self._chk(self._L.svnicp_map_download_normals(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0],
+                                                          C.byref(n)), "svnicp_map_download_normals")
+        return out
+
     def download(self) -> np.ndarray:
         """The rows of the last get_map as a host array (test tap)."""
         C = self._C
@@ -872,6 +891,13 @@ class PipelineConfig:
     seg_params: SegParams = field(default_factory=SegParams)   # the sensor of ImageProjection.h (SEG_PRESETS); HDL-64E by default
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
+    map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
+
+    def __post_init__(self):
+        if self.map_normals and not self.gpu_map:
+            raise ValueError("PipelineConfig: map_normals needs gpu_map=True (the normals are computed from the device map)")
+        if self.map_normals and self.solver.residual != "plane":
+            raise ValueError('PipelineConfig: map_normals needs solver.residual == "plane" (point mode uses no normals)')
 
 
 @dataclass
@@ -887,6 +913,7 @@ class ScanResult:
     preprocessing_s: float = 0.0
     align_s: float = 0.0
     state: int | None = None
+    with_normal: int | None = None           # cfg.map_normals: target rows the map gave a normal
 
 
 class RegistrationPipeline:
@@ -960,15 +987,20 @@ class RegistrationPipeline:
         if self._solver is None:
             self._solver = SVNICP(c.solver, init, ParticleWeightOpt(), device=self.device)
         s = self._solver
+        with_normal = None
         if c.gpu_map:
             ptr, M = self.map.get_map(guess, self.scan_max_range + 10.0)                                        # :577-578
             if M == 0:
                 ptr, M = self.map.get_map()                                                                     # :579-581
+            if c.map_normals:
+                nptr, with_normal = self.map.get_map_normals(c.solver.normal_k)
             if dev:
                 s.add_cloud_device(self._prep.source_ptr, self._prep.n_source, ptr, M, init)                    # :583
             else:
                 s.add_cloud_device_target(source, ptr, M, init)                                                 # :583
                 self.bytes_h2d += source.shape[0] * 24
+            if c.map_normals:
+                s.set_target_normals_device(nptr, M)                  # right after the target they belong to: no normal pass
         else:
             target = self.map.get_map(guess, self.scan_max_range + 10.0)                                        # :577-578
             if target.shape[0] == 0:
@@ -979,11 +1011,12 @@ class RegistrationPipeline:
         s.set_initial_mean(guess)                                                                               # :601
         state = s.stein_align()                                                                                 # :602
         if state != SteinICPState.ALIGN_SUCCESS:                                                                # :602-604
-            return ScanResult(stamp, guess, guess, preprocessing_s=t1 - t0, align_s=time.perf_counter() - t1, state=int(state))
+            return ScanResult(stamp, guess, guess, preprocessing_s=t1 - t0, align_s=time.perf_counter() - t1, state=int(state),
+                              with_normal=with_normal)
         corr = s.get_transformation()                                                                           # :605
         pose = guess @ correction_to_pose(corr)                                                                 # updater_, :37-46
         res = ScanResult(stamp, pose, guess, corr, s.get_distribution(), s.get_cov_matrix(), s.get_particles().reshape(-1),
-                         s.get_particle_weight(), t1 - t0, 0.0, int(state))
+                         s.get_particle_weight(), t1 - t0, 0.0, int(state), with_normal)
         # … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is
         # updated with the same points the solver registered
         if dev:

@@ -314,6 +314,13 @@ class _SolverBase:
             ptr, M, kind = n.ctypes.data_as(C.c_void_p), int(n.shape[0]), 0
         self._check(self._L.svnicp_set_target_normals(self._h, ptr, M, kind), "svnicp_set_target_normals")
 
+    def set_target_normals_device(self, normals_devptr: int, M: int) -> None:
+        """set_target_normals for float64 rows [M][3] that already live in HBM (DeviceVoxelHashMap.get_map_normals): one
+        device-to-device copy, QUEUED on the context's stream like add_cloud_device's target copy (not complete when this
+        returns): the rows must stay unchanged until stein_align or synchronize has returned."""
+        self._check(self._L.svnicp_set_target_normals(self._h, C.c_void_p(int(normals_devptr)), int(M), 1),
+                    "svnicp_set_target_normals")
+
     def get_target_normals(self) -> np.ndarray:
         """The supplied or estimated unit normals of the target, [M, 3]; rows without a normal are 0."""
         out = np.zeros((self._M, 3), np.float64)
