@@ -14,6 +14,7 @@
 
 #include "device_buffer.hpp"
 #include "kernels.hpp"
+#include "stage_a_host.hpp"
 
 using namespace svnicp;
 using namespace svnicp_host;
@@ -21,34 +22,9 @@ using namespace svnicp_host;
 namespace {
 
 // the members of svnicp_ctx, grouped by what owns the fields
-struct CloudState {   // clouds and target layout
-  DevBuf<double> src, tgt, tx, ty, tz;
-  DevBuf<float> txf, tyf, tzf;
-  DevBuf<int32_t> torig;
-  DevBuf<unsigned long long> emax;
+struct CloudState {   // the clouds as given (the re-ordered target copies are stage A's: stage_a_host.hpp)
+  DevBuf<double> src, tgt;
   bool src_set = false, tgt_set = false;
-  int target_layout = -1;  // what the SoA currently holds: 0 hashed order, 1 Morton tiles, -1 nothing
-};
-
-struct StageA {   // stage A working set: pools, fallback lists, tile arena, Morton sort scratch
-  int knn_variant = 0;   // 0 = streaming only (knn_topk), 1 = seeded f32 scan (knn_scan), 2 = pruned tiles (knn_tiles), 3 = brute force
-  int64_t scan_Ms = 0; int scan_rank = 0, scan_S2 = 0;
-  int64_t qrows = 0;                   // query rows stage A is sized for: B, or mb.nq
-  DevBuf<double> pool_d, cand_d2, sl_d, fail_tau, qrec;
-  DevBuf<int32_t> pool_i, cand_idx, pool2, fail_list, sl_i;
-  int sliced_max = 0;  // set at align_begin (kFallbackSlicedMax or SVNICP_FALLBACK_SLICED_MAX)
-  DevBuf<int> fail_count;
-  // correspondence = full reuses fail_list / fail_count for every per-particle search: stage A's own are kept here
-  DevBuf<int> stage_fail_count;
-  DevBuf<int32_t> stage_fail_list;
-  DevBuf<unsigned int> keys_a, keys_b;
-  DevBuf<int32_t> vals_a, order_t, qorder, stat_n;
-  DevBuf<unsigned long long> bbox;
-  DevBuf<float> tile_box;
-  DevBuf<unsigned char> sort_tmp;
-  size_t sort_tmp_bytes = 0;
-  DevBuf<int32_t> arena, chunk_tab;    // stage A (Morton tiles): overflow chunks of the survivor pools and their table
-  int arena_cap = 0;
 };
 
 struct StageB {   // stage B tables and per-iteration scratch
@@ -169,8 +145,7 @@ struct Profiling {   // timing events
   size_t pused = 0;
 };
 
-struct DebugCounters {   // option debug
-  DevBuf<unsigned long long> phase;   // per-phase wave cycles of k_knn_tiles / k_knn_brute (per context, per device)
+struct DebugCounters {   // option debug (stage A keeps its own: StageA::dbg_phase)
   DevBuf<unsigned long long> upd;     // phase cycles of k_particle_update
 };
 
@@ -188,8 +163,8 @@ struct svnicp_ctx {
   std::string err;
   static std::string& create_error() { thread_local std::string s; return s; }   // svnicp_last_error(nullptr)
 
-  int64_t B = 0, M = 0, Mp = 0;
-  int K = 0, S = 0, P = 0;
+  int64_t B = 0, M = 0;
+  int K = 0, P = 0;
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
@@ -199,10 +174,6 @@ struct svnicp_ctx {
 
 // Tuning::fused_update_max_p default 128: measured crossover (C3: equal, P=256: 4.5x); above it the Stein step runs as
 // workgroup-parallel kernels
-constexpr int kFallbackGrid = 256;  // workgroups of the streaming kernel when it only redoes failed queries
-constexpr int kFallbackSlicedMax = 512;  // up to this many failed queries are redone by target slices (all CUs per query)
-constexpr int kFallbackQW = 2;      // … two queries per wave, so a few hundred failures still run in parallel
-
 enum { KC_KNN = 0, KC_TABLE = 1, KC_SEARCH = 2, KC_ACCUM = 3, KC_REDUCE = 4, KC_UPDATE = 5, KC_COUNT = SVNICP_KERNEL_CLASSES };
 
 static hipError_t prof_begin(svnicp_ctx* c, int cls) {
@@ -234,6 +205,10 @@ static hipError_t prof_end(svnicp_ctx* c) {
 static int bind(svnicp_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   return 0;
+}
+
+static StageAEnv stage_a_env(const svnicp_ctx* c) {
+  return {c->stream, c->tune, c->num_cus, c->prm.record_trace != 0, c->cloud.tgt.p, c->B, c->M, c->pose0};
 }
 
 constexpr int kMedianInlineMaxP = 128;   // the one-workgroup pair statistics
@@ -370,8 +345,8 @@ int svnicp_set_target(svnicp_ctx* c, const double* tgt, int64_t M, int mem_kind)
   if (!tgt || M < 1) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target: need M >= 1");
   if (M > 0x7fffffffLL) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target: cloud too large");
   if (const int rc = upload_cloud(c, c->cloud.tgt, tgt, M, mem_kind)) return rc;
-  c->M = M; c->Mp = knn_padded_targets(M);
-  c->cloud.target_layout = -1;  // the SoA copies are (re)built in svnicp_align_begin, once K is final
+  c->M = M;
+  c->sa.held = TargetLayout::None;  // the SoA copies are (re)built in svnicp_align_begin, once K is final
   c->cloud.tgt_set = true;
   c->pl.supplied = false; c->pl.estimated = false;   // normals belong to the target they were given or estimated for
   return SVNICP_OK;
@@ -457,7 +432,8 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   auto num = [&](int lo, int hi, int* out) { char* end = nullptr; const long x = strtol(v.c_str(), &end, 10);
                                              if (end == v.c_str() || *end || x < lo || x > hi) return false; *out = (int)x; return true; };
   bool ok = true;
-  if (k == "knn") { if (v == "auto") t.knn = -1; else if (v == "v1") t.knn = 0; else if (v == "v2") t.knn = 1; else if (v == "brute") t.knn = 2; else if (v == "tiles") t.knn = 3; else ok = false; }
+  if (k == "knn") { if (v == "auto") t.knn = {}; else if (v == "v1") t.knn = {false, KnnKernel::Stream}; else if (v == "v2") t.knn = {false, KnnKernel::SeededScan};
+                    else if (v == "brute") t.knn = {false, KnnKernel::Brute}; else if (v == "tiles") t.knn = {false, KnnKernel::Tiles}; else ok = false; }
   else if (k == "fallback_sliced_max") ok = num(-1, 1 << 20, &t.fallback_sliced_max);
   else if (k == "accum") { if (v == "f64") t.accum = 0; else if (v == "valu") t.accum = 1; else if (v == "split") t.accum = 3; else ok = false; }
   else if (k == "update") { if (v == "auto") t.update_fused = 0; else if (v == "fused") t.update_fused = 1; else ok = false; }
@@ -477,7 +453,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   else return fail(c, SVNICP_ERR_INVALID, "svnicp_set_option: unknown option '" + k + "'");
   if (!ok) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_option: bad value '" + v + "' for option '" + k + "'");
   c->run.have_candidates = false;
-  c->cloud.target_layout = -1;
+  c->sa.held = TargetLayout::None;
   // svnicp_iter_accumulate now refuses until the next svnicp_align_begin; svnicp_iter_update goes on and follows the new options
   if (c->run.began) choose_step_chain(c);
   return SVNICP_OK;
@@ -508,46 +484,10 @@ int svnicp_set_row_shard(svnicp_ctx* c, int row_rank, int row_world, int64_t tot
 
 void* svnicp_rank_sums_devptr(svnicp_ctx* c) { return (c && c->shard.row_world > 1) ? (void*)c->shard.rank_sums.p : nullptr; }
 
-// words of chunk_tab (Morton-tile stage A) for `rows` query rows
-static size_t tiles_chunk_tab_words(int64_t rows) { return (size_t)rows * kTilesChunks + 16 + (size_t)(rows + 63) / 64 + 1; }
-
-// (re)build the target SoA copies in the order the chosen stage-A kernel wants
-static int ensure_target_layout(svnicp_ctx* c) {
-  int want = 0;
-  if (knn_tiles_applicable(c->Mp, c->K)) want = 2;
-  else if (knn_scan_plan(c->Mp, c->K, &c->sa.scan_Ms, &c->sa.scan_rank, &c->sa.scan_S2)) want = 1;
-  if (c->tune.knn == 0) want = 0;   // option "knn": v1 | v2 | brute | tiles (A/B for tests and profiling)
-  if (c->tune.knn == 1) want = knn_scan_plan(c->Mp, c->K, &c->sa.scan_Ms, &c->sa.scan_rank, &c->sa.scan_S2) ? 1 : 0;
-  // small registrations (the scan-to-map loop's sizes, BASELINE C1): brute force in one launch, no target layout at all
-  if ((c->tune.knn == -1 && knn_brute_applicable(c->sa.qrows, c->M, c->K)) || (c->tune.knn == 2 && c->K <= 128 && c->M < (1ll << 31))) want = 3;
-  c->sa.knn_variant = want;
-  if (want == 3) return 0;
-  const int layout = want == 2 ? 1 : 0;
-  if (c->cloud.target_layout == layout) return 0;
-  const int64_t M = c->M, Mp = c->Mp;
-  HIPCHK(c, c->cloud.tx.ensure((size_t)Mp)); HIPCHK(c, c->cloud.ty.ensure((size_t)Mp)); HIPCHK(c, c->cloud.tz.ensure((size_t)Mp));
-  HIPCHK(c, c->cloud.txf.ensure((size_t)Mp)); HIPCHK(c, c->cloud.tyf.ensure((size_t)Mp)); HIPCHK(c, c->cloud.tzf.ensure((size_t)Mp));
-  HIPCHK(c, c->cloud.torig.ensure((size_t)Mp));
-  HIPCHK(c, c->cloud.emax.ensure(1));
-  if (layout == 0) {
-    HIPCHK(c, launch_targets_soa2(c->cloud.tgt.p, M, Mp, c->cloud.tx.p, c->cloud.ty.p, c->cloud.tz.p, c->cloud.txf.p, c->cloud.tyf.p, c->cloud.tzf.p, c->cloud.torig.p,
-                                  c->cloud.emax.p, c->stream));
-  } else {
-    const size_t nmax = (size_t)(M > c->B ? M : c->B);
-    HIPCHK(c, c->sa.keys_a.ensure(nmax)); HIPCHK(c, c->sa.keys_b.ensure(nmax)); HIPCHK(c, c->sa.vals_a.ensure(nmax));
-    HIPCHK(c, c->sa.order_t.ensure((size_t)M)); HIPCHK(c, c->sa.qorder.ensure((size_t)c->B));
-    HIPCHK(c, c->sa.bbox.ensure(6));
-    HIPCHK(c, c->sa.tile_box.ensure((size_t)6 * (Mp / 512)));
-    const size_t tb = sort_temp_bytes(nmax);
-    if (tb > c->sa.sort_tmp_bytes) { HIPCHK(c, c->sa.sort_tmp.ensure(tb)); c->sa.sort_tmp_bytes = tb; }
-    HIPCHK(c, launch_bbox(c->cloud.tgt.p, M, c->sa.bbox.p, c->stream));
-    HIPCHK(c, launch_morton_order(c->cloud.tgt.p, 0, M, 0, c->pose0, c->sa.bbox.p, c->sa.keys_a.p, c->sa.keys_b.p, c->sa.vals_a.p,
-                                  c->sa.order_t.p, c->sa.sort_tmp.p, c->sa.sort_tmp_bytes, c->stream));
-    HIPCHK(c, launch_targets_sorted(c->cloud.tgt.p, M, Mp, c->sa.order_t.p, c->cloud.tx.p, c->cloud.ty.p, c->cloud.tz.p, c->cloud.txf.p, c->cloud.tyf.p, c->cloud.tzf.p,
-                                    c->cloud.torig.p, c->sa.tile_box.p, c->cloud.emax.p, c->stream));
-  }
-  c->cloud.target_layout = layout;
-  return 0;
+// plane mode: this registration estimates the target's normals itself — none were supplied, and the ones at hand were not
+// estimated from this target with this normal_k
+static bool normal_pass_due(const svnicp_ctx* c) {
+  return c->pl.on && !c->pl.supplied && !(c->pl.estimated && c->pl.est_k == c->pl.normal_k);
 }
 
 static int prepare_plane(svnicp_ctx* c);
@@ -597,45 +537,12 @@ int svnicp_align_begin(svnicp_ctx* c) {
   c->mb.on = mb; c->mb.have = false; c->mb.check = false;
   c->mb.rows = mb ? (int64_t)I * c->mb.batch : 0;
   c->mb.nq = mb ? std::min<int64_t>(B, c->mb.rows) : 0;
-  c->sa.qrows = mb ? c->mb.nq : B;
-  const int64_t Bq = c->sa.qrows;                 // rows stage A runs on
+  const int64_t Bq = mb ? c->mb.nq : B;        // rows stage A runs on
   const int64_t Bt = mb ? c->mb.rows : B;      // rows of the candidate tables
   const int64_t Bi = mb ? c->mb.batch : B;     // rows one iteration works on
-  c->S = knn_pool_size(c->K);
   HIPCHK(c, hipEventRecord(c->prof.ev[0], c->stream));
-  if (const int rc = ensure_target_layout(c)) return rc;
-  if (c->sa.knn_variant == 3) {
-    HIPCHK(c, c->sa.fail_count.ensure(1));   // svnicp_get_knn_fallbacks: the brute-force kernel has none (cleared by the begin kernel below)
-  } else if (c->sa.knn_variant != 0) {
-    if (c->sa.knn_variant == 2) {
-      // survivors of the f32 pre-filter: 512 slots per query (median 127 at C3) + a shared arena of 512-slot chunks for the
-      // heavy tail (C3: 0.4 % of the queries, 0.17 M entries; C5: 4 %, 3.1 M entries, up to 9016 per query)
-      c->sa.scan_S2 = kTilesBase + kTilesChunks * kTilesChunk;
-      c->sa.arena_cap = (int)std::max<int64_t>(32768, Bq / 4);
-      HIPCHK(c, c->sa.pool2.ensure((size_t)Bq * kTilesBase));
-      HIPCHK(c, c->sa.arena.ensure((size_t)c->sa.arena_cap * kTilesChunk));
-      HIPCHK(c, c->sa.chunk_tab.ensure(tiles_chunk_tab_words(Bq)));
-    } else {
-      HIPCHK(c, c->sa.pool2.ensure((size_t)Bq * c->sa.scan_S2));
-    }
-    HIPCHK(c, c->sa.fail_list.ensure((size_t)Bq));
-    HIPCHK(c, c->sa.fail_count.ensure(1));
-    HIPCHK(c, c->sa.fail_tau.ensure((size_t)Bq));
-    HIPCHK(c, c->sa.qrec.ensure((size_t)Bq * 6));  // 48-byte records
-    HIPCHK(c, c->sa.pool_d.ensure((size_t)kFallbackGrid * 4 * kFallbackQW * c->S));   // fallback rows only
-    HIPCHK(c, c->sa.pool_i.ensure((size_t)kFallbackGrid * 4 * kFallbackQW * c->S));
-    c->sa.sliced_max = c->tune.fallback_sliced_max >= 0 ? c->tune.fallback_sliced_max : kFallbackSlicedMax;  // 0 forces the list-mode fallback
-    if (c->sa.sliced_max > kFallbackSlicedMax) c->sa.sliced_max = kFallbackSlicedMax;
-    if (c->sa.sliced_max > 0) {
-      HIPCHK(c, c->sa.sl_d.ensure((size_t)c->sa.sliced_max * knn_slice_count(c->K) * c->K));
-      HIPCHK(c, c->sa.sl_i.ensure((size_t)c->sa.sliced_max * knn_slice_count(c->K) * c->K));
-    }
-  } else {
-    HIPCHK(c, c->sa.pool_d.ensure((size_t)Bq * c->S));
-    HIPCHK(c, c->sa.pool_i.ensure((size_t)Bq * c->S));
-  }
-  HIPCHK(c, c->sa.cand_idx.ensure((size_t)Bq * c->K));   // mini-batch: the candidates of the unique drawn rows
-  HIPCHK(c, c->sa.cand_d2.ensure((size_t)Bq * c->K));
+  // stage A: kernel, scratch for every search of this registration (its own, the normal pass, correspondence = full), layout
+  if (const int rc = c->sa.begin(c, stage_a_env(c), Bq, c->K, {c->K, normal_pass_due(c) ? c->pl.normal_k : c->K, c->tune.full_corr ? 1 : c->K})) return rc;
   if (mb) {
     HIPCHK(c, c->mb.idx.ensure((size_t)Bt)); HIPCHK(c, c->mb.flag.ensure((size_t)B)); HIPCHK(c, c->mb.pos.ensure((size_t)B));
     HIPCHK(c, c->mb.bsum.ensure((size_t)minibatch_scan_blocks(B))); HIPCHK(c, c->mb.ctl.ensure(2));
@@ -704,7 +611,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
     add(c->st.uctl.p, update_uctl_doubles(P) * sizeof(double));
     add(c->st.history.p, (size_t)(I > 0 ? I : 1) * 6 * P * sizeof(float));
     add(c->sb.ambig.p, 2 * sizeof(int));
-    if (c->sa.knn_variant == 3) add(c->sa.fail_count.p, sizeof(int));
+    if (c->sa.plan.kernel == KnnKernel::Brute) add(c->sa.fail_count.p, sizeof(int));
     HIPCHK(c, c->st.small_bar.ensure(8));
     add(c->st.small_bar.p, 8 * sizeof(unsigned int));
     if (c->prm.mode == SVNICP_MODE_SVGD) add(c->st.opt.p, (size_t)P * 18 * sizeof(double));
@@ -722,57 +629,6 @@ int svnicp_align_begin(svnicp_ctx* c) {
   c->run.began = true;
   c->st.finish_seen = false;
   c->run.have_result = false;
-  return SVNICP_OK;
-}
-
-// redo the queries listed in fail_list: few -> target-sliced scan + merge, many -> one wave per two queries
-static hipError_t launch_fallback(svnicp_ctx* c, KnnArgs a) {
-  a.qlist = c->sa.fail_list.p; a.qlist_count = c->sa.fail_count.p; a.list_grid = kFallbackGrid; a.list_qw = kFallbackQW;
-  a.slice_max_queries = c->sa.sliced_max; a.slices = 0;
-  hipError_t e = launch_knn_topk(a, c->stream);  // returns at once unless the list is longer than slice_max_queries
-  if (e != hipSuccess || c->sa.sliced_max <= 0) return e;
-  a.slices = knn_slice_count(a.K);
-  a.merge_n = 1;
-  while (a.merge_n < a.slices * a.K) a.merge_n <<= 1;
-  a.sl_d = c->sa.sl_d.p; a.sl_i = c->sa.sl_i.p;
-  e = launch_knn_topk(a, c->stream);
-  if (e != hipSuccess) return e;
-  return launch_knn_merge_slices(a, c->stream);
-}
-
-// option debug: cycle counters of the stage-A kernels and of the Stein step, kept out of the launch sequences
-constexpr size_t kDbgPhaseWaves = 65536;   // per-wave records dbg.phase has room for, behind its 8 totals
-
-// (allocate and) clear the totals and `waves` per-wave records for the next stage-A launch
-static int clear_dbg_phase(svnicp_ctx* c, size_t waves) {
-  HIPCHK(c, c->dbg.phase.ensure(8 + 8 * kDbgPhaseWaves));
-  HIPCHK(c, hipMemsetAsync(c->dbg.phase.p, 0, (8 + 8 * waves) * sizeof(unsigned long long), c->stream));
-  return SVNICP_OK;
-}
-
-// download and print what the stage-A kernel just launched on `n` queries has counted (brute force or Morton tiles)
-static int print_stage_a_phases(svnicp_ctx* c, int64_t n, size_t dbg_waves) {
-  std::vector<unsigned long long> h(8 + 8 * dbg_waves);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->dbg.phase.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->sa.knn_variant == 3) {
-    const int qb = c->tune.brute_qb > 0 ? c->tune.brute_qb : knn_brute_queries_per_block(n, c->num_cus);
-    const double nwg = (double)((n + qb - 1) / qb);
-    fprintf(stderr, "[svnicp] k_knn_brute (%d queries per workgroup) thread-0 cycles per workgroup: pass A %.0f, bound %.0f, pass B %.0f, general path %.0f, rank + write %.0f\n",
-            qb, h[0] / nwg, h[1] / nwg, h[2] / nwg, h[3] / nwg, h[4] / nwg);
-    return SVNICP_OK;
-  }
-  fprintf(stderr, "[svnicp] k_knn_tiles wave cycles: rank %llu seed %llu scan %llu barrier waits + hand-over %llu | counts: seed tiles %llu scan tiles %llu scan (query, tile) pairs %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-  // per-wave records of k_knn_seed: [0] rank (wave 0 of a group only) [1] seed [3] barrier waits [5] tile loop [6] K-th bisection
-  auto column = [&](const char* tag, int col, unsigned long long floor_) {
-    std::vector<unsigned long long> v;
-    for (size_t w = 0; w < dbg_waves; ++w) { const unsigned long long x = h[8 + 8 * w + col]; if (x >= floor_) v.push_back(x); }
-    if (v.empty()) return;
-    std::sort(v.begin(), v.end());
-    fprintf(stderr, "[svnicp]   seed kernel %-12s n %6zu  p50 %8llu  p90 %8llu  p99 %8llu  max %8llu cycles\n", tag, v.size(), v[v.size() / 2],
-            v[v.size() * 9 / 10], v[v.size() * 99 / 100], v.back());
-  };
-  column("rank", 0, 5000); column("seed", 1, 1); column("tile loop", 5, 1); column("bisection", 6, 1); column("waits", 3, 0);
   return SVNICP_OK;
 }
 
@@ -798,80 +654,6 @@ static int print_update_phases(svnicp_ctx* c, bool persistent) {
   return SVNICP_OK;
 }
 
-// exact top-K of pose·qsrc[b_lo, b_hi) against the whole target into out_idx / out_d2 ([rows][K]); K = the context's K for
-// stage A, K = 1 for the per-particle search of correspondence = full (there the seeded-scan variant, whose plan is built
-// for the context's K, is not used)
-static int stage_a(svnicp_ctx* c, const double* qsrc, const Pose0& pose, int K, int32_t* out_idx, double* out_d2, int64_t b_lo,
-                   int64_t b_hi) {
-  KnnArgs a{};
-  a.src = qsrc; a.pose = pose; a.tx = c->cloud.tx.p; a.ty = c->cloud.ty.p; a.tz = c->cloud.tz.p; a.torig = c->cloud.torig.p;
-  a.M = c->M; a.Mp = c->Mp; a.b_lo = b_lo; a.b_hi = b_hi; a.K = K; a.S = knn_pool_size(K);
-  a.pool_d = c->sa.pool_d.p; a.pool_i = c->sa.pool_i.p; a.out_idx = out_idx; a.out_d2 = out_d2;
-  if (c->sa.knn_variant == 3) {
-    KnnBruteArgs k{};
-    k.src = qsrc; k.pose = pose; k.tgt = c->cloud.tgt.p; k.M = c->M; k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.out_idx = out_idx; k.out_d2 = out_d2;
-    if (c->tune.debug) {
-      if (const int rc = clear_dbg_phase(c, 0)) return rc;
-      k.phase_cycles = c->dbg.phase.p;
-    }
-    HIPCHK(c, launch_knn_brute(k, c->num_cus, c->tune.brute_qb, c->stream));
-    if (c->tune.debug)
-      if (const int rc = print_stage_a_phases(c, b_hi - b_lo, 0)) return rc;
-  } else if (c->sa.knn_variant == 2) {
-    const int64_t n = b_hi - b_lo;
-    if (n > 0) {
-      HIPCHK(c, launch_morton_order(qsrc, b_lo, n, 1, pose, c->sa.bbox.p, c->sa.keys_a.p, c->sa.keys_b.p, c->sa.vals_a.p,
-                                    c->sa.qorder.p + b_lo, c->sa.sort_tmp.p, c->sa.sort_tmp_bytes, c->stream));
-      KnnTilesArgs k{};
-      k.src = qsrc; k.pose = pose; k.qorder = c->sa.qorder.p + b_lo;
-      k.tx = c->cloud.tx.p; k.ty = c->cloud.ty.p; k.tz = c->cloud.tz.p; k.txf = c->cloud.txf.p; k.tyf = c->cloud.tyf.p; k.tzf = c->cloud.tzf.p;
-      k.torig = c->cloud.torig.p; k.tile_box = c->sa.tile_box.p; k.emax_bits = c->cloud.emax.p;
-      k.M = c->M; k.Mp = c->Mp; k.n_tiles = (int)(c->Mp / 512); k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = c->sa.scan_S2;
-      k.pool = c->sa.pool2.p; k.out_idx = out_idx; k.out_d2 = out_d2;
-      k.arena = c->sa.arena.p; k.chunk_tab = c->sa.chunk_tab.p; k.arena_cap = c->sa.arena_cap; k.tab_rows = c->sa.qrows;
-      k.scan_split = c->tune.scan_split == 4 ? 4 : 8;
-      {  // a small stride coprime to n_groups: 17 sweeps over the curve (C3 1.04 -> 0.98 ms, C5 1.83 -> 1.65 ms against natural order)
-        const unsigned int ng = (unsigned int)((n + 63) / 64);
-        unsigned int st = c->tune.group_stride > 0 ? (unsigned int)c->tune.group_stride : 17u;
-        auto gcd = [](unsigned int x, unsigned int y) { while (y) { const unsigned int t = x % y; x = y; y = t; } return x; };
-        while (st > 1 && gcd(st, ng) != 1) st += 2;
-        if (ng <= 2 || st >= ng) st = 1;
-        k.group_stride = st;
-      }
-      HIPCHK(c, hipMemsetAsync(c->sa.chunk_tab.p, 0xff, tiles_chunk_tab_words(c->sa.qrows) * sizeof(int32_t), c->stream));
-      k.fail_list = c->sa.fail_list.p; k.fail_count = c->sa.fail_count.p; k.fail_tau = c->sa.fail_tau.p; k.qrec = c->sa.qrec.p;
-      a.qthr = c->sa.fail_tau.p;
-      if (c->prm.record_trace) { HIPCHK(c, c->sa.stat_n.ensure((size_t)c->B)); k.stat_n = c->sa.stat_n.p; }
-      HIPCHK(c, hipMemsetAsync(c->sa.fail_count.p, 0, sizeof(int), c->stream));
-      const size_t dbg_waves = (size_t)((n + 63) / 64) * 4;   // seed kernel: four waves per 64-query group
-      const bool dbg = c->tune.debug && dbg_waves <= kDbgPhaseWaves;   // larger launches are simply not instrumented
-      if (dbg) {
-        if (const int rc = clear_dbg_phase(c, dbg_waves)) return rc;
-        k.phase_cycles = c->dbg.phase.p;
-      }
-      HIPCHK(c, launch_knn_tiles(k, c->stream));
-      if (dbg)
-        if (const int rc = print_stage_a_phases(c, n, dbg_waves)) return rc;
-      HIPCHK(c, launch_fallback(c, a));
-    }
-  } else if (c->sa.knn_variant == 1 && K == c->K) {   // f32 pre-filter (knn_scan.hip) with knn_topk.hip as fallback
-    KnnScanArgs k{};
-    k.src = qsrc; k.pose = pose; k.tx = c->cloud.tx.p; k.ty = c->cloud.ty.p; k.tz = c->cloud.tz.p;
-    k.txf = c->cloud.txf.p; k.tyf = c->cloud.tyf.p; k.tzf = c->cloud.tzf.p; k.torig = c->cloud.torig.p; k.emax_bits = c->cloud.emax.p;
-    k.M = c->M; k.Mp = c->Mp; k.Ms = c->sa.scan_Ms; k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = c->sa.scan_S2;
-    k.seed_rank = c->sa.scan_rank; k.pool = c->sa.pool2.p; k.out_idx = out_idx; k.out_d2 = out_d2;
-    k.fail_list = c->sa.fail_list.p; k.fail_count = c->sa.fail_count.p;
-    HIPCHK(c, hipMemsetAsync(c->sa.fail_count.p, 0, sizeof(int), c->stream));
-    HIPCHK(c, launch_knn_scan(k, c->stream));
-    // redo the (rare) queries whose seeded threshold was too tight: streaming kernel, list mode
-    HIPCHK(c, launch_fallback(c, a));
-  } else {
-    if (c->sa.knn_variant != 0) return fail(c, SVNICP_ERR_INVALID, "correspondence = full needs knn_count <= 128 (Morton-tile stage A) or knn = v1");
-    HIPCHK(c, launch_knn_topk(a, c->stream));
-  }
-  return SVNICP_OK;
-}
-
 // plane mode, end of svnicp_align_begin: the per-registration buffers, and the target's normals when none were supplied and
 // the ones at hand were not estimated from this target with this normal_k.  The neighbours come from stage A itself (target
 // as the query cloud, identity pose, K = normal_k) in blocks of the rows its scratch is sized for.
@@ -883,23 +665,19 @@ static int prepare_plane(svnicp_ctx* c) {
   HIPCHK(c, c->pl.stats.ensure((size_t)c->P * 2));
   HIPCHK(c, hipMemsetAsync(c->pl.stats.p, 0, (size_t)c->P * 2 * sizeof(double), c->stream));
   const int kn = c->pl.normal_k;
-  if (c->pl.supplied || (c->pl.estimated && c->pl.est_k == kn)) return SVNICP_OK;
-  if (c->sa.knn_variant == 1)
+  if (!normal_pass_due(c)) return SVNICP_OK;
+  if (!c->sa.plan.can_search(kn))
     return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the seeded-scan stage A (option knn=v2, or a target beyond the tile kernel's range) cannot "
                                        "search with normal_k neighbours: supply the normals (svnicp_set_target_normals)");
-  const int64_t M = c->M, rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.qrows, M));
+  const int64_t M = c->M, rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.plan.rows, M));
   HIPCHK(c, c->pl.rec.ensure((size_t)M * 6));
   HIPCHK(c, c->pl.nbr.ensure((size_t)rows * kn));
   HIPCHK(c, c->pl.nbr_d2.ensure((size_t)rows * kn));
-  if (c->sa.knn_variant != 3 && c->sa.knn_variant != 0 && c->sa.sliced_max > 0) {   // the sliced fallback's lists are sized by K
-    HIPCHK(c, c->sa.sl_d.ensure((size_t)c->sa.sliced_max * knn_slice_count(kn) * kn));
-    HIPCHK(c, c->sa.sl_i.ensure((size_t)c->sa.sliced_max * knn_slice_count(kn) * kn));
-  }
   Pose0 ident{};
   ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
   for (int64_t lo = 0; lo < M; lo += rows) {
     const int64_t n = std::min<int64_t>(rows, M - lo);
-    if (const int rc = stage_a(c, c->cloud.tgt.p + 3 * lo, ident, kn, c->pl.nbr.p, c->pl.nbr_d2.p, 0, n)) return rc;
+    if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.tgt.p + 3 * lo, ident, kn, c->pl.nbr.p, c->pl.nbr_d2.p, 0, n)) return rc;
     HIPCHK(c, launch_target_normals(c->cloud.tgt.p, M, c->pl.nbr.p, lo, n, kn, c->pl.rec.p, c->stream));
   }
   c->pl.estimated = true; c->pl.est_k = kn;
@@ -922,7 +700,7 @@ int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
     m.src = c->cloud.src.p; m.src_u = c->mb.src_u.p; m.n_q = c->mb.nq;
     HIPCHK(c, prof_begin(c, KC_KNN));
     HIPCHK(c, launch_minibatch_draw_compact(m, c->stream));
-    const int rc = stage_a(c, c->mb.src_u.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, 0, c->mb.nq);
+    const int rc = c->sa.search(c, stage_a_env(c), c->mb.src_u.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, 0, c->mb.nq);
     if (rc) return rc;
     HIPCHK(c, launch_minibatch_expand(m, c->sa.cand_idx.p, c->K, c->mb.src.p, c->mb.cand.p, c->stream));
     HIPCHK(c, prof_end(c));
@@ -931,13 +709,8 @@ int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
     return SVNICP_OK;
   }
   HIPCHK(c, prof_begin(c, KC_KNN));
-  const int rc = stage_a(c, c->cloud.src.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, b_lo, b_hi);
-  if (rc) return rc;
-  if (c->tune.full_corr && c->sa.knn_variant != 0 && c->sa.knn_variant != 3) {   // svnicp_get_knn_fallbacks / _rows describe STAGE A, not the last particle's K = 1 search
-    HIPCHK(c, c->sa.stage_fail_count.ensure(1)); HIPCHK(c, c->sa.stage_fail_list.ensure((size_t)c->B));
-    HIPCHK(c, hipMemcpyAsync(c->sa.stage_fail_count.p, c->sa.fail_count.p, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sa.stage_fail_list.p, c->sa.fail_list.p, (size_t)c->B * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-  }
+  if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.src.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, b_lo, b_hi)) return rc;
+  if (const int rc = c->sa.keep_stage_fallbacks(c, stage_a_env(c))) return rc;
   HIPCHK(c, prof_end(c));
   return SVNICP_OK;
 }
@@ -1042,6 +815,7 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
     // correspondence = full (the reference's get_correspondence, SVGDICP.cpp:274-298): every particle's transformed source
     // against the WHOLE target, K = 1 — P exact nearest-neighbour searches per iteration through the stage-A machinery
     if (c->sb.plan.f32 != 3) return fail(c, SVNICP_ERR_INVALID, "correspondence = full needs the split stage B (accum = split, more than 8 particles or knn_count <= 128)");
+    if (!c->sa.plan.can_search(1)) return fail(c, SVNICP_ERR_INVALID, "correspondence = full needs knn_count <= 128 (Morton-tile stage A) or knn = v1");
     HIPCHK(c, c->sb.full_q.ensure((size_t)c->B * 3)); HIPCHK(c, c->sb.full_d2.ensure((size_t)c->B));
     HIPCHK(c, c->sb.full_idx.ensure((size_t)c->P * c->B));
     Pose0 ident{};
@@ -1049,7 +823,7 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
     HIPCHK(c, prof_begin(c, KC_SEARCH));
     for (int p = c->shard.p_lo; p < c->shard.p_hi; ++p) {
       HIPCHK(c, launch_transform_cloud(c->cloud.src.p, c->B, c->st.Rtot.p + 12 * (size_t)p, c->sb.full_q.p, c->st.ctl.p, c->stream));
-      const int rc = stage_a(c, c->sb.full_q.p, ident, 1, c->sb.full_idx.p + (size_t)p * c->B, c->sb.full_d2.p, 0, c->B);
+      const int rc = c->sa.search(c, stage_a_env(c), c->sb.full_q.p, ident, 1, c->sb.full_idx.p + (size_t)p * c->B, c->sb.full_d2.p, 0, c->B);
       if (rc) return rc;
     }
     HIPCHK(c, prof_end(c));
@@ -1323,30 +1097,31 @@ int svnicp_get_iterations_run(svnicp_ctx* c, int* out) {
 int svnicp_get_knn_fallbacks(svnicp_ctx* c, int* out) {
   CTX_CHECK(c);
   if (!c->run.have_candidates) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
-  if (c->sa.knn_variant == 0) { *out = -1; return SVNICP_OK; }
-  return fetch(c, out, (c->tune.full_corr && c->sa.stage_fail_count.p) ? c->sa.stage_fail_count.p : c->sa.fail_count.p, sizeof(int));
+  const int* count = c->sa.fallback_count(c->tune);
+  if (!count) { *out = -1; return SVNICP_OK; }
+  return fetch(c, out, count, sizeof(int));
 }
 
 int svnicp_get_knn_fallback_rows(svnicp_ctx* c, int32_t* out, int cap, int* n_out) {
   CTX_CHECK(c);
   if (!c->run.have_candidates || !n_out) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
   *n_out = 0;
-  if (c->sa.knn_variant == 0) return SVNICP_OK;
-  const bool snap = c->tune.full_corr && c->sa.stage_fail_count.p;
+  const int* count = c->sa.fallback_count(c->tune);
+  if (!count) return SVNICP_OK;
   int n = 0;
-  int rc = fetch(c, &n, snap ? c->sa.stage_fail_count.p : c->sa.fail_count.p, sizeof(int));
+  int rc = fetch(c, &n, count, sizeof(int));
   if (rc) return rc;
   *n_out = n;
   if (n > cap) n = cap;
-  if (n > 0 && out) return fetch(c, out, snap ? c->sa.stage_fail_list.p : c->sa.fail_list.p, (size_t)n * 4);
+  if (n > 0 && out) return fetch(c, out, c->sa.fallback_rows(c->tune), (size_t)n * 4);
   return SVNICP_OK;
 }
 
 int svnicp_get_knn_survivors(svnicp_ctx* c, int32_t* outB) {
   CTX_CHECK(c);
-  if (!c->run.have_candidates || c->sa.knn_variant != 2 || !c->prm.record_trace || !c->sa.stat_n.p)
-    return fail(c, SVNICP_ERR_INVALID, "svnicp_get_knn_survivors: needs record_trace and the pruned stage-A kernel");
-  return fetch(c, outB, c->sa.stat_n.p, (size_t)c->B * 4);
+  const int32_t* n = c->run.have_candidates ? c->sa.survivors(c->prm.record_trace != 0) : nullptr;
+  if (!n) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_knn_survivors: needs record_trace and the pruned stage-A kernel");
+  return fetch(c, outB, n, (size_t)c->B * 4);
 }
 
 int svnicp_get_ambiguous_steps(svnicp_ctx* c, int* out) {

@@ -1,6 +1,7 @@
 // kernels.hpp — argument blocks and host launchers of the HIP kernels (internal to libsvnicp_hip.so)
 #pragma once
 #include "device_math.hpp"
+#include "stage_a_plan.hpp"
 
 namespace svnicp {
 
@@ -29,10 +30,7 @@ struct KnnArgs {
   int32_t* sl_i;
   const double* qthr;  // sliced list mode, optional: starting threshold of each listed query (from k_knn_tiles)
 };
-int knn_pool_size(int K);
-int knn_slice_count(int K);
 hipError_t launch_knn_merge_slices(const KnnArgs& a, hipStream_t st);
-int64_t knn_padded_targets(int64_t M);
 
 // ---------------- Stage A for small registrations (knn_brute.hip) ----------------
 struct KnnBruteArgs {
@@ -46,7 +44,6 @@ struct KnnBruteArgs {
   double* out_d2;      // [B][K]
   unsigned long long* phase_cycles;   // optional [8]: thread-0 cycles per phase, summed over the workgroups (option debug)
 };
-bool knn_brute_applicable(int64_t B, int64_t M, int K);
 int knn_brute_queries_per_block(int64_t n, int num_cus);
 // queries_per_block: 0 = knn_brute_queries_per_block(n, num_cus); 1..6 = as given (option brute_qb, A/B)
 hipError_t launch_knn_brute(const KnnBruteArgs& a, int num_cus, int queries_per_block, hipStream_t st);
@@ -68,14 +65,11 @@ struct KnnScanArgs {
   int32_t* fail_list;             // [B]
   int* fail_count;
 };
-bool knn_scan_plan(int64_t Mp, int K, int64_t* Ms, int* seed_rank, int* S2);
 hipError_t launch_targets_soa2(const double* tgt, int64_t M, int64_t Mp, double* tx, double* ty, double* tz,
                                float* txf, float* tyf, float* tzf, int32_t* torig, unsigned long long* emax_bits,
                                hipStream_t st);
 hipError_t launch_knn_scan(const KnnScanArgs& a, hipStream_t st);
 hipError_t launch_knn_topk(const KnnArgs& a, hipStream_t st);
-hipError_t launch_build_table(const int32_t* idx, int64_t n_entries, const double* tgt, double* table,
-                              hipStream_t st);
 
 // ---------------- Stage A pruned variant (spatial_prep.hip, knn_tiles.hip) ----------------
 struct KnnTilesArgs {
@@ -107,8 +101,6 @@ struct KnnTilesArgs {
   void* qrec;         // [B] 48-byte per-query records (position, threshold, survivor count) between the two kernels
   double* fail_tau;   // optional [B]: a valid threshold (>= K-th distance) of each failed query, +inf if none
 };
-constexpr int kTilesBase = 512, kTilesChunk = 512, kTilesChunks = 31;   // 512 + 31 * 512 = 16384 survivors per query at most
-bool knn_tiles_applicable(int64_t Mp, int K);
 hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st);
 size_t sort_temp_bytes(size_t n);
 hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, hipStream_t st);
@@ -168,7 +160,7 @@ constexpr int kSmallChainBlocks = 32;
 // accumulation kernel (falls back to 1 when K > 128 or the shard has <= 8 particles)
 // test / profiling knobs of a context (svnicp_set_option); the defaults are the product configuration
 struct Tuning {
-  int knn = -1;                  // stage A kernel: -1 automatic, 0 streaming only (v1), 1 seeded scan (v2), 2 brute force (small sizes), 3 Morton tiles even where brute force applies
+  KnnOption knn;                 // stage A kernel: automatic, or v1 | v2 | tiles | brute (stage_a_plan.hpp: plan_stage_a)
   int fallback_sliced_max = -1;  // stage A: failed queries redone by target slices up to this many (-1 default)
   int accum = 3;                 // stage B: 0 f64 baseline, 1 f32 VALU search (fused), 3 search + accumulate kernels
   int update_fused = 0;          // Stein update: 1 = one fused kernel for 2 <= P <= fused_update_max_p

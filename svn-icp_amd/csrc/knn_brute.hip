@@ -442,10 +442,7 @@ __global__ __launch_bounds__(kNTB) void k_knn_brute(KnnBruteArgs a) {
 
 }  // namespace
 
-// the sizes this kernel is for: every pair is scored twice (float32)
-bool knn_brute_applicable(int64_t B, int64_t M, int K) {
-  return K >= 1 && K <= 128 && B >= 1 && M >= 1 && M < (1ll << 31) && (double)B * (double)M <= 268435456.0;   // 2^28 pairs (2.4e8: 0.20 ms against 0.37 ms for the tile chain with its sorts; 5.4e8: 0.41 against 0.42)
-}
+static_assert(kMatrixKMax <= kCap, "knn_brute_applicable (stage_a_plan.hpp): the K nearest must fit a query's pool");
 
 template <int QB>
 static hipError_t launch_qb(const KnnBruteArgs& a, int64_t n, hipStream_t st) {

@@ -319,7 +319,7 @@ __global__ void k_targets_soa2(const double* __restrict__ tgt, int64_t M, int64_
 
 }  // namespace
 
-int64_t knn_scan_padded_targets(int64_t M) { return ((M + STEP - 1) / STEP) * STEP; }
+static_assert(STEP == kTileSlots, "knn_scan_plan (stage_a_plan.hpp) counts in wave steps of this kernel");
 
 hipError_t launch_targets_soa2(const double* tgt, int64_t M, int64_t Mp, double* tx, double* ty, double* tz,
                                float* txf, float* tyf, float* tzf, int32_t* torig, unsigned long long* emax_bits,
@@ -332,24 +332,6 @@ hipError_t launch_targets_soa2(const double* tgt, int64_t M, int64_t Mp, double*
   hipLaunchKernelGGL(k_targets_soa2, dim3((unsigned)nb), dim3(256), 0, st, tgt, M, Mp, bits, tx, ty, tz, txf, tyf, tzf,
                      torig, emax_bits);
   return hipGetLastError();
-}
-
-// seed parameters: sample Ms ≈ Mp·12/K slots (a multiple of STEP), threshold = lane-minimum of rank
-// ≈ 2.6·K·Ms/Mp.  Returns false when the fast variant does not apply (large K, small M).
-bool knn_scan_plan(int64_t Mp, int K, int64_t* Ms, int* seed_rank, int* S2) {
-  if (K > 200 || Mp < 16 * STEP || (Mp % STEP) != 0) return false;
-  double F = 12.5 / (double)K;
-  if (F > 0.25) F = 0.25;
-  int64_t ms = (int64_t)((double)Mp * F / STEP + 0.5) * STEP;
-  if (ms < STEP) ms = STEP;
-  if (ms > Mp) ms = Mp;
-  int j = (int)(2.6 * (double)K * (double)ms / (double)Mp + 0.5);
-  if (j < 4) j = 4;
-  if (j > 44) j = 44;
-  *Ms = ms;
-  *seed_rank = j - 1;
-  *S2 = 1024;
-  return true;
 }
 
 hipError_t launch_knn_scan(const KnnScanArgs& a, hipStream_t st) {

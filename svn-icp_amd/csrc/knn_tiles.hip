@@ -721,7 +721,7 @@ __global__ __launch_bounds__(256) void k_knn_select(KnnTilesArgs a) {
 
 }  // namespace
 
-bool knn_tiles_applicable(int64_t Mp, int K) { return K <= 128 && Mp >= 16 * STEP && (Mp % STEP) == 0 && Mp / STEP <= MAX_TILES; }
+static_assert(STEP == kTileSlots && MAX_TILES == kMaxTiles, "knn_tiles_applicable (stage_a_plan.hpp) speaks of this kernel's tiles");
 
 hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st) {
   const int64_t nq = a.b_hi - a.b_lo;

@@ -269,25 +269,9 @@ __global__ __launch_bounds__(64) void k_knn_merge_slices(KnnArgs a) {
   }
 }
 
-// target_batch = index_select(target, sourceKNN_idx) (SVGDICP.cpp:191-193), ONE copy [B][K][3]
-__global__ void k_build_table(const int32_t* __restrict__ idx, int64_t n_entries, const double* __restrict__ tgt,
-                              double* __restrict__ table) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_entries) return;
-  const int64_t i = idx[e];
-  table[3 * e] = tgt[3 * i];
-  table[3 * e + 1] = tgt[3 * i + 1];
-  table[3 * e + 2] = tgt[3 * i + 2];
-}
-
 }  // namespace
 
-int knn_pool_size(int K) {
-  int S = 256;
-  while (S < K + 128) S <<= 1;
-  return S;
-}
-int64_t knn_padded_targets(int64_t M) { return ((M + 511) / 512) * 512; }  // multiple of both kernels' steps
+static_assert(kTileSlots % STEP == 0, "knn_padded_targets pads the target to whole wave steps of this kernel");
 
 hipError_t launch_knn_topk(const KnnArgs& a, hipStream_t st) {
   int64_t nb;
@@ -309,13 +293,6 @@ hipError_t launch_knn_topk(const KnnArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-int knn_slice_count(int K) {  // slices x K entries must fit the merge kernel's 8192-entry LDS sort
-  int kp = 1;
-  while (kp < K) kp <<= 1;
-  int ns = 8192 / kp;
-  return ns > 64 ? 64 : (ns < 1 ? 1 : ns);
-}
-
 hipError_t launch_knn_merge_slices(const KnnArgs& a, hipStream_t st) {
   const size_t smem = (size_t)a.slices * a.K * (sizeof(double) + sizeof(int));
   if (smem > 64 * 1024) {
@@ -325,14 +302,6 @@ hipError_t launch_knn_merge_slices(const KnnArgs& a, hipStream_t st) {
   }
   const int nb = a.slice_max_queries < 512 ? a.slice_max_queries : 512;
   hipLaunchKernelGGL(k_knn_merge_slices, dim3(nb > 0 ? nb : 1), dim3(64), smem, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_build_table(const int32_t* idx, int64_t n_entries, const double* tgt, double* table,
-                              hipStream_t st) {
-  if (n_entries <= 0) return hipSuccess;
-  const int64_t nb = (n_entries + 255) / 256;
-  hipLaunchKernelGGL(k_build_table, dim3((unsigned)nb), dim3(256), 0, st, idx, n_entries, tgt, table);
   return hipGetLastError();
 }
 

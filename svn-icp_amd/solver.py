@@ -195,6 +195,21 @@ class _SolverBase:
         self._check(self._L.svnicp_set_particles(self._h, init.ctypes.data_as(C.POINTER(C.c_double)), self._P),
                     "svnicp_set_particles")
 
+    def set_source(self, new_cloud):
+        """svnicp_set_source: a new source scan against the target, particles and initial mean already set (host array
+        or CUDA tensor)."""
+        if _is_torch_cuda(new_cloud):
+            import torch
+            src = new_cloud.to(torch.float64).contiguous()
+            torch.cuda.current_stream(src.device).synchronize()
+            self._keep_source = src                    # as in add_cloud: held until the next call replaces it
+            rc = self._L.svnicp_set_source(self._h, C.c_void_p(src.data_ptr()), src.shape[0], 1)
+        else:
+            src = np.ascontiguousarray(np.asarray(new_cloud, np.float64).reshape(-1, 3))
+            rc = self._L.svnicp_set_source(self._h, src.ctypes.data_as(C.c_void_p), src.shape[0], 0)
+        self._check(rc, "svnicp_set_source")
+        self._B = src.shape[0]
+
     def add_cloud_device_target(self, new_cloud, target_devptr: int, M: int, init_pose):
         """add_cloud with a host source scan and a target that already lives in HBM (DeviceVoxelHashMap.get_map):
         the source goes over PCIe, the target is copied device-to-device."""

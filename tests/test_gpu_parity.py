@@ -305,6 +305,28 @@ def test_stage_a_variants_bit_exact(hip, orc, B, M, K):
         assert fbs["brute"] == 0 and fbs["default"] == 0    # these sizes default to the brute-force kernel, which never falls back
 
 
+def test_source_grows_on_an_unchanged_target(hip, orc):
+    """svnicp_set_source alone, with more points than before, on a target that stays: the target's Morton layout is kept,
+    and the query order (B entries) and the sort scratch (max(M, B) keys) must follow the new B all the same — they are
+    sized at every registration, not with the layout.  M = 8192 is the smallest target the tile kernels take; B = 600
+    outgrows the query order of B = 64, B = 9000 > M outgrows the sort scratch too."""
+    K, M = 8, 8192
+    R0, t0 = hip.scans.rot_zyx(0.01, -0.02, 0.03), np.array([0.3, -0.2, 0.1])
+    src, tgt = hip.scans.random_clouds(9000, M, seed=11, extent=40.0)
+    init = np.zeros((6, 2)); init[0, 1] = 0.01
+    s = _hip_solver(hip, init, trace=False, iterations=1, lr=1.0, max_dist=1.0, knn_count=K, svn_full_grad=False)
+    s.set_option("knn", "tiles")
+    s.add_cloud(src[:64], tgt, init)
+    s.set_initial_mean((R0, t0))
+    for B in (64, 600, 9000):
+        if B != 64:
+            s.set_source(src[:B])
+        s.stein_align()
+        oi, od = orc.knn_topk(orc.transform(src[:B], R0, t0), tgt, K)
+        assert np.array_equal(s.get_candidates().astype(np.int64), oi), B
+        assert np.array_equal(s.get_candidate_dist2(), od), B
+
+
 @pytest.mark.parametrize("sliced_max,K", [(None, 50), ("0", 50), ("100", 50), (None, 128), (None, 7)])
 def test_stage_a_fallback_on_pool_overflow(hip, orc, sliced_max, K):
     """Clustered duplicates: thousands of targets at exactly the same distance overflow the

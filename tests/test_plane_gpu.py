@@ -78,16 +78,20 @@ def _solver(pkg, src, tgt, init, *, K=16, iterations=1, max_dist=1.0, lr=1.0, fu
 # ---------------------------------------------------------------------------------------------
 # 1. normals
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shifted", [False, True], ids=["origin", "shifted"])
-@pytest.mark.parametrize("knn", [None, "brute", "tiles"], ids=["default", "brute", "tiles"])
-@pytest.mark.parametrize("kn", [8, 16])
-@pytest.mark.parametrize("name", ["random", "pair4k"])
-def test_estimated_normals_agree_with_the_helper(hip, orc, name, kn, knn, shifted):
+# every (cloud, normal_k, stage-A kernel, shift) at K = 16, and one search whose normal_k = 64 lists are larger than the
+# context's own K = 3 would size
+NORMAL_CASES = [pytest.param(name, kn, knn, shifted, 16, id=f"{name}-{kn}-{knn or 'default'}-{'shifted' if shifted else 'origin'}")
+                for shifted in (False, True) for knn in (None, "brute", "tiles") for kn in (8, 16) for name in ("random", "pair4k")]
+NORMAL_CASES.append(pytest.param("random", 64, "tiles", False, 3, id="random-64-tiles-origin-K3"))
+
+
+@pytest.mark.parametrize("name,kn,knn,shifted,K", NORMAL_CASES)
+def test_estimated_normals_agree_with_the_helper(hip, orc, name, kn, knn, shifted, K):
     src, tgt = _clouds(0, name)
     off = SHIFT if shifted else 0.0
     src, tgt = src + off, tgt + off
     ref_n, ref_valid, lam = _ref_normals(orc, name, kn, shifted)
-    s = _solver(hip, src, tgt, np.zeros((6, 1)), residual="plane", kn=kn, options=(("knn", knn),) if knn else ())
+    s = _solver(hip, src, tgt, np.zeros((6, 1)), K=K, residual="plane", kn=kn, options=(("knn", knn),) if knn else ())
     assert s._L.svnicp_align_begin(s.handle) == 0, s._L.svnicp_last_error(s.handle)
     n = s.get_target_normals()
     assert s.get_plane_stats(with_sums=False)[1] == 1
