@@ -97,7 +97,29 @@ int svnicp_synchronize(svnicp_ctx *ctx);
  * Split in two because the clouds and the particles are independent buffers; both are copied.  SVNICP_MEM_HOST: the
  * caller's buffer is free when the call returns.  SVNICP_MEM_DEVICE: the copy is QUEUED on the context's stream — the
  * device buffer must stay unchanged until svnicp_align has returned (or svnicp_synchronize).  svnicp_set_particles stages
- * the poses through pinned memory and does not wait for the stream either. */
+ * the poses through pinned memory and does not wait for the stream either.
+ *
+ * Non-finite and huge points.  Clouds are taken as given (svnicp_set_clouds, svnicp_set_source, svnicp_set_target): a row
+ * may hold NaN, +-inf or a finite junk coordinate such as 1e20 or 1e160 (the scan-prep, segmentation, deskew and map entry
+ * points drop such rows; these three do not).  What they do, for every stage-A kernel and every launch chain:
+ *   stage A      per query q = R0 s + t0 and target j: d2 = ((dx*dx) + dy*dy) + dz*dz in float64, unfused.  A target whose d2
+ *                is NaN is never a neighbour; any other d2, +inf included, is a number; the neighbours are the K smallest by
+ *                (d2, index); positions past the number of eligible targets hold index 0 and d2 = 0.0 (a NaN query: the
+ *                whole row).  A row's result depends on that row and the target only.  This is the reference's
+ *                knn_cpu.cpp except where a NaN distance is inserted while its heap is not yet full.
+ *   search       per iteration, strict '<' from candidate 0: a NaN first distance is never replaced, an all-NaN row keeps
+ *                candidate 0.
+ *   point        the mask is a multiplication of the rows, as in the reference (SVGDICP.cpp:331-333): a pair whose source
+ *   residual     row, transformed row or winner has a NaN or an infinite coordinate is 0 * that value = NaN, and the 22 sums
+ *                of every particle it enters are NaN (the early-stop test then never fires: all `iterations` run).  A
+ *                FINITE row whose d2 is huge or overflows to +inf is masked to exact zeros and still adds the identity
+ *                block, like any rejected row.
+ *   plane        a source row with a non-finite coordinate, a pair beyond max_dist and a winner without a normal are
+ *   residual     rejected pairs and contribute exact zeros.  Estimated normals: a target point has no normal when the
+ *                offset to one of its normal_k neighbours is NaN, infinite or too large for float32 to hold its square
+ *                (|d| >= 2^64) -- a non-finite or huge point itself never has one.
+ * A bad target row costs time, not correctness: its float32 image disables the pre-filters of the pruned kernels, and
+ * more queries take their exact fallback. */
 int svnicp_set_clouds(svnicp_ctx *ctx, const double *src_xyz, int64_t B, const double *tgt_xyz,
                       int64_t M, int mem_kind);
 int svnicp_set_particles(svnicp_ctx *ctx, const double *init_pose6xP, int P);
@@ -178,8 +200,9 @@ int svnicp_get_minibatch_rows(svnicp_ctx *ctx, int64_t out2[2]);         /* {uni
  * Normals: those of svnicp_set_target_normals, else estimated on the device when the registration begins — per target point
  * from its normal_k nearest target points, itself included (4..64; 0 = 16; stage A's exact search with the target as the
  * query cloud): covariance of the offsets, eigenvector of the smallest eigenvalue, sign unspecified (the residual does not
- * depend on it).  A point has NO normal when a neighbour is non-finite, when the largest eigenvalue l2 is 0 or when the
- * middle one l1 < 0.01 * l2 (collinear neighbourhoods: the same-ring neighbours of a sparse scan).  Estimated normals are
+ * depend on it).  A point has NO normal when the offset to a neighbour is non-finite or has |d| >= 2^64 (see
+ * svnicp_set_clouds, "non-finite and huge points"), when the largest eigenvalue l2 is 0 or when the middle one
+ * l1 < 0.01 * l2 (collinear neighbourhoods: the same-ring neighbours of a sparse scan).  Estimated normals are
  * kept until the target or normal_k changes: a second registration against the same target pays nothing.
  * SVNICP_RESIDUAL_POINT (the default) runs exactly the launches of a context that never called this.
  * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID in plane mode: SVGD mode, a partial particle shard, a

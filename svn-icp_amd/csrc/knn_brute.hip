@@ -186,11 +186,14 @@ __device__ __forceinline__ void sweep_pass(const KnnBruteArgs& a, const double (
         const float sc = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
         if (BOUND) {
           mn[q] = __builtin_fminf(mn[q], sc);
-        } else if (sc <= tau[q]) {   // (false for the NaN of a row past the end and for tau = -1 of a query that takes no part)
+        } else if (!(sc > tau[q])) {   // (false for tau = -1 of a query that takes no part, whose scores are numbers)
+          // A NaN score passes: where q' and t' are infinities of one sign (coordinates beyond float32's range on the same
+          // side of the origin) the score says nothing while the float64 d² may be a number — E = inf and tau = +inf
+          // then, and float64 decides.  The NaN of a row past the end comes here too and stops at `in`.
           const double ex = sq[q][0] - tx[u], ey = sq[q][1] - ty[u], ez = sq[q][2] - tz[u];
           const double d = (ex * ex + ey * ey) + ez * ez;   // knn_cpu.cpp:43-50 order, unfused
           const unsigned long long bits = (unsigned long long)__double_as_longlong(d);
-          if (bits <= lim[q]) {      // (a NaN's bits lie above +inf's)
+          if (in && bits <= lim[q]) {      // (a NaN's bits lie above +inf's)
             const unsigned int pos = atomicAdd(&pn[q], 1u);
             if (pos < (unsigned int)kCap) { pd[q][pos] = d; pi[q][pos] = (int)j; }
           }

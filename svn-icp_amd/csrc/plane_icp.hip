@@ -33,12 +33,16 @@ __global__ __launch_bounds__(256) void k_target_normals(const double* __restrict
   const int32_t* nb = nbr + r * kn;
   // offsets relative to the point itself: at map-frame coordinates of kilometres the differences are still exact to 1e-13 m
   double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+  // "finite" offsets are those whose square float32 can hold (|d| < 2^64): a junk return of 1e20 or 1e160 is a finite number,
+  // but its neighbourhood is the first kn targets at one rounded distance and its scatter matrix is rounding noise — such a
+  // point has no normal, like a NaN or an infinite one (include/svnicp_hip.h, "non-finite and huge points")
+  constexpr double kOffsetMax = 0x1p64;
   bool finite = true;
   for (int k = 0; k < kn; ++k) {
     int64_t j = nb[k];
     j = j < 0 ? 0 : (j >= M ? M - 1 : j);   // clamped: a corrupted list must never become a wild gather
     const double d0 = tgt[3 * j] - x0, d1 = tgt[3 * j + 1] - x1, d2 = tgt[3 * j + 2] - x2;
-    finite = finite && (fabs(d0) < __builtin_inf()) && (fabs(d1) < __builtin_inf()) && (fabs(d2) < __builtin_inf());
+    finite = finite && (fabs(d0) < kOffsetMax) && (fabs(d1) < kOffsetMax) && (fabs(d2) < kOffsetMax);   // (false for NaN)
     m0 += d0; m1 += d1; m2 += d2;
   }
   m0 /= kn; m1 /= kn; m2 /= kn;

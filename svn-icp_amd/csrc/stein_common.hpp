@@ -40,8 +40,12 @@ __device__ __forceinline__ void accumulate_point(const Pending& pd, const double
     w = wq * wq;                                        // SVNICP.cpp:122
     e0 = w * dx; e1 = w * dy; e2 = w * dz;              // SVNICP.cpp:119,123
     n0 = spts[3 * pd.pt]; n1 = spts[3 * pd.pt + 1]; n2 = spts[3 * pd.pt + 2];
-  } else if (best != best) {   // masking is a multiplication in the reference (SVGDICP.cpp:331-333): a NaN row stays NaN
-    w = best; e0 = best; e1 = best; e2 = best;
+  } else if (!(best < __builtin_huge_val())) {
+    // masking is a multiplication in the reference (SVGDICP.cpp:331-333): the row is 0·s, 0·Ts, 0·q, so a row with a NaN
+    // or an infinite coordinate stays NaN (0·inf), and with it e, |e|, w and every sum; a FINITE row whose d² overflowed is
+    // masked to exact zeros like any other
+    const double z = (0.0 * dx + 0.0 * dy) + 0.0 * dz;
+    if (z != z) { w = z; e0 = z; e1 = z; e2 = z; }
   }
   const double w0 = w * n0, w1 = w * n1, w2 = w * n2;
   acc[0] += w;

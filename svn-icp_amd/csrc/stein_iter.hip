@@ -147,10 +147,12 @@ __global__ __launch_bounds__(NT) void k_icp_single(AccumArgs a, UpdateArgs u) {
       w = wq * wq;                                      // SVNICP.cpp:122
       e0 = w * dx; e1 = w * dy; e2 = w * dz;            // SVNICP.cpp:119,123
       m0 = s0; m1 = s1; m2 = s2;
-    } else if (best != best) {
-      // the reference masks by MULTIPLYING the rows with 0 / 1 (SVGDICP.cpp:331-333): a non-finite row (a particle whose pose
-      // went NaN) stays NaN, and so does every sum it enters — k_stein_accumulate_w forms the same products
-      w = best; e0 = best; e1 = best; e2 = best;
+    } else if (!(best < __builtin_huge_val())) {
+      // the reference masks by MULTIPLYING the rows with 0 / 1 (SVGDICP.cpp:331-333): a row with a NaN or an infinite
+      // coordinate (a particle whose pose went NaN, a junk return in the cloud) stays NaN — 0·inf — and so does every sum it
+      // enters; a finite row whose d² overflowed is masked to exact zeros (accumulate_point, stein_common.hpp)
+      const double z = (0.0 * dx + 0.0 * dy) + 0.0 * dz;
+      if (z != z) { w = z; e0 = z; e1 = z; e2 = z; }
     }
     const double w0 = w * m0, w1 = w * m1, w2 = w * m2;
     acc[0] = w;

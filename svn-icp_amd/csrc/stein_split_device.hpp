@@ -632,8 +632,13 @@ __device__ __forceinline__ void accumulate_body(const AccumArgs& a, int bx, int 
     const double T2 = (s0 * Rt[6] + s1 * Rt[7] + s2 * Rt[8]) + tt[2];
     const double dx = T0 - q0, dy = T1 - q1, dz = T2 - q2;
     const double best = (dx * dx + dy * dy) + dz * dz;   // exact d² of the winner (knn_cpu.cpp:43-50 order)
-    const double mf = best < a.max_dist ? on : 0.0;       // point_filter, SVGDICP.cpp:331-333 (squared distance against max_dist)
-    const double x = mf * best;                           // 0 for a rejected row; NaN stays NaN (a non-finite point)
+    const bool in = best < a.max_dist;                    // point_filter, SVGDICP.cpp:331-333 (squared distance against max_dist)
+    const double mf = in ? on : 0.0;
+    // 0 for a rejected row, SELECTED: the reference multiplies the ROWS by the mask, not d², so a finite row whose d²
+    // overflows (a 1e160 junk return) is masked to exact zeros, where mf·best would be 0·inf.  A row with a NaN or an
+    // infinite coordinate still turns NaN as the reference's does: e = we·d below is 0·inf or 0·NaN for it, and the lane's
+    // sums are poisoned once, after the loop.
+    const double x = in ? mf * best : 0.0;
     // |e| = sqrt(x), SVNICP.cpp:120 on the masked rows: rsq seed (x + 2^-1000 keeps x = 0 finite: 0·2^500 = 0), s = x·r,
     // one coupled Newton step on (s, h = r/2), one residual step on s
     const double r0 = __builtin_amdgcn_rsq(x + 0x1p-1000);
@@ -695,6 +700,15 @@ __device__ __forceinline__ void accumulate_body(const AccumArgs& a, int bx, int 
       const double s0 = sp[0], s1 = sp[1], s2 = sp[2];
       if (!PLAIN && a.corr && valid) a.corr[(size_t)p * a.B + b] = kb[u];
       accumulate(b < blk_hi ? 1.0 : 0.0, s0, s1, s2, q[u][0], q[u][1], q[u][2]);
+    }
+  }
+  // The reference's masked row is 0·s, 0·Ts, 0·q: with a non-finite coordinate e, |e| and so w are NaN, and all 22 sums with
+  // them.  Here such a pair left NaN in the e sums only (w = 1 for a rejected row): finish the job, outside the pair loop.
+  {
+    const double t = (acc[10] + acc[11]) + acc[12];
+    if (t != t) {
+#pragma unroll
+      for (int i = 0; i < kNSums; ++i) acc[i] = t;
     }
   }
 

@@ -760,7 +760,7 @@ def test_two_particles_zero_bandwidth_goes_nan_like_the_reference(hip, orc):
     init = hip.scans.make_particles(P, seed=P) * 0.2
     cfg = dict(iterations=I, lr=1.0, max_dist=1.0, check_early_stop=False, convergence_threshold=1e-5, knn_count=K, svn_full_grad=False)
     o = orc.Solver(init, **cfg); o.add_cloud(src, tgt, init); tro = o.enable_trace(); o.stein_align()
-    for accum in ("valu", "f64"):
+    for accum in ("valu", "f64", "split"):
         s = _hip_solver(hip, init, **cfg); s.set_option("accum", accum); s.add_cloud(src, tgt, init)
         assert s.stein_align() == hip.SteinICPState.ALIGN_SUCCESS
         tr = s.get_trace()
