@@ -224,6 +224,56 @@ int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, i
 int svnicp_get_target_normals(svnicp_ctx *ctx, double *outMx3);
 int svnicp_get_plane_stats(svnicp_ctx *ctx, double *outPx2, int64_t *normal_passes);
 
+/* ---- evaluate a registration: fitness, inlier RMSE, nearest pairs (an extension: the reference returns a pose and a
+ * covariance and nothing that says whether the registration worked) -------------------------------
+ * svnicp_evaluate(ctx, R, t, max_corr_dist, out): one pose against the WHOLE target, on the device, blocking.
+ *   pose         the total pose, map <- sensor.  R and t both NULL: the last registration's result, T0 * Pose3(Rot3::Expmap(
+ *                mean[3:6]), mean[0:3]) with T0 of svnicp_set_initial_mean and mean of svnicp_get_transformation -- the
+ *                composition both pipelines apply (correction_to_pose), in both solver modes.  Only one of the two NULL, or
+ *                a non-finite entry: SVNICP_ERR_INVALID.
+ *   transformed  q = R s + t in float64, unfused: (s0*R[3i] + s1*R[3i+1] + s2*R[3i+2]) + t[i].
+ *   point
+ *   nearest      exact over the whole target, stage A's contract (svnicp_set_clouds) with K = 1: smallest (d2, index), a NaN
+ *   target       distance is never a neighbour.  The search is stage A's own, with the kernel the registration chose.
+ *   evaluated    d2 is recomputed from q and the returned target row; a row is evaluated iff q is finite and that d2 is not
+ *   rows         NaN (which also covers the contract's "index 0, d2 = 0.0" filler of a row with no eligible target).  A d2 of
+ *                +inf is evaluated and never an inlier.
+ *   inliers      evaluated rows with d2 < thr2, thr2 = max_corr_dist * max_corr_dist computed once in float64;
+ *                max_corr_dist must be > 0 and not NaN, +inf is allowed.
+ *   plane        has_normals = 1 iff the context holds normals of the current target: supplied by svnicp_set_target_normals,
+ *   figures      or estimated by an earlier plane-mode registration and not dropped since; evaluate never runs a normal pass
+ *                of its own.  A plane inlier is an inlier whose target normal n is non-zero; its residual is
+ *                r = (n0 e0 + n1 e1) + n2 e2 with e = q - p.  Independent of the residual mode the solver ran.
+ *   determinism  the same context state and arguments give bit-identical results on every call: each workgroup owns a fixed
+ *                range of rows and the records are added in an order that depends on B alone (no atomics).
+ *   when         there must be a finished registration since the source, the target, the initial mean, K, an option, the
+ *                mini-batch or the residual setting last changed (stage A's target layout and scratch belong to that
+ *                registration); otherwise SVNICP_ERR_INVALID, and svnicp_last_error names the reason.  A stage A that cannot
+ *                search with K = 1 is refused too: the seeded scan (option knn=v2) unless knn_count is 1.  Returns with the
+ *                stream synchronised and *out filled.
+ *   side         none: nothing an existing getter returns changes (svnicp_get_knn_fallbacks, _fallback_rows and _survivors
+ *   effects      keep describing the registration), and the next registration is bit for bit that of a context that never
+ *                evaluated.
+ *   sharded      a row-sharded context evaluates its own rows; the counts and the two sums add across ranks.
+ * The per-row results stay in device memory until the next svnicp_evaluate. */
+typedef struct svnicp_eval {
+  int32_t struct_size;    /* in: sizeof(svnicp_eval) */
+  int32_t has_normals;    /* 1: the context holds normals of the current target, plane figures are filled */
+  int64_t rows;           /* B, the context's source rows */
+  int64_t evaluated;      /* rows with a finite transformed point and a nearest target whose d2 is not NaN */
+  int64_t inliers;        /* evaluated rows with d2 < max_corr_dist * max_corr_dist */
+  int64_t plane_inliers;  /* inliers whose nearest target has a normal (0 without normals) */
+  double sum_d2, sum_r2;  /* over inliers; over plane_inliers */
+  double fitness;         /* inliers / rows */
+  double inlier_rmse;     /* sqrt(sum_d2 / inliers), 0 when there are none */
+  double plane_rmse;      /* sqrt(sum_r2 / plane_inliers), 0 when there are none */
+  double R[9], t[3];      /* the pose that was evaluated (row-major), also when NULL was passed */
+} svnicp_eval;
+int svnicp_evaluate(svnicp_ctx *ctx, const double R_rowmajor[9], const double t[3], double max_corr_dist, svnicp_eval *out);
+const int32_t *svnicp_eval_index_devptr(svnicp_ctx *ctx);   /* int32 [B]: nearest target row, -1 = not evaluated */
+const double *svnicp_eval_dist2_devptr(svnicp_ctx *ctx);    /* double [B]: its d2, NaN = not evaluated */
+int svnicp_get_eval_pairs(svnicp_ctx *ctx, int32_t *idxB, double *d2B);   /* host copy of the two; either may be NULL */
+
 /* ---- split-phase entry points: one process per GPU, particles sharded across ranks ----------
  * (new functionality; the reference is single-GPU).  Sequence per registration:
  *   svnicp_set_shard -> svnicp_stage_candidates(b_lo,b_hi) -> [host all-gathers rows of

@@ -31,6 +31,14 @@ class SegParamsStruct(C.Structure):
                 ("valid_line_num", C.c_int32)]
 
 
+class EvalStruct(C.Structure):
+    """struct svnicp_eval (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("rows", C.c_int64), ("evaluated", C.c_int64),
+                ("inliers", C.c_int64), ("plane_inliers", C.c_int64), ("sum_d2", C.c_double), ("sum_r2", C.c_double),
+                ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("plane_rmse", C.c_double), ("R", C.c_double * 9),
+                ("t", C.c_double * 3)]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -163,6 +171,11 @@ def load_library():
     L.svnicp_set_target_normals.argtypes = [vp, vp, C.c_int64, C.c_int]
     L.svnicp_get_target_normals.argtypes = [vp, dp]
     L.svnicp_get_plane_stats.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    L.svnicp_evaluate.argtypes = [vp, dp, dp, C.c_double, C.POINTER(EvalStruct)]
+    for name in ("svnicp_eval_index_devptr", "svnicp_eval_dist2_devptr"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = vp
+    L.svnicp_get_eval_pairs.argtypes = [vp, ip, dp]
     for name in declared_symbols():
         getattr(L, name)  # AttributeError here = the header declares a symbol the library does not export
     _lib = L

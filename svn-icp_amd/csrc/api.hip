@@ -132,6 +132,15 @@ struct PlaneState {
   DevBuf<double> partial, Hb, stats;   // [grid_x][Ppad][kPlaneSums], [P][42], [P][2]
 };
 
+// svnicp_evaluate (csrc/evaluate.hip): its own buffers, nothing of the registration's
+struct EvalState {
+  DevBuf<double> q, d2, partial, result;   // [B][3] transformed source, [B], [evaluate_blocks(B)][kEvalRecord], [kEvalResult]
+  DevBuf<int32_t> idx;                     // [B]
+  PinnedBuf<double> h_result;              // pinned [kEvalResult]
+  bool have = false;                       // idx / d2 hold the rows of an evaluation of `rows` source rows
+  int64_t rows = 0;
+};
+
 struct Trace { DevBuf<double> H, b, N, phi, h; DevBuf<int32_t> corr; };   // record_trace
 
 struct Profiling {   // timing events
@@ -168,7 +177,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb; PlaneState pl;
+  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -710,7 +719,8 @@ int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
   }
   HIPCHK(c, prof_begin(c, KC_KNN));
   if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.src.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, b_lo, b_hi)) return rc;
-  if (const int rc = c->sa.keep_stage_fallbacks(c, stage_a_env(c))) return rc;
+  if (c->tune.full_corr)   // the per-particle searches of every iteration reuse stage A's fallback list
+    if (const int rc = c->sa.keep_stage_fallbacks(c, stage_a_env(c))) return rc;
   HIPCHK(c, prof_end(c));
   return SVNICP_OK;
 }
@@ -1097,7 +1107,7 @@ int svnicp_get_iterations_run(svnicp_ctx* c, int* out) {
 int svnicp_get_knn_fallbacks(svnicp_ctx* c, int* out) {
   CTX_CHECK(c);
   if (!c->run.have_candidates) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
-  const int* count = c->sa.fallback_count(c->tune);
+  const int* count = c->sa.fallback_count();
   if (!count) { *out = -1; return SVNICP_OK; }
   return fetch(c, out, count, sizeof(int));
 }
@@ -1106,14 +1116,14 @@ int svnicp_get_knn_fallback_rows(svnicp_ctx* c, int32_t* out, int cap, int* n_ou
   CTX_CHECK(c);
   if (!c->run.have_candidates || !n_out) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
   *n_out = 0;
-  const int* count = c->sa.fallback_count(c->tune);
+  const int* count = c->sa.fallback_count();
   if (!count) return SVNICP_OK;
   int n = 0;
   int rc = fetch(c, &n, count, sizeof(int));
   if (rc) return rc;
   *n_out = n;
   if (n > cap) n = cap;
-  if (n > 0 && out) return fetch(c, out, c->sa.fallback_rows(c->tune), (size_t)n * 4);
+  if (n > 0 && out) return fetch(c, out, c->sa.fallback_rows(), (size_t)n * 4);
   return SVNICP_OK;
 }
 
@@ -1274,6 +1284,103 @@ int svnicp_get_plane_stats(svnicp_ctx* c, double* outPx2, int64_t* normal_passes
   if (!outPx2) return SVNICP_OK;
   if (!c->run.have_result || !c->pl.on) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_plane_stats: no registration with the point-to-plane residual yet");
   return fetch(c, outPx2, c->pl.stats.p, (size_t)c->P * 16);
+}
+
+// ---- evaluate a registration ----
+// Rot3::Expmap as both pipelines' correction_to_pose states it (pipeline.py / registration_pipeline.hpp: so3_exp)
+static void host_so3_exp(const double w[3], double R[9]) {
+  const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  double K2[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) K2[3 * i + j] = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
+  const double a = th < 1e-10 ? 1.0 : std::sin(th) / th, b = th < 1e-10 ? 0.5 : (1.0 - std::cos(th)) / (th * th);
+  for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * K[i] + b * K2[i];
+}
+
+int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_corr_dist, svnicp_eval* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: null result struct");
+  if (out->struct_size != (int32_t)sizeof(svnicp_eval)) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: svnicp_eval.struct_size mismatch");
+  if (!(max_corr_dist > 0.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: max_corr_dist must be positive and not NaN (+inf: every evaluated row with a finite distance is an inlier)");
+  if ((R == nullptr) != (t == nullptr)) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: R and t must both be given, or both be NULL (the last registration's result)");
+  if (R) {
+    bool finite = true;
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(R[i]);
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(t[i]);
+    if (!finite) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: the pose holds a non-finite entry");
+  }
+  if (!c->run.have_result)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: no finished registration yet (stage A's target layout and scratch belong to one)");
+  if (!c->run.have_candidates)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: the source, the target, the initial mean, K or an option changed since the last registration: "
+                                       "register again first (stage A's target layout and scratch belong to that registration)");
+  if (!c->sa.plan.can_search(1))
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: the seeded-scan stage A (option knn=v2, or a target beyond the tile kernel's range) is built "
+                                       "for knn_count neighbours and cannot search with K = 1");
+  if (const int rc = svnicp_synchronize(c)) return rc;   // an asynchronous registration has finished and its checks have run
+  EvalPose T{};
+  if (R) {
+    std::memcpy(T.R, R, sizeof T.R); std::memcpy(T.t, t, sizeof T.t);
+  } else {   // T0 * Pose3(Rot3::Expmap(mean[3:6]), mean[0:3])
+    double mean[6], Rc[9];
+    if (const int rc = fetch_stats(c, mean, 0, 6)) return rc;
+    host_so3_exp(mean + 3, Rc);
+    const double* R0 = c->pose0.R0;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) T.R[3 * i + j] = R0[3 * i] * Rc[j] + R0[3 * i + 1] * Rc[3 + j] + R0[3 * i + 2] * Rc[6 + j];
+      T.t[i] = (R0[3 * i] * mean[0] + R0[3 * i + 1] * mean[1] + R0[3 * i + 2] * mean[2]) + c->pose0.t0[i];
+    }
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(i < 9 ? T.R[i] : T.t[i - 9])) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: the last registration's result pose is not finite");
+  }
+  const int64_t B = c->B, M = c->M, nblk = evaluate_blocks(B);
+  EvalState& ev = c->ev;
+  ev.have = false;
+  HIPCHK(c, ev.q.ensure((size_t)B * 3)); HIPCHK(c, ev.idx.ensure((size_t)B)); HIPCHK(c, ev.d2.ensure((size_t)B));
+  HIPCHK(c, ev.partial.ensure((size_t)nblk * kEvalRecord)); HIPCHK(c, ev.result.ensure(kEvalResult));
+  if (!ev.h_result.p) HIPCHK(c, ev.h_result.alloc(kEvalResult));
+  HIPCHK(c, launch_evaluate_transform(c->cloud.src.p, B, T, ev.q.p, c->stream));
+  // stage A's own search, K = 1, identity pose, in blocks of the rows its scratch is sized for (a mini-batch registration
+  // sizes it for fewer than B); no survivor counts: svnicp_get_knn_survivors keeps the registration's
+  const StageAEnv env{c->stream, c->tune, c->num_cus, false, c->cloud.tgt.p, c->B, c->M, c->pose0};
+  if (!c->sa.stage_kept)
+    if (const int rc = c->sa.keep_stage_fallbacks(c, env)) return rc;
+  Pose0 ident{};
+  ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
+  const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.plan.rows, B));
+  for (int64_t lo = 0; lo < B; lo += rows) {
+    const int64_t n = std::min<int64_t>(rows, B - lo);
+    if (const int rc = c->sa.search(c, env, ev.q.p + 3 * lo, ident, 1, ev.idx.p + lo, ev.d2.p + lo, 0, n)) return rc;
+  }
+  const bool normals = c->pl.supplied || c->pl.estimated;
+  EvalArgs a{};
+  a.q = ev.q.p; a.tgt = c->cloud.tgt.p; a.rec = normals ? c->pl.rec.p : nullptr; a.B = B; a.M = M;
+  a.thr2 = max_corr_dist * max_corr_dist; a.idx = ev.idx.p; a.d2 = ev.d2.p; a.partial = ev.partial.p;
+  HIPCHK(c, launch_evaluate_pairs(a, ev.result.p, c->stream));
+  HIPCHK(c, hipMemcpyAsync(ev.h_result.p, ev.result.p, kEvalResult * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double* r = ev.h_result.p;
+  out->has_normals = normals ? 1 : 0;
+  out->rows = B;
+  out->evaluated = (int64_t)r[0]; out->inliers = (int64_t)r[1]; out->plane_inliers = (int64_t)r[2];
+  out->sum_d2 = r[3]; out->sum_r2 = r[4]; out->fitness = r[5]; out->inlier_rmse = r[6]; out->plane_rmse = r[7];
+  std::memcpy(out->R, T.R, sizeof T.R); std::memcpy(out->t, T.t, sizeof T.t);
+  ev.have = true; ev.rows = B;
+  return SVNICP_OK;
+}
+
+const int32_t* svnicp_eval_index_devptr(svnicp_ctx* c) { return (c && c->ev.have) ? c->ev.idx.p : nullptr; }
+const double* svnicp_eval_dist2_devptr(svnicp_ctx* c) { return (c && c->ev.have) ? c->ev.d2.p : nullptr; }
+
+int svnicp_get_eval_pairs(svnicp_ctx* c, int32_t* idxB, double* d2B) {
+  CTX_CHECK(c);
+  if (!c->ev.have) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_eval_pairs: no svnicp_evaluate yet");
+  if (idxB)
+    if (const int rc = fetch(c, idxB, c->ev.idx.p, (size_t)c->ev.rows * 4)) return rc;
+  if (d2B)
+    if (const int rc = fetch(c, d2B, c->ev.d2.p, (size_t)c->ev.rows * 8)) return rc;
+  return SVNICP_OK;
 }
 
 int svnicp_get_trace(svnicp_ctx* c, int32_t* corr, double* H, double* b, double* N, double* phi, double* h) {

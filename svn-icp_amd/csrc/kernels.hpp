@@ -272,6 +272,24 @@ hipError_t launch_pack_normals(const double* tgt, const double* nrm, int64_t M, 
 hipError_t launch_plane_accumulate(const AccumPlan& plan, PlaneArgs a, hipStream_t st);
 hipError_t launch_plane_finalize(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* Hb, double* stats,
                                  const int* ctl, hipStream_t st);
+// ---------------- evaluate a registration (evaluate.hip) ----------------
+constexpr int kEvalRecord = 5;   // per workgroup: evaluated, inliers, plane inliers (counts, exact in float64), sum d2, sum r2
+constexpr int kEvalResult = 8;   // the record's five totals | fitness, inlier rmse, plane rmse
+struct EvalPose { double R[9]; double t[3]; };   // the pose under evaluation, row-major, by value
+struct EvalArgs {
+  const double* q;      // [B][3] transformed source
+  const double* tgt;    // [M][3]
+  const double* rec;    // [M][6] target xyz | unit normal when the context holds normals of this target, else nullptr
+  int64_t B, M;
+  double thr2;          // max_corr_dist^2
+  int32_t* idx;         // [B] in: stage A's nearest target (K = 1); out: the same, -1 = not evaluated
+  double* d2;           // [B] out: d2 recomputed from q and that row, NaN = not evaluated
+  double* partial;      // [evaluate_blocks(B)][kEvalRecord]
+};
+int64_t evaluate_blocks(int64_t B);
+hipError_t launch_evaluate_transform(const double* src, int64_t B, const EvalPose& T, double* q, hipStream_t st);
+// k_evaluate_pairs + k_evaluate_finalize: result[kEvalResult] in device memory
+hipError_t launch_evaluate_pairs(const EvalArgs& a, double* result, hipStream_t st);
 // ---------------- mini-batch tables (minibatch.hip) ----------------
 struct MinibatchArgs {
   const int32_t* explicit_idx;  // [n] a caller's table (validated by the draw kernel), or nullptr: generated from `base`

@@ -38,9 +38,11 @@ struct StageA {
   DevBuf<double> pool_d, sl_d, fail_tau, qrec;   // streaming kernel's pools, sliced fallback lists, proven thresholds, per-query records
   DevBuf<int32_t> pool_i, sl_i, pool2, fail_list, stat_n;
   DevBuf<int> fail_count;
-  // correspondence = full reuses fail_list / fail_count for every per-particle search: stage A's own are kept here
+  // a later search of the registration's working set (correspondence = full: one per particle and iteration; svnicp_evaluate)
+  // reuses fail_list / fail_count: stage A's own are kept here, and `stage_kept` says that the getters read them
   DevBuf<int> stage_fail_count;
   DevBuf<int32_t> stage_fail_list;
+  bool stage_kept = false;
   DevBuf<unsigned int> keys_a, keys_b;   // Morton sort scratch, for max(M, B) keys
   DevBuf<int32_t> vals_a, order_t, qorder;
   DevBuf<unsigned char> sort_tmp;
@@ -56,6 +58,7 @@ struct StageA {
   template <class Obj>
   int begin(Obj* o, const StageAEnv& e, int64_t rows, int K, std::initializer_list<int> Ks) {
     plan = plan_stage_a(rows, e.M, K, e.tune.knn, e.tune.fallback_sliced_max);
+    stage_kept = false;
     const size_t Bq = (size_t)rows, B = (size_t)e.B, M = (size_t)e.M, Mp = (size_t)plan.Mp;
     size_t S = 0, slice_entries = 0;
     for (const int k : Ks) { S = std::max<size_t>(S, knn_pool_size(k)); slice_entries = std::max<size_t>(slice_entries, (size_t)knn_slice_count(k) * k); }
@@ -233,21 +236,24 @@ struct StageA {
     return SVNICP_OK;
   }
 
-  // correspondence = full: svnicp_get_knn_fallbacks / _rows describe STAGE A, not the last particle's K = 1 search
+  // svnicp_get_knn_fallbacks / _rows describe STAGE A, not a later K = 1 search through the same working set: called behind
+  // stage A when such searches follow (correspondence = full), or ahead of the first one (svnicp_evaluate, unless kept already)
   template <class Obj>
   int keep_stage_fallbacks(Obj* o, const StageAEnv& e) {
-    if (!e.tune.full_corr || !plan.has_fallback()) return SVNICP_OK;
+    if (!plan.has_fallback()) return SVNICP_OK;
+    HIPCHK(o, stage_fail_count.ensure(1)); HIPCHK(o, stage_fail_list.ensure((size_t)plan.rows));
     HIPCHK(o, hipMemcpyAsync(stage_fail_count.p, fail_count.p, sizeof(int), hipMemcpyDeviceToDevice, e.stream));
-    HIPCHK(o, hipMemcpyAsync(stage_fail_list.p, fail_list.p, (size_t)e.B * sizeof(int32_t), hipMemcpyDeviceToDevice, e.stream));
+    HIPCHK(o, hipMemcpyAsync(stage_fail_list.p, fail_list.p, (size_t)plan.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, e.stream));
+    stage_kept = true;
     return SVNICP_OK;
   }
   // what the getters read: the count of stage A's fallback rows (nullptr: the streaming kernel has no such notion), the rows
   // themselves, the survivor counts of the tile kernels' pre-filter (nullptr: not recorded)
-  const int* fallback_count(const Tuning& t) const {
+  const int* fallback_count() const {
     if (plan.kernel == KnnKernel::Stream) return nullptr;
-    return t.full_corr && plan.has_fallback() ? stage_fail_count.p : fail_count.p;
+    return stage_kept ? stage_fail_count.p : fail_count.p;
   }
-  const int32_t* fallback_rows(const Tuning& t) const { return t.full_corr && plan.has_fallback() ? stage_fail_list.p : fail_list.p; }
+  const int32_t* fallback_rows() const { return stage_kept ? stage_fail_list.p : fail_list.p; }
   const int32_t* survivors(bool record_trace) const { return plan.kernel == KnnKernel::Tiles && record_trace ? stat_n.p : nullptr; }
 };
 

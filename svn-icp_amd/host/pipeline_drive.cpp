@@ -2,10 +2,12 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1]
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist]
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
 //      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
-//      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2)
+//      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2;
+//      eval_dist > 0: PipelineConfig::eval_dist, every registered scan is evaluated and one more line per scan is printed:
+//      "eval <scan>: fitness inlier_rmse plane_rmse plane_inliers" with %.17g, -1 where a figure does not exist)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -36,6 +38,7 @@ int main(int argc, char** argv) {
   cfg.deskew = argc > 9 && atoi(argv[9]) != 0;
   cfg.segmentation = argc > 10 && atoi(argv[10]) != 0;
   cfg.plane = cfg.map_normals = argc > 11 && atoi(argv[11]) != 0;
+  cfg.eval_dist = argc > 12 ? atof(argv[12]) : 0.0;
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;
@@ -70,6 +73,8 @@ int main(int argc, char** argv) {
       if (cfg.map_normals && r.aligned) wr(fo, &r.with_normal, 1);
       printf("scan %d: aligned %d  B %lld  M %lld  voxels %zu  h2d bytes so far %zu  pose t = %.4f %.4f %.4f\n", s, aligned, (long long)B,
              (long long)M, pipe.map_voxels(), pipe.bytes_h2d(), r.pose.t[0], r.pose.t[1], r.pose.t[2]);
+      if (cfg.eval_dist > 0)
+        printf("eval %d: %.17g %.17g %.17g %lld\n", s, r.fitness, r.inlier_rmse, r.plane_rmse, (long long)r.plane_inliers);
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "svnicp: %s\n", e.what());

@@ -585,6 +585,8 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   int normal_k = 16;           // with plane: neighbours a target normal is estimated from (4..64)
   bool map_normals = false;    // with plane and gpu_map: the target's normals come from the map's own voxels
                                // (DeviceVoxelMap::QueryNormals) instead of the solver's pass over the target
+  double eval_dist = 0.0;      // > 0: every registered scan is evaluated at its result pose with this inlier gate
+                               // (svnicp_evaluate) before the map update; 0 = off, no call is made
 };
 
 struct ScanResult {
@@ -595,6 +597,9 @@ struct ScanResult {
   std::array<double, 6> correction{}, variance{};
   std::vector<double> cov, particles, weights;
   int64_t with_normal = -1;   // cfg.map_normals: target rows the map gave a normal
+  // cfg.eval_dist > 0: the result pose against the whole target (svnicp_evaluate); -1 = off, plane figures -1 without normals
+  double fitness = -1, inlier_rmse = -1, plane_rmse = -1;
+  int64_t plane_inliers = -1;
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -712,6 +717,11 @@ class RegistrationPipeline {
     res.particles = solver_->get_particles();
     res.weights = solver_->get_particle_weight();
     res.pose = guess * correction_to_pose(res.correction);                                             // updater_, :37-46
+    if (cfg_.eval_dist > 0) {   // the number a caller may gate the map update on (no policy here)
+      const svnicp_eval ev = solver_->evaluate(cfg_.eval_dist, res.pose.R.data(), res.pose.t.data());
+      res.fitness = ev.fitness; res.inlier_rmse = ev.inlier_rmse;
+      if (ev.has_normals) { res.plane_rmse = ev.plane_rmse; res.plane_inliers = ev.plane_inliers; }
+    }
     // … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is updated
     // with the same points the solver registered
     if (dprep_) dmap_->AddPointCloudDevice(dprep_->source_f32(), dprep_->n_source, res.pose);          // :630

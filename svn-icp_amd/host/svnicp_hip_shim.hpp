@@ -131,6 +131,22 @@ class SVGDICP {
     chk(svnicp_get_plane_stats(h_, o.data(), normal_passes));
     return o;
   }
+  // evaluate a registration (svnicp_hip.h "evaluate a registration"): fitness, inlier RMSE and, with normals, plane RMSE of
+  // a pose (row-major R, t; map <- sensor) against the whole target; both NULL: the last registration's result
+  svnicp_eval evaluate(double max_corr_dist, const double* R_rowmajor = nullptr, const double* t = nullptr) {
+    svnicp_eval e{};
+    e.struct_size = (int32_t)sizeof e;
+    chk(svnicp_evaluate(h_, R_rowmajor, t, max_corr_dist, &e));
+    return e;
+  }
+  // per source row of the last evaluate: nearest target row (-1 = not evaluated) and its d2 (NaN = not evaluated)
+  void get_eval_pairs(std::vector<int32_t>* idx, std::vector<double>* d2, int64_t B) {
+    if (idx) idx->assign((size_t)B, -1);
+    if (d2) d2->assign((size_t)B, 0.0);
+    chk(svnicp_get_eval_pairs(h_, idx ? idx->data() : nullptr, d2 ? d2->data() : nullptr));
+  }
+  const int32_t* eval_index_ptr() { return svnicp_eval_index_devptr(h_); }
+  const double* eval_dist2_ptr() { return svnicp_eval_dist2_devptr(h_); }
   svnicp_ctx* handle() { return h_; }
 
  protected:

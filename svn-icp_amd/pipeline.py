@@ -891,6 +891,7 @@ class PipelineConfig:
     seg_params: SegParams = field(default_factory=SegParams)   # the sensor of ImageProjection.h (SEG_PRESETS); HDL-64E by default
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
+    eval_dist: float = 0.0         # > 0: every registered scan is evaluated at its result pose with this inlier gate (svnicp_evaluate) before the map update; 0 = off, no call is made
     map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
 
     def __post_init__(self):
@@ -914,6 +915,10 @@ class ScanResult:
     align_s: float = 0.0
     state: int | None = None
     with_normal: int | None = None           # cfg.map_normals: target rows the map gave a normal
+    fitness: float | None = None             # cfg.eval_dist > 0: inliers / source rows of the result pose against the whole target
+    inlier_rmse: float | None = None         # … sqrt(mean d2) over the inliers
+    plane_rmse: float | None = None          # … sqrt(mean r2) over the inliers whose target has a normal; None without normals
+    plane_inliers: int | None = None
 
 
 class RegistrationPipeline:
@@ -1017,6 +1022,11 @@ class RegistrationPipeline:
         pose = guess @ correction_to_pose(corr)                                                                 # updater_, :37-46
         res = ScanResult(stamp, pose, guess, corr, s.get_distribution(), s.get_cov_matrix(), s.get_particles().reshape(-1),
                          s.get_particle_weight(), t1 - t0, 0.0, int(state), with_normal)
+        if c.eval_dist > 0:   # the number a caller may gate the map update on (no policy here)
+            ev = s.evaluate(c.eval_dist, pose)
+            res.fitness, res.inlier_rmse = ev.fitness, ev.inlier_rmse
+            if ev.has_normals:
+                res.plane_rmse, res.plane_inliers = ev.plane_rmse, ev.plane_inliers
         # … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is
         # updated with the same points the solver registered
         if dev:

@@ -63,6 +63,22 @@ class ParticleWeightOpt:  # include/core/SVNICP.h:25-27
     use_weight_mean: bool = False
 
 
+@dataclass
+class RegistrationEval:
+    """struct svnicp_eval (include/svnicp_hip.h, "evaluate a registration"): one pose against the whole target."""
+    has_normals: bool          # the context holds normals of the current target: the plane figures are filled
+    rows: int                  # B
+    evaluated: int             # rows with a finite transformed point and a nearest target whose d2 is not NaN
+    inliers: int               # evaluated rows with d2 < max_corr_dist^2
+    plane_inliers: int         # inliers whose nearest target has a normal (0 without normals)
+    sum_d2: float              # over the inliers
+    sum_r2: float              # over the plane inliers
+    fitness: float             # inliers / rows
+    inlier_rmse: float         # sqrt(sum_d2 / inliers), 0 when there are none
+    plane_rmse: float          # sqrt(sum_r2 / plane_inliers), 0 when there are none
+    pose: np.ndarray           # 4x4, the pose that was evaluated (map <- sensor)
+
+
 def initialize_particles(particle_count: int, ub, lb, rng: np.random.Generator | None = None) -> np.ndarray:
     """svnicp::initialize_particles (src/core/ICPUtils.cpp:45-58): uniform in [lb, ub] per row,
     zeros for a single particle.  Returns [6, P] float64."""
@@ -351,6 +367,44 @@ class _SolverBase:
         self._check(self._L.svnicp_get_plane_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_double)) if with_sums else None,
                                                    C.byref(n)), "svnicp_get_plane_stats")
         return out, int(n.value)
+
+    # -- evaluate a registration (include/svnicp_hip.h "evaluate a registration") ---------------------------------------------
+    def evaluate(self, max_corr_dist: float, pose=None) -> RegistrationEval:
+        """Fitness, inlier RMSE and (with normals) plane RMSE of ``pose`` (4x4, map <- sensor) against the whole target, on
+        the device; ``pose=None``: the last registration's result, initial mean times the mean correction."""
+        e = binding.EvalStruct()
+        e.struct_size = C.sizeof(binding.EvalStruct)
+        dp = C.POINTER(C.c_double)
+        if pose is None:
+            R = t = None
+        else:
+            T = np.asarray(pose, np.float64).reshape(4, 4)
+            Rk, tk = np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+            R, t = Rk.ctypes.data_as(dp), tk.ctypes.data_as(dp)
+        self._check(self._L.svnicp_evaluate(self._h, R, t, float(max_corr_dist), C.byref(e)), "svnicp_evaluate")
+        T = np.eye(4)
+        T[:3, :3] = np.array(e.R[:]).reshape(3, 3)
+        T[:3, 3] = e.t[:]
+        return RegistrationEval(bool(e.has_normals), int(e.rows), int(e.evaluated), int(e.inliers), int(e.plane_inliers),
+                                float(e.sum_d2), float(e.sum_r2), float(e.fitness), float(e.inlier_rmse), float(e.plane_rmse), T)
+
+    def get_eval_pairs(self) -> tuple:
+        """Per source row of the last ``evaluate``: (nearest target row, int32 [B], -1 = not evaluated; its d2, float64 [B],
+        NaN = not evaluated)."""
+        idx, d2 = np.zeros(self._B, np.int32), np.zeros(self._B, np.float64)
+        self._check(self._L.svnicp_get_eval_pairs(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  d2.ctypes.data_as(C.POINTER(C.c_double))), "svnicp_get_eval_pairs")
+        return idx, d2
+
+    @property
+    def eval_index_ptr(self) -> int:
+        """Device address of the last evaluate's int32 [B] nearest target rows (0 before any)."""
+        return int(self._L.svnicp_eval_index_devptr(self._h) or 0)
+
+    @property
+    def eval_dist2_ptr(self) -> int:
+        """Device address of the last evaluate's float64 [B] squared distances (0 before any)."""
+        return int(self._L.svnicp_eval_dist2_devptr(self._h) or 0)
 
     def set_threshold(self, max_dist: float):
         self._check(self._L.svnicp_set_max_dist(self._h, float(max_dist)), "svnicp_set_max_dist")
