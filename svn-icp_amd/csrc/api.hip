@@ -1,6 +1,9 @@
 // api.hip — the C ABI of libsvnicp_hip.so (include/svnicp_hip.h): context, device buffers,
 // launch sequencing.  Host-side mirror of the reference's solver object state
 // (include/core/SVGDICP.h:170-210): clouds, R0/t0, particles R_/t_, pose_particles_, history.
+// What a registration decides is not here: stage A's kernel and sizes are stage_a_plan.hpp / stage_a_host.hpp, everything
+// behind it (rows, refusals, stage-B variant and shape, step chain, how svnicp_align drives the iterations) is
+// registration_plan.hpp, sized by stage_b_host.hpp.  svnicp_align_begin asks once and stores the answers.
 // No CPU fallback: every compute entry point needs a gfx950 device and fails loudly without one.
 #include "../../include/svnicp_hip.h"
 
@@ -15,6 +18,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "stage_a_host.hpp"
+#include "stage_b_host.hpp"
 
 using namespace svnicp;
 using namespace svnicp_host;
@@ -25,38 +29,6 @@ namespace {
 struct CloudState {   // the clouds as given (the re-ordered target copies are stage A's: stage_a_host.hpp)
   DevBuf<double> src, tgt;
   bool src_set = false, tgt_set = false;
-};
-
-struct StageB {   // stage B tables and per-iteration scratch
-  AccumPlan plan{};
-  int accum_mode = 3;  // 0 f64 baseline, 1 f32 VALU search (fused), 3 bf16 matrix-pipe search + accumulate kernels
-  DevBuf<double> table, anchor, sums, partial;
-  DevBuf<float4> tablef, tablea;
-  DevBuf<float> cmaxb;
-  DevBuf<uint8_t> kbest;
-  DevBuf<int32_t> kidx;
-  DevBuf<int> ambig;
-  DevBuf<double> full_q, full_d2;      // correspondence = full: one particle's transformed source, its nearest distances
-  DevBuf<int32_t> full_idx;            // … and the nearest target of every (particle of the shard, source point): [P][B]
-};
-
-// which launches carry the Stein step of 2 <= P particles (P = 1 and option update=fused: OneKernel); chosen once per
-// registration by choose_step_chain at the end of svnicp_align_begin
-enum class StepChain {
-  // P = 1 (no pair statistics) and option update=fused: the whole Stein step is one one-workgroup kernel on the main stream
-  OneKernel,
-  // few (point, particle) pairs: the accumulate kernel runs at most kSmallChainBlocks workgroups, nothing reduces their records
-  // (the prepare lanes add them), and the pair statistics share the prepare kernel's launch on the main stream
-  SmallChain,
-  // general chain, up to 128 particles (the one-workgroup pair statistics): they run as the last workgroup of the prepare
-  // kernel's launch on the main stream.  The second stream hid their 12 us behind the search kernel, but its fork and join
-  // (event record / wait on both sides, one more launch) cost more: C3 7.25 -> 6.99 ms, C2 2.72 -> 2.56 ms per registration,
-  // and 0.25 ms less host time to enqueue a registration.  Above 128 particles the three-kernel chain stays on the second stream.
-  InlineMedian,
-  // the pair statistics of iteration `it` (bandwidth h from the exact median of the pair distances): they depend on the
-  // poses only, so they are forked onto the second stream at the START of the iteration and run beside the search and
-  // accumulate kernels; svnicp_iter_update joins before the Stein direction
-  SideStream,
 };
 
 struct SteinState {   // particle and Stein-step state
@@ -70,16 +42,13 @@ struct SteinState {   // particle and Stein-step state
   bool host_stats_valid = false;   // h_stats holds the last registration's results (after the stream has been synchronised)
   Event ev_init;
   bool init_in_flight = false;
-  StepChain chain = StepChain::OneKernel;
-  // ONE particle, no exchange between ranks ahead, the fused f32 kernel: its last workgroup reduces the partial sums and
-  // runs the Stein step (for P = 1 the Newton step and the pose update) — the iteration is this one launch
-  bool single_fused = false;
+  StepPlan step;     // the launches of this registration's Stein step (svnicp_align_begin; svnicp_set_option chooses again)
+  DrivePlan drive;   // svnicp_align / svnicp_align_async: how their loop runs the iterations; defer_fin holds inside that loop only
   int single_done_it = -1;   // iteration whose Stein step the accumulate kernel's last workgroup has already enqueued (P = 1)
   Event ev_fork, ev_join;   // the second queue is forked from and joined into `stream`: the caller still sees one ordered queue
   bool median_pending = false;
   DevBuf<unsigned int> small_bar;   // persistent small-registration kernel: arrivals, generation, error word
   bool small_launched = false;      // the last svnicp_align_async ran the persistent kernel (its error word is checked at the next synchronisation)
-  bool defer_fin = false;           // svnicp_align's own loop: iteration i's early-stop decision is taken by iteration i + 1's search kernel
   // blocking svnicp_align with early stop: the stop flag follows every few iterations into pinned memory, so that the host
   // stops enqueuing soon after the device has stopped (three slots, the host runs two chunks ahead)
   Event ev_chunk[3];
@@ -220,19 +189,16 @@ static StageAEnv stage_a_env(const svnicp_ctx* c) {
   return {c->stream, c->tune, c->num_cus, c->prm.record_trace != 0, c->cloud.tgt.p, c->B, c->M, c->pose0};
 }
 
-constexpr int kMedianInlineMaxP = 128;   // the one-workgroup pair statistics
-
-// the launches of this registration's Stein step: from the options and the stage-B plan svnicp_align_begin has just made
-static void choose_step_chain(svnicp_ctx* c) {
-  const Tuning& t = c->tune;
-  const AccumPlan& pl = c->sb.plan;
-  const int P = c->P;
-  if (P < 2 || (t.update_fused && P <= t.fused_update_max_p)) c->st.chain = StepChain::OneKernel;
-  else if (pl.f32 == 3 && pl.small && pl.grid_x <= kSmallChainBlocks) c->st.chain = StepChain::SmallChain;
-  else if (P <= kMedianInlineMaxP && P <= t.fused_update_max_p && t.median_inline != 0) c->st.chain = StepChain::InlineMedian;
-  else c->st.chain = StepChain::SideStream;
-  c->st.single_fused = P == 1 && c->prm.mode == SVNICP_MODE_SVN && c->shard.row_world == 1 && c->shard.p_lo == 0 && c->shard.p_hi == 1 &&
-                       !t.full_corr && t.single_fused && accumulate_can_fuse_single(pl) && !c->pl.on;
+// what the rules of registration_plan.hpp read of the context; plane: the residual this registration runs with
+static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane) {
+  RegistrationFacts f;
+  f.P = c->P; f.K = c->K; f.I = c->prm.iterations; f.B = c->B; f.M = c->M;
+  f.svgd = c->prm.mode == SVNICP_MODE_SVGD; f.check_early_stop = c->prm.check_early_stop != 0; f.record_trace = c->prm.record_trace != 0;
+  f.profiling = c->prof.on;
+  f.shard_set = c->shard.set; f.p_lo = c->shard.p_lo; f.p_hi = c->shard.p_hi; f.row_world = c->shard.row_world;
+  f.batch = c->mb.batch; f.explicit_tab = c->mb.explicit_tab; f.tab_I = c->mb.tab_I;
+  f.plane = plane; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
+  return f;
 }
 
 extern "C" {
@@ -464,7 +430,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   c->run.have_candidates = false;
   c->sa.held = TargetLayout::None;
   // svnicp_iter_accumulate now refuses until the next svnicp_align_begin; svnicp_iter_update goes on and follows the new options
-  if (c->run.began) choose_step_chain(c);
+  if (c->run.began) c->st.step = plan_step(registration_facts(c, c->pl.on), c->tune, c->sb.plan);
   return SVNICP_OK;
 }
 
@@ -507,90 +473,41 @@ int svnicp_align_begin(svnicp_ctx* c) {
   if (bind(c)) return SVNICP_ERR_HIP;
   const int I = c->prm.iterations, P = c->P;
   const int64_t B = c->B;
-  // mini-batch: what this registration draws, and what it is not combined with
-  bool mb = false;
-  if (c->mb.batch != 0) {
-    const char* why = nullptr;
-    if (c->mb.batch < 0) why = "batch_size must be positive";
-    else if (c->shard.set && (c->shard.p_lo != 0 || c->shard.p_hi != P)) why = "a partial particle shard (svnicp_set_shard) is set";
-    else if (c->shard.row_world > 1) why = "a source-row shard (svnicp_set_row_shard) is set";
-    else if (c->tune.full_corr) why = "option correspondence=full is set";
-    else if (c->tune.persistent) why = "option chain=persistent is set";
-    else if ((int64_t)I * c->mb.batch > kMinibatchMaxRows) why = "iterations * batch_size exceeds 2^22 table rows (about 2.5 KB of tables per row)";
-    else if (c->mb.explicit_tab && c->mb.tab_I != I) why = "the explicit index table's iteration count differs from params.iterations";
-    if (why) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ") + why);
-    if (c->mb.explicit_tab && !c->mb.tab_h.empty() && c->mb.tab_checked_B != B) {
-      for (const int32_t v : c->mb.tab_h)
-        if (v < 0 || (int64_t)v >= B)
-          return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the mini-batch index table holds " + std::to_string(v) + ", outside [0, " + std::to_string(B) + ")");
-      c->mb.tab_checked_B = B;
-    }
-    mb = I > 0;
-  }
-  // point-to-plane residual: what it is not combined with (all left for later)
   const bool plane = c->pl.residual == SVNICP_RESIDUAL_PLANE;
-  if (plane) {
-    const char* why = nullptr;
-    if (c->prm.mode == SVNICP_MODE_SVGD) why = "SVGD mode has no Hessian to put the plane residual in";
-    else if (c->shard.set && (c->shard.p_lo != 0 || c->shard.p_hi != P)) why = "a partial particle shard (svnicp_set_shard) is set";
-    else if (c->shard.row_world > 1) why = "a source-row shard (svnicp_set_row_shard) is set: the rank exchange carries the 22 point-to-point sums";
-    else if (c->mb.batch != 0) why = "mini-batch mode (svnicp_set_minibatch) is set";
-    else if (c->tune.full_corr) why = "option correspondence=full is set";
-    else if (c->tune.persistent) why = "option chain=persistent is set";
-    else if (c->tune.accum != 3) why = "option accum is not split: the plane kernel consumes the search kernel's winner index";
-    else if (c->K > 128) why = "knn_count exceeds 128: the plane kernel consumes the matrix-pipe search kernel's winner index";
-    else if (!c->pl.supplied && c->M < c->pl.normal_k) why = "the target has fewer points than normal_k and no normals were supplied";
-    if (why) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ") + why);
+  const RegistrationFacts f = registration_facts(c, plane);
+  if (const char* why = minibatch_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kMinibatchRefusal) + why);
+  if (c->mb.batch != 0 && c->mb.explicit_tab && !c->mb.tab_h.empty() && c->mb.tab_checked_B != B) {
+    for (const int32_t v : c->mb.tab_h)
+      if (v < 0 || (int64_t)v >= B)
+        return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the mini-batch index table holds " + std::to_string(v) + ", outside [0, " + std::to_string(B) + ")");
+    c->mb.tab_checked_B = B;
   }
+  if (const char* why = plane_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kPlaneRefusal) + why);
+  const RegistrationRows r = registration_rows(c->mb.batch, I, B);
+  const AccumPlan shape = plan_stage_b(f, c->tune, r.Bi);
+  // (the stage-A plan StageA::begin is about to make: every refusal comes before the context changes)
+  const bool stage_a_k1 = StageA::plan_for(stage_a_env(c), r.Bq, c->K).can_search(1);
+  if (const char* why = full_corr_refusal(f, c->tune, shape.f32, stage_a_k1)) return fail(c, SVNICP_ERR_INVALID, why);
   c->pl.on = plane;
-  c->mb.on = mb; c->mb.have = false; c->mb.check = false;
-  c->mb.rows = mb ? (int64_t)I * c->mb.batch : 0;
-  c->mb.nq = mb ? std::min<int64_t>(B, c->mb.rows) : 0;
-  const int64_t Bq = mb ? c->mb.nq : B;        // rows stage A runs on
-  const int64_t Bt = mb ? c->mb.rows : B;      // rows of the candidate tables
-  const int64_t Bi = mb ? c->mb.batch : B;     // rows one iteration works on
+  c->mb.on = r.mb; c->mb.have = false; c->mb.check = false;
+  c->mb.rows = r.mb ? r.Bt : 0;
+  c->mb.nq = r.mb ? r.Bq : 0;
   HIPCHK(c, hipEventRecord(c->prof.ev[0], c->stream));
   // stage A: kernel, scratch for every search of this registration (its own, the normal pass, correspondence = full), layout
-  if (const int rc = c->sa.begin(c, stage_a_env(c), Bq, c->K, {c->K, normal_pass_due(c) ? c->pl.normal_k : c->K, c->tune.full_corr ? 1 : c->K})) return rc;
-  if (mb) {
-    HIPCHK(c, c->mb.idx.ensure((size_t)Bt)); HIPCHK(c, c->mb.flag.ensure((size_t)B)); HIPCHK(c, c->mb.pos.ensure((size_t)B));
+  if (const int rc = c->sa.begin(c, stage_a_env(c), r.Bq, c->K, {c->K, normal_pass_due(c) ? c->pl.normal_k : c->K, c->tune.full_corr ? 1 : c->K})) return rc;
+  if (r.mb) {
+    HIPCHK(c, c->mb.idx.ensure((size_t)r.Bt)); HIPCHK(c, c->mb.flag.ensure((size_t)B)); HIPCHK(c, c->mb.pos.ensure((size_t)B));
     HIPCHK(c, c->mb.bsum.ensure((size_t)minibatch_scan_blocks(B))); HIPCHK(c, c->mb.ctl.ensure(2));
-    HIPCHK(c, c->mb.src_u.ensure((size_t)Bq * 3)); HIPCHK(c, c->mb.src.ensure((size_t)Bt * 3));
-    HIPCHK(c, c->mb.cand.ensure((size_t)Bt * c->K));
+    HIPCHK(c, c->mb.src_u.ensure((size_t)r.Bq * 3)); HIPCHK(c, c->mb.src.ensure((size_t)r.Bt * 3));
+    HIPCHK(c, c->mb.cand.ensure((size_t)r.Bt * c->K));
   }
-  c->sb.accum_mode = c->tune.accum;   // option "accum": f64 | valu | split
-  HIPCHK(c, c->sb.cmaxb.ensure((size_t)Bt));
-  HIPCHK(c, c->sb.ambig.ensure(2));   // [0] wave steps with an undecided lane, [1] undecided (point, particle) pairs (cleared by the begin kernel below)
+  if (const int rc = c->sb.begin(c, f, c->tune, r, shape, c->num_cus)) return rc;
   HIPCHK(c, c->st.history.ensure((size_t)(I > 0 ? I : 1) * 6 * P));
   c->st.hist_I = I; c->st.hist_P = P;
-  const int nshard = c->shard.p_hi - c->shard.p_lo;
-  if (nshard > 0) {
-    // small chain (few pairs, one context holds everything, 2 <= P <= 128): decided here, carried by the plan
-    Tuning tn = c->tune;
-    tn.small_chain = tn.small_chain && P >= 2 && P <= 128 && P <= tn.fused_update_max_p && !tn.update_fused && c->shard.row_world == 1 &&
-                     c->shard.p_lo == 0 && c->shard.p_hi == P && !tn.full_corr && !plane;
-    tn.force_split = plane ? 1 : 0;   // plane mode: the split kernels for any particle count, and never the small chain
-    c->sb.plan = plan_accumulate(nshard, Bi, c->K, c->num_cus, c->sb.accum_mode, tn);
-    if (c->tune.debug)
-      fprintf(stderr, "[svnicp] stage-B plan: mode=%d PW=%d WP=%d TP=%d grid=%dx%d tiles/block=%d smem=%zu sgrid=%d pts/block=%d/%d\n", c->sb.plan.f32,
-              c->sb.plan.PW, c->sb.plan.WP, c->sb.plan.TP, c->sb.plan.grid_x, c->sb.plan.grid_y, c->sb.plan.tiles_per_block, c->sb.plan.smem,
-              c->sb.plan.sgrid_x, c->sb.plan.spts_per_block, c->sb.plan.pts_per_block);
-    if (c->sb.plan.smem > 160u * 1024)   // K > 128 runs the LDS-tile VALU search: its smallest tile must fit one CU's LDS
-      return fail(c, SVNICP_ERR_INVALID, "svnicp_align: knn_count " + std::to_string(c->K) + " needs " + std::to_string(c->sb.plan.smem) +
-                  " bytes of LDS per workgroup (limit 163840): the candidate count is too large for this particle count");
-    HIPCHK(c, c->sb.partial.ensure((size_t)std::max(c->sb.plan.grid_x, P == 1 ? single_particle_grid(Bi) : 0) * c->sb.plan.Ppad * kNSums));
-  } else {
-    c->sb.plan = AccumPlan{};
-    c->sb.plan.f32 = c->sb.accum_mode == 3 ? 1 : c->sb.accum_mode;
-  }
-  if (c->sb.plan.f32 != 3) HIPCHK(c, c->sb.table.ensure((size_t)Bt * c->K * 3));  // the split variant gathers from the target cloud
-  if (c->sb.plan.f32 == 3) { HIPCHK(c, c->sb.tablea.ensure((size_t)Bt * 128)); HIPCHK(c, c->sb.anchor.ensure((size_t)Bt * 3)); }
-  if (c->sb.plan.f32 == 3) { HIPCHK(c, c->sb.kbest.ensure((size_t)Bi * c->sb.plan.Ppad)); HIPCHK(c, c->sb.kidx.ensure((size_t)Bi * c->sb.plan.Ppad)); }
-  else HIPCHK(c, c->sb.tablef.ensure((size_t)Bt * c->K));
   if (c->prm.record_trace) {
     const size_t IP = (size_t)I * P;
-    HIPCHK(c, c->tr.corr.ensure(IP * Bi));
-    HIPCHK(c, hipMemsetAsync(c->tr.corr.p, 0xff, IP * Bi * 4, c->stream));
+    HIPCHK(c, c->tr.corr.ensure(IP * r.Bi));
+    HIPCHK(c, hipMemsetAsync(c->tr.corr.p, 0xff, IP * r.Bi * 4, c->stream));
     const struct { DevBuf<double>& buf; size_t n; } dbl[] = {{c->tr.H, IP * 36}, {c->tr.b, IP * 6}, {c->tr.N, IP * 6}, {c->tr.phi, IP * 6}, {c->tr.h, (size_t)I + 1}};
     for (const auto& x : dbl) {
       HIPCHK(c, x.buf.ensure(x.n));
@@ -634,7 +551,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   }
   if (plane)
     if (const int rc = prepare_plane(c)) return rc;
-  choose_step_chain(c);
+  c->st.step = plan_step(f, c->tune, c->sb.plan);
   c->run.began = true;
   c->st.finish_seen = false;
   c->run.have_result = false;
@@ -667,8 +584,6 @@ static int print_update_phases(svnicp_ctx* c, bool persistent) {
 // the ones at hand were not estimated from this target with this normal_k.  The neighbours come from stage A itself (target
 // as the query cloud, identity pose, K = normal_k) in blocks of the rows its scratch is sized for.
 static int prepare_plane(svnicp_ctx* c) {
-  if (c->sb.plan.f32 != 3)
-    return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the point-to-plane residual needs the split stage B (option accum=split, knn_count <= 128)");
   HIPCHK(c, c->pl.partial.ensure((size_t)c->sb.plan.grid_x * c->sb.plan.Ppad * kPlaneSums));
   HIPCHK(c, c->pl.Hb.ensure((size_t)c->P * 42));
   HIPCHK(c, c->pl.stats.ensure((size_t)c->P * 2));
@@ -678,17 +593,15 @@ static int prepare_plane(svnicp_ctx* c) {
   if (!c->sa.plan.can_search(kn))
     return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the seeded-scan stage A (option knn=v2, or a target beyond the tile kernel's range) cannot "
                                        "search with normal_k neighbours: supply the normals (svnicp_set_target_normals)");
-  const int64_t M = c->M, rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.plan.rows, M));
+  const int64_t M = c->M, rows = c->sa.block_rows(M);
   HIPCHK(c, c->pl.rec.ensure((size_t)M * 6));
   HIPCHK(c, c->pl.nbr.ensure((size_t)rows * kn));
   HIPCHK(c, c->pl.nbr_d2.ensure((size_t)rows * kn));
-  Pose0 ident{};
-  ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
-  for (int64_t lo = 0; lo < M; lo += rows) {
-    const int64_t n = std::min<int64_t>(rows, M - lo);
-    if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.tgt.p + 3 * lo, ident, kn, c->pl.nbr.p, c->pl.nbr_d2.p, 0, n)) return rc;
+  const int rc = c->sa.search_blocks(c, stage_a_env(c), c->cloud.tgt.p, M, kn, c->pl.nbr.p, c->pl.nbr_d2.p, 0, [&](int64_t lo, int64_t n) {
     HIPCHK(c, launch_target_normals(c->cloud.tgt.p, M, c->pl.nbr.p, lo, n, kn, c->pl.rec.p, c->stream));
-  }
+    return (int)SVNICP_OK;
+  });
+  if (rc) return rc;
   c->pl.estimated = true; c->pl.est_k = kn;
   c->pl.passes += 1;
   return SVNICP_OK;
@@ -734,11 +647,7 @@ int svnicp_build_candidate_table(svnicp_ctx* c) {
   HIPCHK(c, prof_begin(c, KC_TABLE));
   const int32_t* cand = c->mb.on ? c->mb.cand.p : c->sa.cand_idx.p;   // mini-batch: one table row per drawn position
   const int64_t rows = c->mb.on ? c->mb.rows : c->B;
-  if (c->sb.plan.f32 == 3)
-    HIPCHK(c, launch_build_table3(cand, rows, c->K, c->cloud.tgt.p, c->M, c->sb.plan.f32 == 3 ? nullptr : c->sb.table.p,
-                                  c->sb.anchor.p, c->sb.tablea.p, c->sb.cmaxb.p, c->stream));
-  else
-    HIPCHK(c, launch_build_table2(cand, rows, c->K, c->cloud.tgt.p, c->M, c->sb.table.p, c->sb.tablef.p, c->sb.cmaxb.p, c->stream));
+  if (const int rc = c->sb.build_table(c, cand, rows, c->K, c->cloud.tgt.p, c->M, c->stream)) return rc;
   HIPCHK(c, prof_end(c));
   HIPCHK(c, hipEventRecord(c->prof.ev[1], c->stream));
   c->run.have_candidates = true;
@@ -785,7 +694,7 @@ static AccumArgs accum_args(svnicp_ctx* c, int it) {
   }
   a.svgd = c->prm.mode == SVNICP_MODE_SVGD ? 1 : 0;
   a.fin_iteration = -1;
-  if (c->st.defer_fin && it >= 1) {   // the previous iteration's early-stop decision rides on this iteration's search launch
+  if (c->st.drive.defer_fin && it >= 1) {   // the previous iteration's early-stop decision rides on this iteration's search launch
     const UpdateArgs up = update_args(c, it - 1);
     a.fin_iteration = it - 1; a.fin_P = c->P; a.fin_thr = c->prm.convergence_threshold; a.fin_norms = update_step_norms(up);
     a.fin_pose = c->st.pose_out.p; a.fin_history = c->st.history.p; a.fin_ctl = c->st.ctl.p;
@@ -796,11 +705,11 @@ static AccumArgs accum_args(svnicp_ctx* c, int it) {
 
 // svnicp_align's own loop (defer_fin): iteration `it`'s early-stop decision is taken by iteration it + 1's search kernel, so
 // its direction kernel is not followed by k_upd_finish; the last iteration keeps it
-static bool step_finishes(const svnicp_ctx* c, int it) { return !(c->st.defer_fin && it < c->prm.iterations - 1); }
+static bool step_finishes(const svnicp_ctx* c, int it) { return !(c->st.drive.defer_fin && it < c->prm.iterations - 1); }
 
 // side-stream chain: fork the pair statistics of iteration `it` onto the second stream (once per iteration)
 static int fork_median(svnicp_ctx* c, int it) {
-  if (c->st.chain != StepChain::SideStream || c->st.median_pending) return SVNICP_OK;
+  if (c->st.step.chain != StepChain::SideStream || c->st.median_pending) return SVNICP_OK;
   if (const int rc = ensure_dbg_upd(c)) return rc;
   const UpdateArgs u = update_args(c, it);
   HIPCHK(c, hipEventRecord(c->st.ev_fork, c->stream));
@@ -824,17 +733,11 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
   if (c->tune.full_corr) {
     // correspondence = full (the reference's get_correspondence, SVGDICP.cpp:274-298): every particle's transformed source
     // against the WHOLE target, K = 1 — P exact nearest-neighbour searches per iteration through the stage-A machinery
-    if (c->sb.plan.f32 != 3) return fail(c, SVNICP_ERR_INVALID, "correspondence = full needs the split stage B (accum = split, more than 8 particles or knn_count <= 128)");
-    if (!c->sa.plan.can_search(1)) return fail(c, SVNICP_ERR_INVALID, "correspondence = full needs knn_count <= 128 (Morton-tile stage A) or knn = v1");
-    HIPCHK(c, c->sb.full_q.ensure((size_t)c->B * 3)); HIPCHK(c, c->sb.full_d2.ensure((size_t)c->B));
-    HIPCHK(c, c->sb.full_idx.ensure((size_t)c->P * c->B));
-    Pose0 ident{};
-    ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
+    // (svnicp_align_begin has refused what this needs and does not have, and sized full_q / full_d2 / full_idx)
     HIPCHK(c, prof_begin(c, KC_SEARCH));
     for (int p = c->shard.p_lo; p < c->shard.p_hi; ++p) {
       HIPCHK(c, launch_transform_cloud(c->cloud.src.p, c->B, c->st.Rtot.p + 12 * (size_t)p, c->sb.full_q.p, c->st.ctl.p, c->stream));
-      const int rc = c->sa.search(c, stage_a_env(c), c->sb.full_q.p, ident, 1, c->sb.full_idx.p + (size_t)p * c->B, c->sb.full_d2.p, 0, c->B);
-      if (rc) return rc;
+      if (const int rc = c->sa.search_blocks(c, stage_a_env(c), c->sb.full_q.p, c->B, 1, c->sb.full_idx.p + (size_t)p * c->B, c->sb.full_d2.p, 1)) return rc;
     }
     HIPCHK(c, prof_end(c));
     a.full_idx = c->sb.full_idx.p;
@@ -857,13 +760,13 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
     HIPCHK(c, prof_end(c));
     return SVNICP_OK;
   }
-  const bool single = c->st.single_fused;   // the iteration is this one launch
+  const bool single = c->st.step.single_fused;   // the iteration is this one launch
   const UpdateArgs us = update_args(c, it);
   HIPCHK(c, prof_begin(c, KC_ACCUM));
   HIPCHK(c, launch_accumulate(c->sb.plan, a, single ? &us : nullptr, c->stream));
   HIPCHK(c, prof_end(c));
   if (single) { c->st.single_done_it = it; return SVNICP_OK; }
-  if (c->st.chain == StepChain::SmallChain) return SVNICP_OK;   // the update kernels add the workgroups' records themselves
+  if (c->st.step.chain == StepChain::SmallChain) return SVNICP_OK;   // the update kernels add the workgroups' records themselves
   HIPCHK(c, prof_begin(c, KC_REDUCE));
   // one rank: the particle's record; source-row sharding: this rank's slot of the [row_world][P][22] array
   double* rec = c->shard.row_world > 1 ? c->shard.rank_sums.p + (size_t)c->shard.row_rank * c->P * kNSums : c->sb.sums.p;
@@ -883,7 +786,7 @@ int svnicp_iter_update(svnicp_ctx* c, int it) {
   HIPCHK(c, prof_begin(c, KC_UPDATE));
   if (c->tune.debug && it == c->prm.iterations - 1)   // phase cycles of the one-workgroup kernels so far
     if (const int rc = print_update_phases(c, false)) return rc;
-  const StepChain chain = c->st.chain;
+  const StepChain chain = c->st.step.chain;
   if (chain == StepChain::OneKernel) {
     u.svgd = 0;   // the one-workgroup kernels are per mode
     if (c->prm.mode == SVNICP_MODE_SVGD) HIPCHK(c, launch_update_svgd(u, c->stream));
@@ -948,8 +851,10 @@ static int align_enqueue(svnicp_ctx* c, bool follow_stop) {
   if ((rc = svnicp_stage_candidates(c, 0, c->B))) return rc;
   if ((rc = svnicp_build_candidate_table(c))) return rc;
   c->st.small_launched = false;
-  if (c->st.chain == StepChain::SmallChain && c->tune.persistent && !c->prm.record_trace && !c->prof.on && c->prm.iterations > 0 &&
-      small_registration_supported(c->sb.plan.PW, c->sb.plan.WP, c->K)) {
+  const DrivePlan drive = plan_drive(registration_facts(c, c->pl.on), c->tune, c->sb.plan, c->st.step, follow_stop);
+  c->st.drive = drive;
+  c->st.drive.defer_fin = false;   // holds inside the loop below only: not in the persistent kernel, not in a caller's own split-phase loop
+  if (drive.persistent_try) {
     // all iterations in ONE cooperative launch (small_registration.hip: k_small_registration); anything the runtime refuses
     // (no cooperative launch, grid not resident) falls back to the four launches per iteration
     const AccumArgs a = accum_args(c, 0);   // defer_fin is off here: fin_iteration = -1, the search body decides nothing
@@ -963,19 +868,16 @@ static int align_enqueue(svnicp_ctx* c, bool follow_stop) {
     if (e == hipSuccess) { c->st.small_launched = true; return svnicp_finish(c); }
     (void)hipGetLastError();
   }
-  constexpr int kChunk = 4;   // (2: 1.29 ms at the shipped settings against 1.26 — the host then waits more often than it saves launches)
-  const bool follow = follow_stop && c->prm.check_early_stop && c->prm.iterations > 2 * kChunk;
-  if (follow && !c->st.h_flags.p) {
+  c->st.drive.defer_fin = drive.defer_fin;
+  struct Reset { bool& f; ~Reset() { f = false; } } reset_defer{c->st.drive.defer_fin};   // a caller's own split-phase loop keeps k_upd_finish
+  if (drive.follow && !c->st.h_flags.p) {
     HIPCHK(c, c->st.h_flags.alloc(3));
     for (auto& e : c->st.ev_chunk) HIPCHK(c, e.create(hipEventDisableTiming));
   }
-  // early stop: iteration i's decision is taken by iteration i + 1's search kernel (the last iteration keeps k_upd_finish)
-  c->st.defer_fin = c->prm.check_early_stop && !c->prm.record_trace && c->sb.plan.f32 == 3 && !c->tune.full_corr && c->st.chain != StepChain::OneKernel;
-  struct Reset { bool& f; ~Reset() { f = false; } } reset_defer{c->st.defer_fin};
   for (int it = 0; it < c->prm.iterations; ++it) {
     if ((rc = svnicp_iter_accumulate(c, it))) return rc;
     if ((rc = svnicp_iter_update(c, it))) return rc;
-    if (follow && (it + 1) % kChunk == 0) {
+    if (drive.follow && (it + 1) % kChunk == 0) {
       const int chunk = it / kChunk, slot = chunk % 3;
       HIPCHK(c, hipMemcpyAsync(&c->st.h_flags.p[slot], c->st.ctl.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipEventRecord(c->st.ev_chunk[slot], c->stream));
@@ -1136,14 +1038,14 @@ int svnicp_get_knn_survivors(svnicp_ctx* c, int32_t* outB) {
 
 int svnicp_get_ambiguous_steps(svnicp_ctx* c, int* out) {
   NEED_RESULT(c);
-  if (c->sb.accum_mode == 0) { *out = -1; return SVNICP_OK; }
+  if (c->sb.plan.f32 == 0) { *out = -1; return SVNICP_OK; }
   return fetch(c, out, c->sb.ambig.p, sizeof(int));
 }
 
 int svnicp_get_ambiguous_pairs(svnicp_ctx* c, int64_t* out) {
   CTX_CHECK(c);
   if (!c->run.have_result || !out) return fail(c, SVNICP_ERR_INVALID, "no registration result yet");
-  if (c->sb.accum_mode != 3 || c->sb.plan.f32 != 3) { *out = -1; return SVNICP_OK; }   // counted by the bf16 search kernel only
+  if (c->sb.plan.f32 != 3) { *out = -1; return SVNICP_OK; }   // counted by the bf16 search kernel only
   int v[2] = {0, 0};
   const int rc = fetch(c, v, c->sb.ambig.p, sizeof v);
   *out = v[1];
@@ -1346,13 +1248,7 @@ int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_
   const StageAEnv env{c->stream, c->tune, c->num_cus, false, c->cloud.tgt.p, c->B, c->M, c->pose0};
   if (!c->sa.stage_kept)
     if (const int rc = c->sa.keep_stage_fallbacks(c, env)) return rc;
-  Pose0 ident{};
-  ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
-  const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(c->sa.plan.rows, B));
-  for (int64_t lo = 0; lo < B; lo += rows) {
-    const int64_t n = std::min<int64_t>(rows, B - lo);
-    if (const int rc = c->sa.search(c, env, ev.q.p + 3 * lo, ident, 1, ev.idx.p + lo, ev.d2.p + lo, 0, n)) return rc;
-  }
+  if (const int rc = c->sa.search_blocks(c, env, ev.q.p, B, 1, ev.idx.p, ev.d2.p, 1)) return rc;
   const bool normals = c->pl.supplied || c->pl.estimated;
   EvalArgs a{};
   a.q = ev.q.p; a.tgt = c->cloud.tgt.p; a.rec = normals ? c->pl.rec.p : nullptr; a.B = B; a.M = M;

@@ -1,6 +1,7 @@
 // kernels.hpp — argument blocks and host launchers of the HIP kernels (internal to libsvnicp_hip.so)
 #pragma once
 #include "device_math.hpp"
+#include "registration_plan.hpp"
 #include "stage_a_plan.hpp"
 
 namespace svnicp {
@@ -153,35 +154,9 @@ struct AccumArgs {
   float* fin_history;                 // [I][6][P]
   int* fin_ctl;                       // [0] stop flag, [1] finish_iter
 };
-struct AccumPlan { int PW, WP, TP, grid_x, grid_y, tiles_per_block, Ppad, RS, f32, K, sgrid_x, pts_per_block, spts_per_block; int64_t n_tiles; size_t smem;
-                   int small; /* split variant, few (point, particle) pairs: at most kSmallChainBlocks accumulate workgroups, see api.hip small_chain */ };
-constexpr int kSmallChainBlocks = 32;
-// f32: 0 = float64 baseline, 1 = float32 VALU search (fused with the accumulation), 3 = bf16 matrix-pipe search kernel +
-// accumulation kernel (falls back to 1 when K > 128 or the shard has <= 8 particles)
-// test / profiling knobs of a context (svnicp_set_option); the defaults are the product configuration
-struct Tuning {
-  KnnOption knn;                 // stage A kernel: automatic, or v1 | v2 | tiles | brute (stage_a_plan.hpp: plan_stage_a)
-  int fallback_sliced_max = -1;  // stage A: failed queries redone by target slices up to this many (-1 default)
-  int accum = 3;                 // stage B: 0 f64 baseline, 1 f32 VALU search (fused), 3 search + accumulate kernels
-  int update_fused = 0;          // Stein update: 1 = one fused kernel for 2 <= P <= fused_update_max_p
-  int fused_update_max_p = 128;  // above this the Stein step runs as workgroup-parallel kernels
-  int wgpcu_search = 0, wgpcu_accum = 0;   // workgroups per CU the stage-B grids are sized for (0 = automatic)
-  int tp = 0;                    // fused stage-B variants: source points per LDS tile (0 = automatic)
-  int accum_min_steps = 0;       // least wave steps per accumulate workgroup (0 = default 4)
-  int group_stride = 0;          // stage A scan: group order stride (0 = default, 1 = natural order)
-  int scan_split = 0;            // stage A scan: waves per 64-query workgroup, 4 or 8 (0 = default)
-  int debug = 0;                 // print plans and per-phase cycle counters to stderr
-  int single_fused = 1;          // one particle: reduce + Stein step in the accumulate kernel's last workgroup (0: three launches, A/B)
-  int small_chain = 1;           // small registrations: no k_reduce_partials, Stein-step front in one launch on the main stream (0: the general chain, A/B)
-  int persistent = 0;            // 1: svnicp_align runs all iterations of a small-chain registration in ONE cooperative launch (k_small_registration;
-                                 // measured SLOWER than the four launches per iteration on this eight-XCD part: off by default, option chain=persistent)
-  int median_inline = -1;        // pair statistics in the prepare kernel's launch on the main stream also in the general chain: -1 automatic (P <= 128), 0 never (second stream), 1 the same as automatic
-  int brute_qb = 0;              // brute-force stage A: queries per workgroup, 0 automatic (knn_brute_queries_per_block)
-  int full_corr = 0;             // 1: correspondence = full — per-particle exact NN over the whole target (SVGDICP.cpp:274-298)
-  int force_split = 0;           // plan only (never an option): the split stage B for any particle count — the point-to-plane
-                                 // accumulate kernel consumes the search kernel's winner index (api.hip, plane mode)
-};
-AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f32, const Tuning& tune);
+// completes the registration's stage-B plan (registration_plan.hpp: plan_stage_b — variant, shape, `small`) with what depends
+// on the device: the grids of B rows per iteration from the kernels' occupancy, the LDS tiles of the fused variants
+AccumPlan plan_accumulate(AccumPlan shape, int64_t B, int num_cus, const Tuning& tune);
 hipError_t launch_search_split(const AccumPlan& plan, AccumArgs a, hipStream_t st);         // split variant, kernel 1
 hipError_t launch_accumulate_split(const AccumPlan& plan, const AccumArgs& a, hipStream_t st);  // split variant, kernel 2 (via launch_accumulate)
 void split_occupancy_blocks(int PW, int WP, int K, size_t smem, int* search, int* accum);
@@ -228,7 +203,6 @@ struct BeginZero { unsigned int* ptr[6]; unsigned int dwords[6]; int n; int* ctl
 hipError_t launch_init_particles(const double* init6xP, int P, const Pose0& pose, int mode, double* R, double* t,
                                  double* Rtot, double* pose_out, int refresh_pose, double* eul, hipStream_t st, const BeginZero* zero = nullptr);
 // stage B accumulate (fused variants: whole stage B); single: see stein_iter.hip — the one-particle iteration in one launch
-bool accumulate_can_fuse_single(const AccumPlan& plan);
 int single_particle_grid(int64_t B);   // workgroups of the one-particle iteration kernel (rows of `partial` it writes)
 hipError_t launch_accumulate(const AccumPlan& plan, AccumArgs a, const UpdateArgs* single, hipStream_t st);
 hipError_t launch_update_svgd(const UpdateArgs& a, hipStream_t st);
@@ -239,7 +213,6 @@ hipError_t launch_update_median(const UpdateArgs& a, int num_cus, int max_p_one_
 hipError_t launch_update_prepare(const UpdateArgs& a, hipStream_t st);
 hipError_t launch_update_prepare_median(const UpdateArgs& a, hipStream_t st);   // small chain: both in one launch (2 <= P <= 128)
 // small chain, all iterations in one cooperative launch (small_registration.hip: k_small_registration)
-bool small_registration_supported(int PW, int WP, int K);
 hipError_t launch_small_registration(const AccumPlan& plan, AccumArgs a, const UpdateArgs& u, int iterations, unsigned int* bar,
                                      int num_cus, hipStream_t st);
 hipError_t launch_update_direction(const UpdateArgs& a, hipStream_t st, bool finish = true);   // finish: k_upd_finish behind it when the step needs one
@@ -305,7 +278,6 @@ struct MinibatchArgs {
   double* src_u;                // [n_q][3] unique rows, then copies of the last one
   int64_t n_q;                  // queries stage A runs: min(B, n)
 };
-constexpr int64_t kMinibatchMaxRows = 1ll << 22;   // iterations * batch: about 2.5 KB of per-row tables each (10 GB)
 unsigned long long minibatch_stream_base(unsigned long long seed, unsigned long long registration);
 int64_t minibatch_scan_blocks(int64_t B);
 // memsets + draw/mark + scan + compaction + fill of src_u; no host synchronisation

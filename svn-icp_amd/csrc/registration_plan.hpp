@@ -1,0 +1,225 @@
+// registration_plan.hpp — the rules of a registration behind stage A: how many rows each part works on, what is refused,
+// which stage-B variant and shape the particle shard gets, which launches carry the Stein step and how svnicp_align drives
+// them (host only; no HIP needed, so the CPU tests compile it on its own).  Pure functions of the options (Tuning) and of
+// the facts svnicp_align_begin reads off the context (RegistrationFacts); plan_accumulate (stein_iter.hip) only completes
+// the shape with the device-dependent grid sizes.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
+
+#include "stage_a_plan.hpp"
+
+namespace svnicp {
+
+// test / profiling knobs of a context (svnicp_set_option); the defaults are the product configuration
+struct Tuning {
+  KnnOption knn;                 // stage A kernel: automatic, or v1 | v2 | tiles | brute (stage_a_plan.hpp: plan_stage_a)
+  int fallback_sliced_max = -1;  // stage A: failed queries redone by target slices up to this many (-1 default)
+  int accum = 3;                 // stage B: 0 f64 baseline, 1 f32 VALU search (fused), 3 search + accumulate kernels
+  int update_fused = 0;          // Stein update: 1 = one fused kernel for 2 <= P <= fused_update_max_p
+  int fused_update_max_p = 128;  // above this the Stein step runs as workgroup-parallel kernels
+  int wgpcu_search = 0, wgpcu_accum = 0;   // workgroups per CU the stage-B grids are sized for (0 = automatic)
+  int tp = 0;                    // fused stage-B variants: source points per LDS tile (0 = automatic)
+  int accum_min_steps = 0;       // least wave steps per accumulate workgroup (0 = default 4)
+  int group_stride = 0;          // stage A scan: group order stride (0 = default, 1 = natural order)
+  int scan_split = 0;            // stage A scan: waves per 64-query workgroup, 4 or 8 (0 = default)
+  int debug = 0;                 // print plans and per-phase cycle counters to stderr
+  int single_fused = 1;          // one particle: reduce + Stein step in the accumulate kernel's last workgroup (0: three launches, A/B)
+  int small_chain = 1;           // small registrations: no k_reduce_partials, Stein-step front in one launch on the main stream (0: the general chain, A/B)
+  int persistent = 0;            // 1: svnicp_align runs all iterations of a small-chain registration in ONE cooperative launch (k_small_registration;
+                                 // measured SLOWER than the four launches per iteration on this eight-XCD part: off by default, option chain=persistent)
+  int median_inline = -1;        // pair statistics in the prepare kernel's launch on the main stream also in the general chain: -1 automatic (P <= 128), 0 never (second stream), 1 the same as automatic
+  int brute_qb = 0;              // brute-force stage A: queries per workgroup, 0 automatic (knn_brute_queries_per_block)
+  int full_corr = 0;             // 1: correspondence = full — per-particle exact NN over the whole target (SVGDICP.cpp:274-298)
+};
+
+// what the rules read of the context besides its options, at svnicp_align_begin
+struct RegistrationFacts {
+  int P = 0, K = 0, I = 0;             // particles, knn_count, params.iterations
+  int64_t B = 0, M = 0;                // source and target rows
+  bool svgd = false, check_early_stop = false, record_trace = false;
+  bool profiling = false;              // svnicp_set_profile
+  bool shard_set = false;              // svnicp_set_shard: this context's particles are [p_lo, p_hi), else [0, P)
+  int p_lo = 0, p_hi = 0;
+  int row_world = 1;                   // svnicp_set_row_shard
+  int batch = 0;                       // svnicp_set_minibatch, 0 = off
+  bool explicit_tab = false;           // … with a caller's table of tab_I iterations
+  int tab_I = 0;
+  bool plane = false;                  // svnicp_set_residual: point-to-plane
+  bool normals_supplied = false;
+  int normal_k = 16;
+  int nshard() const { return p_hi - p_lo; }
+  bool whole_shard() const { return p_lo == 0 && p_hi == P; }
+};
+
+// ---------------- row counts ----------------
+constexpr int64_t kMinibatchMaxRows = 1ll << 22;   // iterations * batch: about 2.5 KB of per-row tables each (10 GB)
+struct RegistrationRows {
+  bool mb;       // this registration runs on a mini-batch table
+  int64_t Bq;    // rows stage A runs on (mini-batch: no more than the table can draw)
+  int64_t Bt;    // rows of the candidate tables (mini-batch: one per table position, epoch-major)
+  int64_t Bi;    // rows one iteration works on
+};
+inline RegistrationRows registration_rows(int batch, int I, int64_t B) {
+  if (batch == 0 || I <= 0) return {false, B, B, B};
+  const int64_t n = (int64_t)I * batch;
+  return {true, B < n ? B : n, n, batch};
+}
+
+// ---------------- refusals ----------------
+// Each ladder is a list of (condition, reason): the first condition that holds is the one reported.
+struct Refusal { bool holds; const char* why; };
+inline const char* first_refusal(std::initializer_list<Refusal> ladder) {
+  for (const Refusal& r : ladder)
+    if (r.holds) return r.why;
+  return nullptr;
+}
+constexpr const char* kMinibatchRefusal = "svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ";
+constexpr const char* kPlaneRefusal = "svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ";
+
+// mini-batch: what it is not combined with (nullptr: nothing, or mini-batch is off)
+inline const char* minibatch_refusal(const RegistrationFacts& f, const Tuning& t) {
+  if (f.batch == 0) return nullptr;
+  return first_refusal({
+      {f.batch < 0, "batch_size must be positive"},
+      {f.shard_set && !f.whole_shard(), "a partial particle shard (svnicp_set_shard) is set"},
+      {f.row_world > 1, "a source-row shard (svnicp_set_row_shard) is set"},
+      {t.full_corr != 0, "option correspondence=full is set"},
+      {t.persistent != 0, "option chain=persistent is set"},
+      {(int64_t)f.I * f.batch > kMinibatchMaxRows, "iterations * batch_size exceeds 2^22 table rows (about 2.5 KB of tables per row)"},
+      {f.explicit_tab && f.tab_I != f.I, "the explicit index table's iteration count differs from params.iterations"},
+  });
+}
+// point-to-plane residual: what it is not combined with (all left for later).  What passes has accum = split, K <= 128 and
+// the whole shard: stage_b_variant then gives the split kernels for any particle count.
+inline const char* plane_refusal(const RegistrationFacts& f, const Tuning& t) {
+  if (!f.plane) return nullptr;
+  return first_refusal({
+      {f.svgd, "SVGD mode has no Hessian to put the plane residual in"},
+      {f.shard_set && !f.whole_shard(), "a partial particle shard (svnicp_set_shard) is set"},
+      {f.row_world > 1, "a source-row shard (svnicp_set_row_shard) is set: the rank exchange carries the 22 point-to-point sums"},
+      {f.batch != 0, "mini-batch mode (svnicp_set_minibatch) is set"},
+      {t.full_corr != 0, "option correspondence=full is set"},
+      {t.persistent != 0, "option chain=persistent is set"},
+      {t.accum != 3, "option accum is not split: the plane kernel consumes the search kernel's winner index"},
+      {f.K > 128, "knn_count exceeds 128: the plane kernel consumes the matrix-pipe search kernel's winner index"},
+      {!f.normals_supplied && f.M < f.normal_k, "the target has fewer points than normal_k and no normals were supplied"},
+  });
+}
+// correspondence = full (the whole message): its per-particle searches feed the split accumulate kernel and run through
+// stage A's working set with K = 1 (stage_a_k1: StageAPlan::can_search(1)).  An empty particle shard searches nothing.
+inline const char* full_corr_refusal(const RegistrationFacts& f, const Tuning& t, int variant, bool stage_a_k1) {
+  if (!t.full_corr || f.nshard() <= 0) return nullptr;
+  return first_refusal({
+      {variant != 3, "correspondence = full needs the split stage B (accum = split, more than 8 particles or knn_count <= 128)"},
+      {!stage_a_k1, "correspondence = full needs knn_count <= 128 (Morton-tile stage A) or knn = v1"},
+  });
+}
+
+// ---------------- stage B: variant and shape ----------------
+struct AccumPlan { int PW, WP, TP, grid_x, grid_y, tiles_per_block, Ppad, RS, f32, K, sgrid_x, pts_per_block, spts_per_block; int64_t n_tiles; size_t smem;
+                   int small; /* split variant, few (point, particle) pairs: at most kSmallChainBlocks accumulate workgroups (small_registration) */ };
+constexpr int kSmallChainBlocks = 32;
+
+// AccumPlan::f32: 0 = float64 baseline, 1 = float32 VALU search (fused with the accumulation), 3 = bf16 matrix-pipe search
+// kernel + accumulation kernel.  Option accum asks; the MFMA tiles are 16 particles wide and 128 candidate rows deep, so
+// K > 128 and shards of <= 8 particles get the fused f32 kernels instead — except that correspondence = full and the
+// point-to-plane residual consume the split kernels' winner index and keep them for any particle count.
+inline int stage_b_variant(int accum, int K, int nshard, bool full_corr, bool plane) {
+  if (accum != 3) return accum;
+  if (nshard <= 0 || K > 128 || (nshard <= 8 && !full_corr && !plane)) return 1;
+  return 3;
+}
+// particles per wave (PW), waves along the particles (WP), workgroups along the particles, row stride; an empty shard has
+// a variant and no grid
+inline AccumPlan stage_b_shape(int variant, int nshard, int K) {
+  AccumPlan pl{};
+  pl.f32 = variant;
+  if (nshard <= 0) return pl;
+  int PW = variant == 3 ? 16 : 8;
+  while (PW < 64 && PW < nshard) PW <<= 1;
+  int WP = 1;
+  if (PW == 64) { WP = (nshard + 63) / 64; if (WP >= 3) WP = 4; }
+  pl.PW = PW; pl.WP = WP; pl.K = K;
+  pl.grid_y = (nshard + PW * WP - 1) / (PW * WP);
+  pl.Ppad = pl.grid_y * PW * WP;
+  pl.RS = (3 * K) | 1;
+  return pl;
+}
+// small registration (few pairs, one context holds everything, 2 <= P <= 128): the accumulate kernel runs at most
+// kSmallChainBlocks workgroups (plan_accumulate clamps its grid), so the update kernels add their records themselves
+inline bool small_registration(const AccumPlan& shape, const RegistrationFacts& f, const Tuning& t, int64_t Bi) {
+  return shape.f32 == 3 && shape.grid_y == 1 && Bi * f.nshard() <= (1 << 19) && t.small_chain && f.P >= 2 && f.P <= 128 &&
+         f.P <= t.fused_update_max_p && !t.update_fused && f.row_world == 1 && f.whole_shard() && !t.full_corr && !f.plane;
+}
+// the stage-B plan of a registration as far as it does not depend on the device
+inline AccumPlan plan_stage_b(const RegistrationFacts& f, const Tuning& t, int64_t Bi) {
+  AccumPlan pl = stage_b_shape(stage_b_variant(t.accum, f.K, f.nshard(), t.full_corr != 0, f.plane), f.nshard(), f.K);
+  pl.small = small_registration(pl, f, t, Bi) ? 1 : 0;
+  return pl;
+}
+
+// ---------------- the Stein step ----------------
+// which launches carry the Stein step of 2 <= P particles (P = 1 and option update=fused: OneKernel); chosen once per
+// registration by plan_step at the end of svnicp_align_begin
+enum class StepChain {
+  // P = 1 (no pair statistics) and option update=fused: the whole Stein step is one one-workgroup kernel on the main stream
+  OneKernel,
+  // few (point, particle) pairs: the accumulate kernel runs at most kSmallChainBlocks workgroups, nothing reduces their records
+  // (the prepare lanes add them), and the pair statistics share the prepare kernel's launch on the main stream
+  SmallChain,
+  // general chain, up to 128 particles (the one-workgroup pair statistics): they run as the last workgroup of the prepare
+  // kernel's launch on the main stream.  The second stream hid their 12 us behind the search kernel, but its fork and join
+  // (event record / wait on both sides, one more launch) cost more: C3 7.25 -> 6.99 ms, C2 2.72 -> 2.56 ms per registration,
+  // and 0.25 ms less host time to enqueue a registration.  Above 128 particles the three-kernel chain stays on the second stream.
+  InlineMedian,
+  // the pair statistics of iteration `it` (bandwidth h from the exact median of the pair distances): they depend on the
+  // poses only, so they are forked onto the second stream at the START of the iteration and run beside the search and
+  // accumulate kernels; svnicp_iter_update joins before the Stein direction
+  SideStream,
+};
+constexpr int kMedianInlineMaxP = 128;   // the one-workgroup pair statistics
+
+struct StepPlan {
+  StepChain chain = StepChain::OneKernel;
+  // ONE particle, no exchange between ranks ahead, the fused f32 kernel: its last workgroup reduces the partial sums and
+  // runs the Stein step (for P = 1 the Newton step and the pose update) — the iteration is this one launch
+  bool single_fused = false;
+};
+// from the options and the stage-B plan of the registration (its variant and `small`)
+inline StepPlan plan_step(const RegistrationFacts& f, const Tuning& t, const AccumPlan& pl) {
+  StepPlan s;
+  if (f.P < 2 || (t.update_fused && f.P <= t.fused_update_max_p)) s.chain = StepChain::OneKernel;
+  else if (pl.small) s.chain = StepChain::SmallChain;
+  else if (f.P <= kMedianInlineMaxP && f.P <= t.fused_update_max_p && t.median_inline != 0) s.chain = StepChain::InlineMedian;
+  else s.chain = StepChain::SideStream;
+  s.single_fused = f.P == 1 && !f.svgd && f.row_world == 1 && f.p_lo == 0 && f.p_hi == 1 && !t.full_corr && t.single_fused && pl.f32 == 1 &&
+                   !f.plane;
+  return s;
+}
+
+// (PW, WP) of the plan and knn_count for which the persistent kernel is instantiated (small_registration.hip:
+// launch_small_registration; the others run the four-launch chain)
+inline bool small_registration_supported(int PW, int WP, int K) {
+  return K >= 97 && K <= 100 && ((WP == 1 && (PW == 16 || PW == 32 || PW == 64)) || (PW == 64 && WP == 2));
+}
+
+// ---------------- how svnicp_align / svnicp_align_async drive the iterations ----------------
+// blocking svnicp_align with early stop: the stop flag follows every kChunk iterations into pinned memory
+constexpr int kChunk = 4;   // (2: 1.29 ms at the shipped settings against 1.26 — the host then waits more often than it saves launches)
+struct DrivePlan {
+  bool persistent_try = false;   // all iterations in ONE cooperative launch, if the runtime takes it
+  bool defer_fin = false;        // early stop: iteration i's decision is taken by iteration i + 1's search kernel (the last iteration keeps k_upd_finish)
+  bool follow = false;           // the host enqueues in chunks and stops soon after the device has
+};
+inline DrivePlan plan_drive(const RegistrationFacts& f, const Tuning& t, const AccumPlan& pl, const StepPlan& s, bool blocking) {
+  DrivePlan d;
+  d.persistent_try = s.chain == StepChain::SmallChain && t.persistent && !f.record_trace && !f.profiling && f.I > 0 &&
+                     small_registration_supported(pl.PW, pl.WP, f.K);
+  d.defer_fin = f.check_early_stop && !f.record_trace && pl.f32 == 3 && !t.full_corr && s.chain != StepChain::OneKernel;
+  d.follow = blocking && f.check_early_stop && f.I > 2 * kChunk;
+  return d;
+}
+
+}  // namespace svnicp

@@ -134,11 +134,6 @@ hipError_t launch_small_t(const AccumArgs& a, const UpdateArgs& u, const SmallAr
 }
 }  // namespace
 
-// (PW, WP) of the plan and knn_count for which the persistent kernel is instantiated (the others run the four-launch chain)
-bool small_registration_supported(int PW, int WP, int K) {
-  return K >= 97 && K <= 100 && ((WP == 1 && (PW == 16 || PW == 32 || PW == 64)) || (PW == 64 && WP == 2));
-}
-
 // all iterations of a small registration in one cooperative launch; `bar`: three zeroed words (arrivals, generation, error)
 hipError_t launch_small_registration(const AccumPlan& plan, AccumArgs a, const UpdateArgs& u, int iterations, unsigned int* bar,
                                      int num_cus, hipStream_t st) {
@@ -162,6 +157,8 @@ hipError_t launch_small_registration(const AccumPlan& plan, AccumArgs a, const U
   if (grid > num_cus) return hipErrorCooperativeLaunchTooLarge;
   const size_t smem_median = median_lds_bytes(P);
   const size_t smem = smem_median > plan.smem ? smem_median : plan.smem;
+  // small_registration_supported (registration_plan.hpp) names exactly the (PW, WP) instantiated below; NRB = 6 search row
+  // blocks cover its 97 <= knn_count <= 100
   if (!small_registration_supported(plan.PW, plan.WP, plan.K)) return hipErrorInvalidValue;
   if (plan.PW == 16) return launch_small_t<16, 1, 6, true>(a, u, s, grid, smem, st);
   if (plan.PW == 32) return launch_small_t<32, 1, 6, true>(a, u, s, grid, smem, st);

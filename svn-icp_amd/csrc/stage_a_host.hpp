@@ -55,9 +55,10 @@ struct StageA {
   // registration included, whose neighbour counts are Ks (K itself, normal_k of a normal pass, 1 of correspondence = full) —
   // and (re)build the target copies when they do not hold the layout the kernel wants.  DevBuf::ensure is a compare when
   // the buffer is large enough, so a steady state allocates nothing.
+  static StageAPlan plan_for(const StageAEnv& e, int64_t rows, int K) { return plan_stage_a(rows, e.M, K, e.tune.knn, e.tune.fallback_sliced_max); }
   template <class Obj>
   int begin(Obj* o, const StageAEnv& e, int64_t rows, int K, std::initializer_list<int> Ks) {
-    plan = plan_stage_a(rows, e.M, K, e.tune.knn, e.tune.fallback_sliced_max);
+    plan = plan_for(e, rows, K);
     stage_kept = false;
     const size_t Bq = (size_t)rows, B = (size_t)e.B, M = (size_t)e.M, Mp = (size_t)plan.Mp;
     size_t S = 0, slice_entries = 0;
@@ -232,6 +233,26 @@ struct StageA {
     }
     case KnnKernel::Stream:
       HIPCHK(o, launch_knn_topk(a, e.stream));
+    }
+    return SVNICP_OK;
+  }
+
+  // A later search of the registration's working set: the exact top-Kq of q[0, n) (already in the target's frame: the
+  // identity pose) in blocks of the rows the scratch is sized for (a mini-batch registration sizes it for fewer than B).
+  // Every block writes to out_idx / out_d2 + out_step * Kq * (its first row) — out_step 1: one [n][Kq] result, 0: every
+  // block into the same block_rows(n) rows, which done(first row, rows) consumes behind its search (the normal pass: [n][Kq]
+  // of a whole target would be gigabytes).  The caller has asked plan.can_search(Kq).
+  int64_t block_rows(int64_t n) const { return std::max<int64_t>(1, std::min<int64_t>(plan.rows, n)); }
+  template <class Obj, class Done = int (*)(int64_t, int64_t)>
+  int search_blocks(Obj* o, const StageAEnv& e, const double* q, int64_t n, int Kq, int32_t* out_idx, double* out_d2, int out_step,
+                    Done done = [](int64_t, int64_t) { return 0; }) {
+    Pose0 ident{};
+    ident.R0[0] = ident.R0[4] = ident.R0[8] = 1.0;
+    const int64_t rows = block_rows(n);
+    for (int64_t lo = 0; lo < n; lo += rows) {
+      const int64_t cnt = std::min<int64_t>(rows, n - lo), off = lo * out_step * Kq;
+      if (const int rc = search(o, e, q + 3 * lo, ident, Kq, out_idx + off, out_d2 + off, 0, cnt)) return rc;
+      if (const int rc = done(lo, cnt)) return rc;
     }
     return SVNICP_OK;
   }

@@ -538,22 +538,11 @@ static int occupancy_blocks(const AccumPlan& pl) {
   }
 }
 
-AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f32, const Tuning& tune) {
-  AccumPlan pl{};
-  // MFMA tiles: 16 particles wide, 128 candidate rows; correspondence = full and the point-to-plane residual keep the split kernels for any particle count
-  if (f32 == 3 && (K > 128 || (n_particles <= 8 && !tune.full_corr && !tune.force_split))) f32 = 1;
-  pl.f32 = f32;
-  int PW = f32 == 3 ? 16 : 8;
-  while (PW < 64 && PW < n_particles) PW <<= 1;
-  int WP = 1;
-  if (PW == 64) { WP = (n_particles + 63) / 64; if (WP >= 3) WP = 4; }
-  pl.PW = PW; pl.WP = WP; pl.K = K;
+AccumPlan plan_accumulate(AccumPlan pl, int64_t B, int num_cus, const Tuning& tune) {
+  const int f32 = pl.f32, PW = pl.PW, WP = pl.WP, K = pl.K;
   const int per_wg = PW * WP;
-  pl.grid_y = (n_particles + per_wg - 1) / per_wg;
-  pl.Ppad = pl.grid_y * per_wg;
   const int BW = 64 / PW, WB = 4 / WP;
   const int pass = BW * WB;                  // points per workgroup pass
-  pl.RS = (3 * K) | 1;
   if (f32 == 3) {  // split variant: no LDS tiles; each kernel gets one resident round of workgroups (search: two)
     const int64_t steps = (B + pass - 1) / pass;
     auto size_grid = [&](int wg_per_cu, int* gx, int* ppb, int min_steps) {
@@ -581,8 +570,7 @@ AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f3
     }
     size_grid(occ_a, &pl.grid_x, &pl.pts_per_block, tune.accum_min_steps > 0 ? tune.accum_min_steps : 4);
     // few pairs (the scan-to-map loop's sizes): at most kSmallChainBlocks accumulate workgroups, so that the update kernels can
-    // add their records themselves and k_reduce_partials is not launched (api.hip: small_chain)
-    pl.small = (pl.grid_y == 1 && (int64_t)B * n_particles <= (1 << 19) && tune.small_chain) ? 1 : 0;
+    // add their records themselves and k_reduce_partials is not launched (registration_plan.hpp: small_registration)
     if (pl.small && pl.grid_x > kSmallChainBlocks) {
       const int64_t spb = (steps + kSmallChainBlocks - 1) / kSmallChainBlocks;
       pl.pts_per_block = (int)(spb * pass);
@@ -620,7 +608,6 @@ AccumPlan plan_accumulate(int n_particles, int64_t B, int K, int num_cus, int f3
 // single != nullptr (one particle, fused f32 plan, no exchange between ranks): k_icp_single runs the whole iteration — its
 // last workgroup also reduces the partial sums and runs the Stein step, the caller launches neither k_reduce_partials nor an
 // update kernel
-bool accumulate_can_fuse_single(const AccumPlan& plan) { return plan.f32 == 1; }
 int single_particle_grid(int64_t B) { return (int)((B + 63) / 64); }
 hipError_t launch_accumulate(const AccumPlan& plan, AccumArgs a, const UpdateArgs* single, hipStream_t st) {
   a.TP = plan.TP; a.RS = plan.RS; a.tiles_per_block = plan.tiles_per_block; a.n_tiles = plan.n_tiles;

@@ -267,6 +267,19 @@ def test_full_correspondence_mode_refusals(hip):
         s.stein_align()
     with pytest.raises(Exception):
         s.set_option("correspondence", "sometimes")
+    # split-phase: the refusal comes from svnicp_align_begin (not from the first svnicp_iter_accumulate), and the context is
+    # usable again once the option is off
+    L = hip.load_library()
+    assert L.svnicp_align_begin(s.handle) == -1      # SVNICP_ERR_INVALID
+    assert L.svnicp_last_error(s.handle).decode() == \
+        "correspondence = full needs the split stage B (accum = split, more than 8 particles or knn_count <= 128)"
+    s.set_option("correspondence", "fast")
+    assert L.svnicp_align_begin(s.handle) == 0, L.svnicp_last_error(s.handle)
+    assert L.svnicp_stage_candidates(s.handle, 0, 300) == 0 and L.svnicp_build_candidate_table(s.handle) == 0
+    for it in range(2):
+        assert L.svnicp_iter_accumulate(s.handle, it) == 0 and L.svnicp_iter_update(s.handle, it) == 0
+    assert L.svnicp_finish(s.handle) == 0 and L.svnicp_synchronize(s.handle) == 0
+    assert np.isfinite(s.get_transformation()).all()
 
 # ------------------------------------------------------------------ stage A variants
 @pytest.mark.parametrize("B,M,K", [(700, 20000, 7), (300, 9000, 1), (1000, 16384, 128), (513, 8192, 100), (64, 40000, 33),
