@@ -324,6 +324,10 @@ int svnicp_map_add_cloud(svnicp_map *map, const float *xyz, int64_t n, int mem_k
 /* points svnicp_map_add_cloud has not stored since creation / clear because they lie outside +-2^20 voxels or are NaN
  * (the reference would index a voxel for them; here they are counted and the call still succeeds) */
 int svnicp_map_skipped_points(svnicp_map *map, int64_t *out);
+/* the hash table as the host knows it (test tap, no device work): slots of the table, tombstones counted by the statistics the
+ * last modifying call read back, and table rebuilds (growth or tombstone clearing) since creation — svnicp_map_clear keeps
+ * the capacity and the rebuild count.  Any out pointer may be NULL. */
+int svnicp_map_table_info(svnicp_map *map, int64_t *capacity_slots, int64_t *tombstones, int64_t *rebuilds);
 /* VoxelHashMap::GetMap(pose, max_range) — VoxelHashMap.cpp:48-58; center NULL or max_range < 0: GetMap() (:44-46).
  * The points are written as float64 [count][3] rows into a device buffer owned by the map (valid until the next query),
  * voxels in ascending (x, y, z) index, points of a voxel in insertion order. */

@@ -436,6 +436,7 @@ struct svnicp_map {
   int64_t last_live = 0;
   int64_t nrm_M = 0;     // rows of nrm that belong to the last query (0 until svnicp_map_query_normals ran for it)
   int64_t skipped = 0;   // points svnicp_map_add_cloud did not store (outside the index range or NaN), since creation / clear
+  int64_t rebuilds = 0;  // rebuild() calls since creation (svnicp_map_table_info)
   int h_stats[4] = {0, 0, 0, 0};
   std::string err;
   static std::string& create_error() { thread_local std::string s; return s; }   // svnicp_map_last_error(nullptr)
@@ -475,6 +476,7 @@ int rebuild(svnicp_map* m, int64_t new_cap) {
   HIPCHK(m, hipStreamSynchronize(m->stream));
   m->keys = std::move(nk); m->counts = std::move(nc); m->pts = std::move(np);
   m->cap = new_cap;
+  ++m->rebuilds;
   return 0;
 }
 }  // namespace
@@ -533,6 +535,14 @@ int svnicp_map_clear(svnicp_map* m) {
 int svnicp_map_skipped_points(svnicp_map* m, int64_t* out) {
   if (!m || !out) return SVNICP_ERR_INVALID;
   *out = m->skipped;
+  return SVNICP_OK;
+}
+
+int svnicp_map_table_info(svnicp_map* m, int64_t* capacity_slots, int64_t* tombstones, int64_t* rebuilds) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (capacity_slots) *capacity_slots = m->cap;
+  if (tombstones) *tombstones = m->h_stats[1];
+  if (rebuilds) *rebuilds = m->rebuilds;
   return SVNICP_OK;
 }
 

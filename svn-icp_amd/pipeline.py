@@ -499,6 +499,13 @@ class DeviceVoxelHashMap:
         self._chk(self._L.svnicp_map_skipped_points(self._h, self._C.byref(n)), "svnicp_map_skipped_points")
         return int(n.value)
 
+    def table_info(self):
+        """-> (capacity in slots, tombstones after the last modifying call, table rebuilds since creation) (test tap)."""
+        C = self._C
+        cap, tomb, reb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.svnicp_map_table_info(self._h, C.byref(cap), C.byref(tomb), C.byref(reb)), "svnicp_map_table_info")
+        return int(cap.value), int(tomb.value), int(reb.value)
+
     def add_pointcloud(self, cloud: np.ndarray, pose: np.ndarray):
         C = self._C
         pts = np.ascontiguousarray(np.asarray(cloud, np.float32)[:, :3])

@@ -9,6 +9,7 @@ import map_normals_reference as mr
 
 SHIFT = np.array([3000.0, -2000.0, 50.0])
 DRIVE_VOXEL, DRIVE_MAX_POINTS = 0.5, 20
+DENSE = {"dense65": (65, 6000), "dense130": (130, 9000), "dense256": (256, 12000)}      # name -> (max_points, points drawn)
 
 
 def _pose(R, t):
@@ -63,6 +64,15 @@ def case_inputs(name):
         nodes = nodes[rng.random(nodes.shape[0]) < 0.5]
         rng.shuffle(nodes)
         return 1.0, 20, 1e9, [((nodes * 0.25).astype(np.float32), np.eye(4))]
+    if name in DENSE:
+        # voxels of more than 64 points (the second 64-point block of k_map_normals) up to max_points itself, filled over three
+        # calls; blocks from a few dozen candidates (fewer than normal_k 64: no normal) to several 1024-candidate tiles
+        mp, n = DENSE[name]
+        rng = np.random.default_rng(mp)
+        cloud = (rng.normal(size=(n, 3)) * [1.2, 1.2, 0.7]).astype(np.float32)
+        cloud = cloud[np.abs(cloud).max(axis=1) < 2.9]
+        cloud[:70] = cloud[0]
+        return 1.0, mp, 1e9, [(part, np.eye(4)) for part in np.array_split(cloud, 3)]
     raise KeyError(name)
 
 
@@ -74,6 +84,9 @@ def host_map(name):
     hm = pl.VoxelHashMap(voxel, max_range, mp)
     for cloud, T in steps:
         hm.add_pointcloud(cloud, T)
+    if name in DENSE:      # what makes these cases a test of a voxel's second block of 64 points
+        sizes = np.array([len(v) for v in hm._vox.values()])
+        assert sizes.max() == mp and int((sizes > 64).sum()) >= 10, (name, sizes.max(), int((sizes > 64).sum()))
     return hm
 
 

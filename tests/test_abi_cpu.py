@@ -100,3 +100,12 @@ def test_cpp_shim_registers_on_gpu(pkg):
     exe = _build_example(root)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
+
+
+def test_map_table_info_is_declared_and_mirrored(pkg):
+    """svnicp_map_table_info (the read-only tap the voxel-map tests assert rebuilds with): declared, bound, refused without a map."""
+    assert "svnicp_map_table_info" in pkg.declared_symbols()
+    L = pkg.load_library()
+    assert L.svnicp_map_table_info.argtypes[1:] == [C.POINTER(C.c_int64)] * 3
+    assert L.svnicp_map_table_info(None, None, None, None) == -1      # SVNICP_ERR_INVALID, and no device is touched
+    assert callable(pkg.pipeline.DeviceVoxelHashMap.table_info)

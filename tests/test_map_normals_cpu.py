@@ -97,3 +97,15 @@ def test_map_normals_needs_the_device_map_and_plane_mode(pkg):
         pl.PipelineConfig(map_normals=True, gpu_map=True)
     assert pl.PipelineConfig(map_normals=True, gpu_map=True, solver=plane).map_normals
     assert pl.PipelineConfig(gpu_map=True, solver=plane).map_normals is False      # plane mode with the solver's own pass
+
+
+@pytest.mark.parametrize("name,above64,above128", [("dense65", 15, 0), ("dense130", 19, 15), ("dense256", 26, 16)])
+def test_dense_cases_fill_voxels_past_the_first_block(pkg, name, above64, above128):
+    """The dense cases of tests/test_map_normals_gpu.py: voxels filled over three calls up to max_points itself, 15 / 19 / 26
+    of them past 64 points (the second 64-point block of k_map_normals), 15 and 16 past 128 at max_points 130 and 256."""
+    mp, _ = mc.DENSE[name]
+    sizes = np.array([len(v) for v in mc.host_map(name)._vox.values()])      # host_map asserts max == max_points, >= 10 above 64
+    print(f"{name}: {sizes.size} voxels, {int(sizes.sum())} points, {int((sizes > 64).sum())} above 64, {int((sizes > 128).sum())} above 128")
+    assert 85 <= sizes.size <= 94 and sizes.max() == mp
+    assert int((sizes > 64).sum()) == above64 and int((sizes > 128).sum()) == above128
+    assert len(mc.case_inputs(name)[3]) == 3

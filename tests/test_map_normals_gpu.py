@@ -5,7 +5,9 @@ Comparison rule: flags equal; with_normal equal to the restatement's count; 1 - 
 (lambda1 - lambda0) / lambda2 >= 1e-3 (the eigenvector of lambda0 is then determined to eps / gap ~ 1e-13 rad); rows left
 out by that floor, or whose flag sits on the threshold (|lambda1 - 0.01 lambda2| <= 1e-9 lambda2), are at most 1 % of the
 rows (on the CPU the restatement alone leaves out at most 0.31 %, on the lattice at normal_k 8).  On every input here the
-restatement has NO row on the threshold; the tests assert that, so flags and counts are compared on all rows."""
+restatement has NO row on the threshold; the tests assert that, so flags and counts are compared on all rows.
+The dense cases (voxels of up to 65, 130 and 256 points, normal_k 4, 16, 64) leave out no row; on an MI355X every flag and count
+is equal and max 1 - |n.n_ref| = 2.2e-16 in all nine."""
 import ctypes as C
 import importlib
 import os
@@ -27,7 +29,7 @@ ERR_INVALID = -1
 
 def _device_map(hip, name):
     voxel, mp, max_range, steps = mc.case_inputs(name)
-    dm = hip.pipeline.DeviceVoxelHashMap(voxel, max_range, mp, device=0)
+    dm = hip.pipeline.DeviceVoxelHashMap(voxel, max_range, mp, device=0, capacity_voxels=1 if name in mc.DENSE else 0)
     for cloud, T in steps:
         dm.add_pointcloud(cloud, T)
     return dm
@@ -69,8 +71,8 @@ def _check_queries(tag, dm, vox, ref, kn, pose, radius, cut_may_be_empty=False):
 # ---------------------------------------------------------------------------------------------
 # 1. inputs
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kn", [8, 16])
-@pytest.mark.parametrize("name", ["drive", "drive_shifted", "uniform64", "uniform3", "lattice"])
+@pytest.mark.parametrize("name,kn", [(name, kn) for name in ("drive", "drive_shifted", "uniform64", "uniform3", "lattice") for kn in (8, 16)] +
+                         [(name, kn) for name in mc.DENSE for kn in (4, 16, 64)])
 def test_map_normals_agree_with_the_restatement(hip, name, kn):
     ref = mc.reference(name, kn)
     dm = _device_map(hip, name)
@@ -80,7 +82,19 @@ def test_map_normals_agree_with_the_restatement(hip, name, kn):
         assert ref.boundary_tie.mean() > 0.5
     if name == "uniform64":    # more candidates than one tile of the kernel (1024), and the 64 copies of point 0
         assert ref.n_cand.max() > 1024 and int((~ref.valid).sum()) >= 64
+    if name in mc.DENSE:       # rows in a voxel's second (and at 256: third, fourth) block of 64; at normal_k 64 every lane holds a
+        in_voxel = np.arange(ref.points.shape[0]) - np.repeat(ref.offs[:-1], np.diff(ref.offs))      # neighbour and some blocks are too small
+        print(f"{name} normal_k {kn}: {len(ref.keys)} voxels, {int((np.diff(ref.offs) > 64).sum())} above 64 points, rows past the first "
+              f"block {int((in_voxel >= 64).sum())}, candidates {ref.n_cand.min()}..{ref.n_cand.max()}, no normal {int((~ref.valid).sum())}")
+        assert ref.valid[in_voxel >= 64].sum() >= 10 and ref.n_cand.max() > 1024 and int((~ref.valid).sum()) >= 65
+        if name == "dense256":     # blocks below normal_k 64 and blocks of four tiles; rows in a third block
+            assert ref.n_cand.min() < 64 and ref.n_cand.max() > 3072 and ref.valid[in_voxel >= 128].sum() >= 100
     _check_queries(name, dm, mc.host_map(name)._vox, ref, kn, pose, radius)
+    if name in mc.DENSE and kn == 16:      # normal_k 0 means 16
+        _, w16 = dm.get_map_normals(16)
+        n16 = dm.download_normals()
+        _, w0 = dm.get_map_normals(0)
+        assert w0 == w16 and n16.shape[0] > 0 and np.array_equal(dm.download_normals(), n16)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -88,23 +102,32 @@ def test_map_normals_agree_with_the_restatement(hip, name, kn):
 # ---------------------------------------------------------------------------------------------
 def test_map_normals_follow_a_moving_sensor(hip):
     """The sequence of test_device_map_equals_host_map's first case: 5 clouds of 30 000 points, the sensor moves, far voxels
-    are culled (tombstones in the probe chains) and the table is rebuilt.  Normals are checked after every step."""
+    are culled (tombstones in the probe chains) and the table is rebuilt: it starts at 65 536 slots, so from the second cloud on
+    (live + 30 000) * 2 exceeds the capacity and live voxels are moved into a larger table, with tombstones arriving afterwards.
+    Normals are checked after every step."""
     from test_voxel_map_gpu import _pose
     pl = hip.pipeline
     voxel, max_pts, n, extent, steps, kn = 1.0, 20, 30000, 40.0, 5, 8
     rng = np.random.default_rng(int(voxel * 100) + max_pts)
     max_range = 0.6 * extent
     hm = pl.VoxelHashMap(voxel, max_range, max_pts)
-    dm = pl.DeviceVoxelHashMap(voxel, max_range, max_pts, device=0)
+    dm = pl.DeviceVoxelHashMap(voxel, max_range, max_pts, device=0, capacity_voxels=1)
+    moved = []      # live voxels at each rebuild
     for k in range(steps):
         cloud = (rng.uniform(-1, 1, size=(n, 3)) * extent * 0.5).astype(np.float32)
         cloud[: n // 10] = cloud[0]
         T = _pose(rng, extent * 0.15 * k)
+        live, rebuilds = len(hm), dm.table_info()[2]
         hm.add_pointcloud(cloud, T); dm.add_pointcloud(cloud, T)
+        if dm.table_info()[2] > rebuilds:
+            moved.append(live)
         assert len(dm) == len(hm), k
         Q = _pose(rng, extent * 0.1)
         _check_queries(f"step {k}", dm, hm._vox, mr.map_normals(hm._vox, kn), kn, Q, 0.3 * extent,
                        cut_may_be_empty=True)      # the last step's query centre has left the map
+    print(f"table_info {dm.table_info()}, live voxels at the rebuilds {moved}")
+    assert dm.table_info()[2] >= 1
+    assert max(moved) > 1000      # a rebuild of a table that held voxels
 
 
 # ---------------------------------------------------------------------------------------------
