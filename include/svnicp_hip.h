@@ -274,6 +274,61 @@ const int32_t *svnicp_eval_index_devptr(svnicp_ctx *ctx);   /* int32 [B]: neares
 const double *svnicp_eval_dist2_devptr(svnicp_ctx *ctx);    /* double [B]: its d2, NaN = not evaluated */
 int svnicp_get_eval_pairs(svnicp_ctx *ctx, int32_t *idxB, double *d2B);   /* host copy of the two; either may be NULL */
 
+/* ---- score and weight the particles (an extension: the reference declares ParticleWeightOpt::use_weight_mean,
+ * include/core/SVNICP.h:25-27, and writes its getters for arbitrary weights, SVNICP.cpp:286-308, but particle_weight_ never
+ * becomes anything but ones / P) --------------------------------------------------------------------
+ * svnicp_score_particles(ctx, max_corr_dist, outPx6, posesPx12): every particle's final pose scored through the candidate
+ * table the registration built -- the nearest-of-K rule of the iterations, not svnicp_evaluate's search of the whole target.
+ *   poses        particle p is scored at the total pose the device holds after the last executed update, [R0 R_p | t0 + R0 t_p]:
+ *                the pose the next iteration's search would have used, also after an early stop.  posesPx12 (may be NULL)
+ *                returns exactly those 12 doubles per particle, R row-major, then t.  The kernels ignore the stop flag.
+ *   transformed  for source row b: T_i = (s0*R[3i] + s1*R[3i+1] + s2*R[3i+2]) + t[i], float64, unfused (the search's).
+ *   point
+ *   winner       among the knn_count candidates cand[b][0..K) of the registration (svnicp_candidates_devptr): e = T - q_k,
+ *                d2 = ((e0*e0) + e1*e1) + e2*e2, strict '<' from candidate 0, exactly the "search" rule under
+ *                svnicp_set_clouds: a NaN first distance is never replaced.  Candidate indices are clamped to [0, M) before
+ *                they become addresses.
+ *   classes      a row is evaluated iff T is finite and the winner's d2 is not NaN; an inlier iff evaluated and d2 < thr2,
+ *                thr2 = max_corr_dist * max_corr_dist computed once in float64; a plane inlier iff an inlier, the context holds
+ *                normals of the current target (svnicp_evaluate's has_normals; no normal pass is ever run here) and the
+ *                winner's normal n is non-zero, with r = (n0*e0 + n1*e1) + n2*e2.  sum_d2 runs over the inliers, sum_r2 =
+ *                sum r*r over the plane inliers; operands of rejected pairs are selected to zero, never multiplied.
+ *   cost         cost_p = (sum_d2_p + (B - inliers_p) * thr2) / B, the mean truncated squared distance: a row that is not an
+ *                inlier costs the gate.  max_corr_dist must be finite and > 0, so the cost is always finite.
+ *   out          outPx6, per particle: {evaluated, inliers, plane_inliers, sum_d2, sum_r2, cost}; the counts are exact
+ *                integers held in doubles.
+ *   determinism  no atomics: each workgroup owns a fixed range of rows and the records are added in an order that depends on
+ *                B and P alone; the same context state gives the same bits on every call.
+ *   when         as svnicp_evaluate: a finished registration since the source, the target, the initial mean, K, an option,
+ *                the mini-batch or the residual setting last changed; otherwise SVNICP_ERR_INVALID with the reason in
+ *                svnicp_last_error.  Refused after a registration that ran with a partial particle shard, a source-row shard,
+ *                mini-batch mode or the option correspondence=full; allowed in SVGD mode, in plane mode, for every stage-B
+ *                variant and chain and any K the registration accepted.  Synchronises first and returns with the results on
+ *                the host.
+ * svnicp_set_particle_weighting(ctx, kind, max_corr_dist, temperature): SVNICP_WEIGHT_UNIFORM (the reference, the default)
+ * runs exactly the launches of a context that never called this.  With SVNICP_WEIGHT_SOFTMIN every following registration
+ * ends (svnicp_finish, so also svnicp_align and svnicp_align_async) with one scoring at max_corr_dist, the weights
+ *   w_p = exp(-(cost_p - cost_min) / temperature) / Z      (Z added in particle order; temperature in m^2, finite and > 0)
+ * and the reference's own weighted expressions in float64, every sum in particle order: mean_i = sum_p x_ip w_p,
+ * var_i = sum_p (x_ip - mean_i)^2 w_p, cov_rc = sum_p w_p (x_rp - mean_r)(x_cp - mean_c).  svnicp_get_transformation,
+ * svnicp_get_distribution, svnicp_get_cov_matrix and svnicp_get_particle_weight (w) return them, and what builds on the mean
+ * follows: svnicp_evaluate(NULL, NULL), the pipelines' correction_to_pose.  For any kind but UNIFORM the setter itself refuses
+ * a max_corr_dist or temperature that is not finite and > 0 (SVNICP_ERR_INVALID).  Refused by svnicp_align /
+ * svnicp_align_begin with SVNICP_ERR_INVALID while weighting is on: an unknown kind, SVGD mode (the option belongs to SVNICP's
+ * constructor only), a partial particle shard, a source-row shard, mini-batch mode (its candidate tables are per drawn
+ * position) and the option correspondence=full.
+ * svnicp_get_particle_scores: the last scoring, whoever ran it -- a weighted registration supplies it at no extra GPU work;
+ * SVNICP_ERR_INVALID before there is one.
+ * Side effects: none.  No existing getter changes in UNIFORM mode, and the next registration of a context that scored or
+ * weighted is bit for bit that of one that never did. */
+#define SVNICP_SCORE_FIELDS 6
+/* per particle p: {evaluated, inliers, plane_inliers, sum_d2, sum_r2, cost}; the counts are exact integers held in doubles */
+int svnicp_score_particles(svnicp_ctx *ctx, double max_corr_dist, double *outPx6, double *posesPx12);
+#define SVNICP_WEIGHT_UNIFORM 0   /* the reference, the default */
+#define SVNICP_WEIGHT_SOFTMIN 1
+int svnicp_set_particle_weighting(svnicp_ctx *ctx, int kind, double max_corr_dist, double temperature);
+int svnicp_get_particle_scores(svnicp_ctx *ctx, double *outPx6, double *posesPx12);  /* of the last scoring, whoever ran it */
+
 /* ---- split-phase entry points: one process per GPU, particles sharded across ranks ----------
  * (new functionality; the reference is single-GPU).  Sequence per registration:
  *   svnicp_set_shard -> svnicp_stage_candidates(b_lo,b_hi) -> [host all-gathers rows of

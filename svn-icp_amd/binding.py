@@ -177,6 +177,9 @@ def load_library():
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = vp
     L.svnicp_get_eval_pairs.argtypes = [vp, ip, dp]
+    L.svnicp_score_particles.argtypes = [vp, C.c_double, dp, dp]
+    L.svnicp_set_particle_weighting.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+    L.svnicp_get_particle_scores.argtypes = [vp, dp, dp]
     for name in declared_symbols():
         getattr(L, name)  # AttributeError here = the header declares a symbol the library does not export
     _lib = L

@@ -110,6 +110,17 @@ struct EvalState {
   int64_t rows = 0;
 };
 
+// svnicp_score_particles / svnicp_set_particle_weighting (csrc/particle_score.hip): its own buffers
+struct ScoreState {
+  int kind = SVNICP_WEIGHT_UNIFORM;        // what the next registration ends with
+  double gate = 0.0, temperature = 0.0;
+  bool on = false;                         // the registration begun last ends with a scoring and weighted statistics
+  const char* reg_refusal = nullptr;       // why the registration begun last cannot be scored (registration_plan.hpp: scoring_refusal)
+  DevBuf<double> partial, scores, poses, w;   // [score_blocks(B)][Ppad][kScoreRecord], [P][kScoreFields], [P][12], [P]
+  bool have = false;                       // scores / poses hold a scoring of `P` particles
+  int P = 0;
+};
+
 struct Trace { DevBuf<double> H, b, N, phi, h; DevBuf<int32_t> corr; };   // record_trace
 
 struct Profiling {   // timing events
@@ -146,7 +157,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev;
+  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev; ScoreState sc;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -198,6 +209,7 @@ static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane) {
   f.shard_set = c->shard.set; f.p_lo = c->shard.p_lo; f.p_hi = c->shard.p_hi; f.row_world = c->shard.row_world;
   f.batch = c->mb.batch; f.explicit_tab = c->mb.explicit_tab; f.tab_I = c->mb.tab_I;
   f.plane = plane; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
+  f.weighting = c->sc.kind;
   return f;
 }
 
@@ -365,6 +377,7 @@ int svnicp_set_particles(svnicp_ctx* c, const double* init, int P) {
   c->st.init_in_flight = true;
   c->st.host_stats_valid = false;
   const bool first = !c->run.particles_set || P != c->P;
+  if (P != c->P) c->sc.have = false;   // the last scoring was of another particle count
   if (first && c->shard.row_world > 1) { c->shard.row_world = 1; c->shard.row_rank = 0; c->shard.B_total = 0; }   // the record array is sized by P: set the row shard again
   c->P = P;
   if (!c->shard.set || first) { c->shard.p_lo = 0; c->shard.p_hi = P; c->shard.set = false; }
@@ -483,12 +496,16 @@ int svnicp_align_begin(svnicp_ctx* c) {
     c->mb.tab_checked_B = B;
   }
   if (const char* why = plane_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kPlaneRefusal) + why);
+  if (const char* why = weighting_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + why);
+  if (f.weighting && score_tile_rows(P, c->K, true) < 1)
+    return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + "knn_count is too large for one row's candidates to fit the scoring kernel's LDS tile");
   const RegistrationRows r = registration_rows(c->mb.batch, I, B);
   const AccumPlan shape = plan_stage_b(f, c->tune, r.Bi);
   // (the stage-A plan StageA::begin is about to make: every refusal comes before the context changes)
   const bool stage_a_k1 = StageA::plan_for(stage_a_env(c), r.Bq, c->K).can_search(1);
   if (const char* why = full_corr_refusal(f, c->tune, shape.f32, stage_a_k1)) return fail(c, SVNICP_ERR_INVALID, why);
   c->pl.on = plane;
+  c->sc.on = f.weighting != 0; c->sc.reg_refusal = scoring_refusal(f, c->tune);
   c->mb.on = r.mb; c->mb.have = false; c->mb.check = false;
   c->mb.rows = r.mb ? r.Bt : 0;
   c->mb.nq = r.mb ? r.Bq : 0;
@@ -810,13 +827,40 @@ int svnicp_iter_update(svnicp_ctx* c, int it) {
   return SVNICP_OK;
 }
 
+// k_particle_score + k_particle_score_finalize on the context's stream: sc.scores [P][6] and sc.poses [P][12] (a copy of the
+// total poses that were scored: the next svnicp_set_particles rewrites Rtot)
+static int enqueue_scoring(svnicp_ctx* c, double gate) {
+  const bool normals = c->pl.supplied || c->pl.estimated;
+  if (score_tile_rows(c->P, c->K, normals) < 1)
+    return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + "knn_count is too large for one row's candidates to fit the scoring kernel's LDS tile");
+  ScoreState& sc = c->sc;
+  sc.have = false;
+  HIPCHK(c, sc.partial.ensure((size_t)score_blocks(c->B) * score_padded_particles(c->P, c->K) * kScoreRecord));
+  HIPCHK(c, sc.scores.ensure((size_t)c->P * kScoreFields));
+  HIPCHK(c, sc.poses.ensure((size_t)c->P * 12));
+  ScoreArgs a{};
+  a.src = c->cloud.src.p; a.tgt = c->cloud.tgt.p; a.rec = normals ? c->pl.rec.p : nullptr; a.cand = c->sa.cand_idx.p; a.Rtot = c->st.Rtot.p;
+  a.B = c->B; a.M = c->M; a.K = c->K; a.P = c->P; a.thr2 = gate * gate; a.partial = sc.partial.p;
+  HIPCHK(c, launch_particle_score(a, sc.scores.p, c->stream));
+  HIPCHK(c, hipMemcpyAsync(sc.poses.p, c->st.Rtot.p, (size_t)c->P * 12 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  sc.have = true; sc.P = c->P;
+  return SVNICP_OK;
+}
+
 int svnicp_finish(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (!c->run.began) return fail(c, SVNICP_ERR_INVALID, "svnicp_finish: call svnicp_align_begin first");
   if (bind(c)) return SVNICP_ERR_HIP;
   HIPCHK(c, hipEventRecord(c->prof.ev[2], c->stream));
   StatsArgs s{c->st.pose_out.p, c->P, c->prm.mode, c->st.stats.p};
-  HIPCHK(c, launch_stats(s, c->stream));
+  if (c->sc.on) {   // one scoring at the poses the iterations left, the weights, the reference's weighted expressions
+    if (const int rc = enqueue_scoring(c, c->sc.gate)) return rc;
+    HIPCHK(c, c->sc.w.ensure((size_t)c->P));
+    HIPCHK(c, launch_particle_weights(c->sc.scores.p, c->P, c->sc.temperature, c->sc.w.p, c->stream));
+    HIPCHK(c, launch_stats_weighted(s, c->sc.w.p, c->stream));
+  } else {
+    HIPCHK(c, launch_stats(s, c->stream));
+  }
   // the result block follows the kernels down the stream into pinned memory: the getters then cost no GPU round trip
   c->st.host_stats_valid = false;
   if (c->st.h_stats.p && (size_t)c->P + 48 <= c->st.h_stats.cap)
@@ -1276,6 +1320,47 @@ int svnicp_get_eval_pairs(svnicp_ctx* c, int32_t* idxB, double* d2B) {
     if (const int rc = fetch(c, idxB, c->ev.idx.p, (size_t)c->ev.rows * 4)) return rc;
   if (d2B)
     if (const int rc = fetch(c, d2B, c->ev.d2.p, (size_t)c->ev.rows * 8)) return rc;
+  return SVNICP_OK;
+}
+
+// ---- score and weight the particles ----
+int svnicp_get_particle_scores(svnicp_ctx* c, double* outPx6, double* posesPx12) {
+  CTX_CHECK(c);
+  if (!c->sc.have) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_particle_scores: no scoring yet (svnicp_score_particles, or a registration with svnicp_set_particle_weighting)");
+  if (outPx6)
+    if (const int rc = fetch(c, outPx6, c->sc.scores.p, (size_t)c->sc.P * kScoreFields * sizeof(double))) return rc;
+  if (posesPx12)
+    if (const int rc = fetch(c, posesPx12, c->sc.poses.p, (size_t)c->sc.P * 12 * sizeof(double))) return rc;
+  return SVNICP_OK;
+}
+
+int svnicp_score_particles(svnicp_ctx* c, double max_corr_dist, double* outPx6, double* posesPx12) {
+  CTX_CHECK(c);
+  if (!(max_corr_dist > 0.0) || !std::isfinite(max_corr_dist))
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_score_particles: max_corr_dist must be finite and positive");
+  if (!c->run.have_result)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_score_particles: no finished registration yet (the candidate table belongs to one)");
+  if (!c->run.have_candidates)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_score_particles: the source, the target, the initial mean, K or an option changed since the last registration: "
+                                       "register again first (the candidate table belongs to that registration)");
+  if (c->sc.reg_refusal) return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + c->sc.reg_refusal);
+  if (const int rc = svnicp_synchronize(c)) return rc;   // an asynchronous registration has finished and its checks have run
+  if (bind(c)) return SVNICP_ERR_HIP;
+  if (const int rc = enqueue_scoring(c, max_corr_dist)) return rc;
+  if (!outPx6 && !posesPx12) { HIPCHK(c, hipStreamSynchronize(c->stream)); return SVNICP_OK; }
+  return svnicp_get_particle_scores(c, outPx6, posesPx12);
+}
+
+int svnicp_set_particle_weighting(svnicp_ctx* c, int kind, double max_corr_dist, double temperature) {
+  CTX_CHECK(c);
+  if (kind != SVNICP_WEIGHT_UNIFORM) {
+    if (!(max_corr_dist > 0.0) || !std::isfinite(max_corr_dist))
+      return fail(c, SVNICP_ERR_INVALID, "svnicp_set_particle_weighting: max_corr_dist must be finite and positive");
+    if (!(temperature > 0.0) || !std::isfinite(temperature))
+      return fail(c, SVNICP_ERR_INVALID, "svnicp_set_particle_weighting: temperature must be finite and positive");
+  }
+  c->sc.kind = kind;   // an unknown kind is refused by svnicp_align_begin
+  c->sc.gate = max_corr_dist; c->sc.temperature = temperature;
   return SVNICP_OK;
 }
 

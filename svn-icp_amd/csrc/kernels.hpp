@@ -263,6 +263,31 @@ int64_t evaluate_blocks(int64_t B);
 hipError_t launch_evaluate_transform(const double* src, int64_t B, const EvalPose& T, double* q, hipStream_t st);
 // k_evaluate_pairs + k_evaluate_finalize: result[kEvalResult] in device memory
 hipError_t launch_evaluate_pairs(const EvalArgs& a, double* result, hipStream_t st);
+// ---------------- score and weight the particles (particle_score.hip) ----------------
+constexpr int kScoreRecord = 5;        // per (workgroup, particle): evaluated, inliers, plane inliers (exact counts), sum d2, sum r2
+constexpr int kScoreFields = 6;        // per particle: the record's five totals | cost  (SVNICP_SCORE_FIELDS)
+constexpr int kScoreRowsPerBlock = 64; // source rows a workgroup owns: a multiple of every row step of the geometry
+struct ScoreArgs {
+  const double* src;    // [B][3]
+  const double* tgt;    // [M][3]
+  const double* rec;    // [M][6] target xyz | unit normal when the context holds normals of this target, else nullptr
+  const int32_t* cand;  // [B][K] the registration's candidate target indices (stage A)
+  const double* Rtot;   // [P][12] the poses that are scored
+  int64_t B, M;
+  int K, P;
+  int Ppad, TH;         // set by the launcher: padded particle count, source rows per LDS tile
+  double thr2;          // max_corr_dist^2
+  double* partial;      // [score_blocks(B)][Ppad][kScoreRecord]
+};
+int64_t score_blocks(int64_t B);
+int score_padded_particles(int P, int K);
+// source rows per LDS tile for this K (0: one row's candidates do not fit, the launch is refused)
+int score_tile_rows(int P, int K, bool normals);
+// k_particle_score + k_particle_score_finalize: scores [P][kScoreFields] in device memory
+hipError_t launch_particle_score(ScoreArgs a, double* scores, hipStream_t st);
+// w[p] = exp(-(cost_p - cost_min) / temperature) / Z, Z added in particle order (one workgroup)
+hipError_t launch_particle_weights(const double* scores, int P, double temperature, double* w, hipStream_t st);
+
 // ---------------- mini-batch tables (minibatch.hip) ----------------
 struct MinibatchArgs {
   const int32_t* explicit_idx;  // [n] a caller's table (validated by the draw kernel), or nullptr: generated from `base`
@@ -288,5 +313,7 @@ hipError_t launch_minibatch_expand(const MinibatchArgs& a, const int32_t* cand_u
 
 struct StatsArgs { const double* pose; int P; int mode; double* out; /* mean6,var6,cov36,weightsP */ };
 hipError_t launch_stats(const StatsArgs& a, hipStream_t st);
+// the same block with the weights w[P] of launch_particle_weights (SVN mode; SVNICP.cpp:286-308 as written, for any weights)
+hipError_t launch_stats_weighted(const StatsArgs& a, const double* w, hipStream_t st);
 
 }  // namespace svnicp

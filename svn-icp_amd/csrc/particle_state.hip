@@ -80,6 +80,44 @@ __global__ void k_stats(StatsArgs a) {
   for (int p = tid; p < P; p += blockDim.x) a.out[48 + p] = a.mode == 0 ? wsvn : 1.0;
 }
 
+// the same block with weights w[P] (svnicp_set_particle_weighting; SVN mode): the reference's getters as written for arbitrary
+// weights (SVNICP.cpp:286-308) — mean_i = sum x_ip w_p, var_i = sum (x_ip - mean_i)^2 w_p, cov_rc = sum w_p (x_rp - mean_r)
+// (x_cp - mean_c), every sum in particle order.  A kernel of its own: k_stats, the uniform path, stays as it is bit for bit.
+__global__ void k_stats_weighted(StatsArgs a, const double* __restrict__ w) {
+  const int tid = threadIdx.x;
+  const int P = a.P;
+  __shared__ double mean[6];
+  constexpr int kStage = 896;   // 7 x 896 doubles: 49 KB of LDS
+  __shared__ double sp[7 * kStage];
+  const bool staged = P <= kStage;
+  if (staged) {
+    for (int e = tid; e < 6 * P; e += blockDim.x) sp[e] = a.pose[e];
+    for (int e = tid; e < P; e += blockDim.x) sp[6 * P + e] = w[e];
+  }
+  __syncthreads();
+  const double* pose = staged ? sp : a.pose;
+  const double* wp = staged ? sp + 6 * P : w;
+  if (tid < 6) {
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) s += pose[tid * P + p] * wp[p];
+    mean[tid] = s;
+    a.out[tid] = s;
+  }
+  __syncthreads();
+  if (tid < 6) {
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) { const double d = pose[tid * P + p] - mean[tid]; s += d * d * wp[p]; }
+    a.out[6 + tid] = s;
+  }
+  if (tid < 36) {
+    const int r = tid / 6, c = tid % 6;
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) s += wp[p] * ((pose[r * P + p] - mean[r]) * (pose[c * P + p] - mean[c]));
+    a.out[12 + tid] = s;
+  }
+  for (int p = tid; p < P; p += blockDim.x) a.out[48 + p] = wp[p];
+}
+
 }  // namespace
 
 hipError_t launch_init_particles(const double* init6xP, int P, const Pose0& pose, int mode, double* R, double* t,
@@ -98,6 +136,11 @@ hipError_t launch_init_particles(const double* init6xP, int P, const Pose0& pose
 
 hipError_t launch_stats(const StatsArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_stats, dim3(1), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_stats_weighted(const StatsArgs& a, const double* w, hipStream_t st) {
+  hipLaunchKernelGGL(k_stats_weighted, dim3(1), dim3(256), 0, st, a, w);
   return hipGetLastError();
 }
 

@@ -49,6 +49,7 @@ struct RegistrationFacts {
   bool plane = false;                  // svnicp_set_residual: point-to-plane
   bool normals_supplied = false;
   int normal_k = 16;
+  int weighting = 0;                   // svnicp_set_particle_weighting: SVNICP_WEIGHT_* (0 = uniform, the reference)
   int nshard() const { return p_hi - p_lo; }
   bool whole_shard() const { return p_lo == 0 && p_hi == P; }
 };
@@ -77,6 +78,8 @@ inline const char* first_refusal(std::initializer_list<Refusal> ladder) {
 }
 constexpr const char* kMinibatchRefusal = "svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ";
 constexpr const char* kPlaneRefusal = "svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ";
+constexpr const char* kWeightingRefusal = "svnicp_align: particle weighting (svnicp_set_particle_weighting) is not available here: ";
+constexpr const char* kScoringRefusal = "svnicp_score_particles: the last registration cannot be scored: ";
 
 // mini-batch: what it is not combined with (nullptr: nothing, or mini-batch is off)
 inline const char* minibatch_refusal(const RegistrationFacts& f, const Tuning& t) {
@@ -106,6 +109,25 @@ inline const char* plane_refusal(const RegistrationFacts& f, const Tuning& t) {
       {f.K > 128, "knn_count exceeds 128: the plane kernel consumes the matrix-pipe search kernel's winner index"},
       {!f.normals_supplied && f.M < f.normal_k, "the target has fewer points than normal_k and no normals were supplied"},
   });
+}
+// scoring the particles through the registration's candidate table (svnicp_score_particles): what the registration must
+// not have run with.  The table is [B][K] of the whole scan for all particles; allowed in SVGD mode, in plane mode, for
+// every stage-B variant and chain and any K the registration accepted.
+inline const char* scoring_refusal(const RegistrationFacts& f, const Tuning& t) {
+  return first_refusal({
+      {f.shard_set && !f.whole_shard(), "a partial particle shard (svnicp_set_shard) is set"},
+      {f.row_world > 1, "a source-row shard (svnicp_set_row_shard) is set: this context holds a part of the scan"},
+      {f.batch != 0, "mini-batch mode (svnicp_set_minibatch) is set: its candidate tables are per drawn position"},
+      {t.full_corr != 0, "option correspondence=full is set: the iterations did not search the candidate table"},
+  });
+}
+// weighting the particle set at the end of a registration (nullptr: nothing, or the weights are uniform).  The setter
+// itself refuses a non-finite or non-positive max_corr_dist or temperature.
+inline const char* weighting_refusal(const RegistrationFacts& f, const Tuning& t) {
+  if (f.weighting == 0) return nullptr;
+  if (f.weighting != 1) return "unknown weighting kind";
+  if (f.svgd) return "SVGD mode: the weight option belongs to SVNICP's constructor only";
+  return scoring_refusal(f, t);
 }
 // correspondence = full (the whole message): its per-particle searches feed the split accumulate kernel and run through
 // stage A's working set with K = 1 (stage_a_k1: StageAPlan::can_search(1)).  An empty particle shard searches nothing.

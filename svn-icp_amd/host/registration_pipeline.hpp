@@ -587,6 +587,9 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
                                // (DeviceVoxelMap::QueryNormals) instead of the solver's pass over the target
   double eval_dist = 0.0;      // > 0: every registered scan is evaluated at its result pose with this inlier gate
                                // (svnicp_evaluate) before the map update; 0 = off, no call is made
+  double weight_dist = 0.0;    // > 0: every registration ends with one scoring of the particles at this gate and soft-min weights
+                               // (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures
+  double weight_temperature = 0.0;   // with weight_dist: the soft-min temperature in m^2, > 0
 };
 
 struct ScanResult {
@@ -615,6 +618,9 @@ class RegistrationPipeline {
  public:
   explicit RegistrationPipeline(const PipelineConfig& cfg)
       : cfg_(cfg), map_(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points), rng_(cfg.seed * 0x9e3779b97f4a7c15ull + 0x2545f4914f6cdd1dull) {
+    if (!(std::isfinite(cfg.weight_dist) && cfg.weight_dist >= 0)) throw std::invalid_argument("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)");
+    if (cfg.weight_dist > 0 && !(std::isfinite(cfg.weight_temperature) && cfg.weight_temperature > 0))
+      throw std::invalid_argument("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)");
     if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
     if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
     if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
@@ -684,7 +690,7 @@ class RegistrationPipeline {
     }
     std::vector<double> src64;
     if (!dprep_) src64 = widen(source);                                                                // ICPUtils.cpp:27-43
-    if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{}, cfg_.device);
+    if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{cfg_.weight_dist > 0, cfg_.weight_dist, cfg_.weight_temperature}, cfg_.device);
     std::vector<double> tgt64;
     if (dmap_) {
       int64_t M = dmap_->GetMap(guess, scan_max_range_ + 10.0);                                        // :577-578

@@ -35,7 +35,10 @@ struct SteinICPParam {  // SVGDICP.h:41-57 (same names and defaults; solver-rele
   int normal_k = 16;                // plane residual: neighbours a target normal is estimated from (4..64)
 };
 
-struct ParticleWeightOpt { bool use_weight_mean = false; };  // SVNICP.h:25-27
+// SVNICP.h:25-27.  use_weight_mean alone is as inert as in the reference (particle_weight_ stays ones / P); with weight_dist > 0
+// as well (not in the reference) every registration ends with one scoring of the particles at that gate (metres) and soft-min
+// weights of `temperature` (m^2, > 0) that the getters honour (svnicp_hip.h "score and weight the particles")
+struct ParticleWeightOpt { bool use_weight_mean = false; double weight_dist = 0.0; double temperature = 0.0; };
 
 class SVGDICP {
  public:
@@ -145,6 +148,23 @@ class SVGDICP {
     if (d2) d2->assign((size_t)B, 0.0);
     chk(svnicp_get_eval_pairs(h_, idx ? idx->data() : nullptr, d2 ? d2->data() : nullptr));
   }
+  // score and weight the particles (svnicp_hip.h): [P][SVNICP_SCORE_FIELDS] {evaluated, inliers, plane inliers, sum d2, sum r2,
+  // cost} of every particle's final pose through the registration's candidate table; poses: [P][12] (R row-major, t), optional
+  std::vector<double> score_particles(double max_corr_dist, std::vector<double>* poses = nullptr) {
+    std::vector<double> o((size_t)P_ * SVNICP_SCORE_FIELDS);
+    if (poses) poses->assign((size_t)P_ * 12, 0.0);
+    chk(svnicp_score_particles(h_, max_corr_dist, o.data(), poses ? poses->data() : nullptr));
+    return o;
+  }
+  std::vector<double> get_particle_scores(std::vector<double>* poses = nullptr) {   // the last scoring, whoever ran it
+    std::vector<double> o((size_t)P_ * SVNICP_SCORE_FIELDS);
+    if (poses) poses->assign((size_t)P_ * 12, 0.0);
+    chk(svnicp_get_particle_scores(h_, o.data(), poses ? poses->data() : nullptr));
+    return o;
+  }
+  void set_particle_weighting(int kind, double max_corr_dist = 0.0, double temperature = 0.0) {
+    chk(svnicp_set_particle_weighting(h_, kind, max_corr_dist, temperature));
+  }
   const int32_t* eval_index_ptr() { return svnicp_eval_index_devptr(h_); }
   const double* eval_dist2_ptr() { return svnicp_eval_dist2_devptr(h_); }
   svnicp_ctx* handle() { return h_; }
@@ -159,8 +179,10 @@ class SVGDICP {
 
 class SVNICP final : public SVGDICP {
  public:
-  SVNICP(const SteinICPParam& p, const std::vector<double>& init_pose, const ParticleWeightOpt& = {}, int device = 0)
-      : SVGDICP(p, init_pose, device, SVNICP_MODE_SVN) {}
+  SVNICP(const SteinICPParam& p, const std::vector<double>& init_pose, const ParticleWeightOpt& w = {}, int device = 0)
+      : SVGDICP(p, init_pose, device, SVNICP_MODE_SVN) {
+    if (w.use_weight_mean && w.weight_dist > 0) set_particle_weighting(SVNICP_WEIGHT_SOFTMIN, w.weight_dist, w.temperature);
+  }
 };
 
 }  // namespace svnicp

@@ -899,9 +899,15 @@ class PipelineConfig:
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
     eval_dist: float = 0.0         # > 0: every registered scan is evaluated at its result pose with this inlier gate (svnicp_evaluate) before the map update; 0 = off, no call is made
+    weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
+    weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
     map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
 
     def __post_init__(self):
+        if not (np.isfinite(self.weight_dist) and self.weight_dist >= 0):
+            raise ValueError("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)")
+        if self.weight_dist > 0 and not (np.isfinite(self.weight_temperature) and self.weight_temperature > 0):
+            raise ValueError("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)")
         if self.map_normals and not self.gpu_map:
             raise ValueError("PipelineConfig: map_normals needs gpu_map=True (the normals are computed from the device map)")
         if self.map_normals and self.solver.residual != "plane":
@@ -997,7 +1003,7 @@ class RegistrationPipeline:
             self.poses.append(guess); self.times.append(stamp)
             return ScanResult(stamp, guess, guess, preprocessing_s=time.perf_counter() - t0)
         if self._solver is None:
-            self._solver = SVNICP(c.solver, init, ParticleWeightOpt(), device=self.device)
+            self._solver = SVNICP(c.solver, init, ParticleWeightOpt(c.weight_dist > 0, c.weight_dist, c.weight_temperature), device=self.device)
         s = self._solver
         with_normal = None
         if c.gpu_map:

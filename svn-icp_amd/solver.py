@@ -60,7 +60,26 @@ class SteinICPParam:  # include/core/SVGDICP.h:41-57 (same field names and defau
 
 @dataclass
 class ParticleWeightOpt:  # include/core/SVNICP.h:25-27
+    """``use_weight_mean`` alone is as inert as in the reference, whose particle_weight_ never leaves ones / P
+    (SVNICP.cpp:32, :46).  With ``weight_dist > 0`` as well (not in the reference) every registration of an ``SVNICP`` ends
+    with one scoring of the particles at the gate ``weight_dist`` (metres) and soft-min weights of temperature
+    ``temperature`` (m^2, > 0), which get_transformation / get_distribution / get_cov_matrix / get_particle_weight then
+    honour (include/svnicp_hip.h, "score and weight the particles")."""
     use_weight_mean: bool = False
+    weight_dist: float = 0.0
+    temperature: float = 0.0
+
+
+@dataclass
+class ParticleScores:
+    """svnicp_score_particles (include/svnicp_hip.h): every particle's final pose scored through the candidate table."""
+    evaluated: np.ndarray      # [P] rows with a finite transformed point and a winner whose d2 is not NaN
+    inliers: np.ndarray        # [P] evaluated rows with d2 < max_corr_dist^2
+    plane_inliers: np.ndarray  # [P] inliers whose winner has a normal (0 without normals)
+    sum_d2: np.ndarray         # [P] over the inliers
+    sum_r2: np.ndarray         # [P] over the plane inliers
+    cost: np.ndarray           # [P] (sum_d2 + (B - inliers) * max_corr_dist^2) / B
+    poses: np.ndarray          # [P, 3, 4] the total poses that were scored, [R | t]
 
 
 @dataclass
@@ -119,6 +138,12 @@ def minibatch_indices(seed: int, registration: int, iterations: int, batch_size:
     return idx.astype(np.int32).reshape(I, b)
 
 
+def poses_3x4(poses12: np.ndarray) -> np.ndarray:
+    """[P, 12] (R row-major, then t) as [P, 3, 4] = [R | t]."""
+    p = np.asarray(poses12, np.float64).reshape(-1, 12)
+    return np.concatenate([p[:, :9].reshape(-1, 3, 3), p[:, 9:].reshape(-1, 3, 1)], axis=2)
+
+
 def _is_torch_cuda(x) -> bool:
     return hasattr(x, "is_cuda") and bool(x.is_cuda)
 
@@ -149,6 +174,9 @@ class _SolverBase:
             self.set_minibatch(int(parameters.batch_size), int(parameters.minibatch_seed))
         if parameters.residual != "point":
             self.set_residual(parameters.residual, float(parameters.huber_delta), int(parameters.normal_k))
+        w = self.weight_config
+        if self._mode == 0 and w.use_weight_mean and w.weight_dist > 0:   # the option belongs to SVNICP's constructor only
+            self.set_particle_weighting("softmin", float(w.weight_dist), float(w.temperature))
 
     # -- plumbing -------------------------------------------------------------------------
     @staticmethod
@@ -405,6 +433,36 @@ class _SolverBase:
     def eval_dist2_ptr(self) -> int:
         """Device address of the last evaluate's float64 [B] squared distances (0 before any)."""
         return int(self._L.svnicp_eval_dist2_devptr(self._h) or 0)
+
+    # -- score and weight the particles (include/svnicp_hip.h "score and weight the particles") -------------------------------
+    _WEIGHTING = {"uniform": 0, "softmin": 1}
+
+    def set_particle_weighting(self, kind="uniform", max_corr_dist: float = 0.0, temperature: float = 0.0) -> None:
+        """"uniform" (the reference) or "softmin": every following registration ends with one scoring at ``max_corr_dist``
+        and the weights exp(-(cost - cost_min) / temperature) / Z."""
+        k = self._WEIGHTING.get(kind, kind)
+        self._check(self._L.svnicp_set_particle_weighting(self._h, int(k), float(max_corr_dist), float(temperature)),
+                    "svnicp_set_particle_weighting")
+
+    def _scores(self, out: np.ndarray, poses: np.ndarray) -> ParticleScores:
+        return ParticleScores(out[:, 0].astype(np.int64), out[:, 1].astype(np.int64), out[:, 2].astype(np.int64),
+                              out[:, 3].copy(), out[:, 4].copy(), out[:, 5].copy(), poses_3x4(poses))
+
+    def score_particles(self, max_corr_dist: float) -> ParticleScores:
+        """Score every particle's final pose through the registration's candidate table at the gate ``max_corr_dist``."""
+        out, poses = np.zeros((self._P, 6), np.float64), np.zeros((self._P, 12), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.svnicp_score_particles(self._h, float(max_corr_dist), out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
+                    "svnicp_score_particles")
+        return self._scores(out, poses)
+
+    def get_particle_scores(self) -> ParticleScores:
+        """The last scoring, whoever ran it (``score_particles``, or a registration with weighting on)."""
+        out, poses = np.zeros((self._P, 6), np.float64), np.zeros((self._P, 12), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.svnicp_get_particle_scores(self._h, out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
+                    "svnicp_get_particle_scores")
+        return self._scores(out, poses)
 
     def set_threshold(self, max_dist: float):
         self._check(self._L.svnicp_set_max_dist(self._h, float(max_dist)), "svnicp_set_max_dist")

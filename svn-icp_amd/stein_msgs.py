@@ -191,6 +191,27 @@ def fill_runtime(steinicp_time: float, preprocessing_time: float, stamp: float, 
     return m
 
 
+def fill_parameters(solver_param, weight_opt, stamp: float, particle_count: int = 0, **node_fields) -> Msg:
+    """The solver's part of SteinParameters.  ``weight_mean`` is the option actually in force: the reference publishes its
+    use_weight_mean flag while its weights never leave ones / P; here it is true only when the registrations end with the
+    soft-min weights (``ParticleWeightOpt.use_weight_mean`` and ``weight_dist > 0``).  ``node_fields``: the node's own
+    parameters (deskew_cloud, voxel_size, ...) by field name."""
+    m = default("stein_msgs/SteinParameters")
+    m.fields["header"] = _header(stamp)
+    in_force = bool(weight_opt is not None and weight_opt.use_weight_mean and weight_opt.weight_dist > 0)
+    m.fields.update(optimizer=str(solver_param.optimizer), iterations=int(solver_param.iterations),
+                    batch_size=int(solver_param.batch_size), particle_count=int(particle_count),
+                    normalize=bool(solver_param.normalize_cloud), learning_rate=float(solver_param.lr),
+                    correspondence_distance=float(solver_param.max_dist), early_stop=bool(solver_param.check_early_stop),
+                    converge_steps=int(solver_param.convergence_steps), converge_threshold=float(solver_param.convergence_threshold),
+                    weight_mean=in_force)
+    for k, v in node_fields.items():
+        if k not in m.fields or k == "header":
+            raise KeyError(f"SteinParameters has no field {k!r}")
+        m.fields[k] = v
+    return m
+
+
 def fill_variance(var_icp, stamp: float, var_mean_filtered=None, var_maxsliding_filtered=None, var_random_walk=None) -> Msg:
     m = default("stein_msgs/Variance")
     m.fields["header"] = _header(stamp)
