@@ -501,7 +501,7 @@ __device__ __forceinline__ void median_body(const UpdateArgs& a) {
 #pragma unroll
     for (int k = 0; k < KH; ++k) {
       const int e = tid + k * T;
-      keys[k] = __builtin_huge_val();
+      keys[k] = -1.0;                        // "no key": the keys are non-negative, and +inf is a key (an overflowed distance)
       const int i = c >= ra ? ra : Pe - 1 - ra, j = c >= ra ? c + 1 : Pe - 1 - c;
       if (e < npair && j < P) {              // (j < P also implies i < P; only an odd P has a virtual last index)
         const double sq = pair_sq(lx, i, j);
@@ -524,7 +524,7 @@ __device__ __forceinline__ void median_body(const UpdateArgs& a) {
   const int bstar = sh_bin;
 #pragma unroll
   for (int k = 0; k < KH; ++k) {
-    if (keys[k] < __builtin_huge_val() && key_bin((unsigned long long)__double_as_longlong(keys[k])) == bstar) {
+    if (keys[k] >= 0.0 && key_bin((unsigned long long)__double_as_longlong(keys[k])) == bstar) {
       const unsigned int pos = atomicAdd(&sh_cnt, 1u);
       if (pos < FRONT_BUF) lbuf[pos] = keys[k];
     }
@@ -538,7 +538,7 @@ __device__ __forceinline__ void median_body(const UpdateArgs& a) {
     // zeros: the value with #less <= r < #less + #equal is the median
     const int r = sh_rank;
     const bool zin = bstar == bin0;          // the diagonal's zeros are in this bin
-    for (int e = m + tid; e < ((m + 7) & ~7); e += T) lbuf[e] = __builtin_huge_val();  // pad to the unroll width
+    for (int e = m + tid; e < ((m + 7) & ~7); e += T) lbuf[e] = __builtin_nan("");  // pad to the unroll width: neither below nor equal to any key
     __syncthreads();
     for (int e = tid; e < m; e += T) {
       const double v = lbuf[e];

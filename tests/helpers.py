@@ -8,10 +8,11 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def golden_cases(mode=None):
+    """The whole-registration vectors of make_golden.py; stein_step.npz (make_stein_step.py) lies beside them and is not one."""
     out = []
     for f in sorted(glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))):
         name = os.path.basename(f)[:-4]
-        if mode is None or name.startswith(mode):
+        if name != "stein_step" and (mode is None or name.startswith(mode)):
             out.append(name)
     return out
 

@@ -626,7 +626,7 @@ def test_single_particle_fused_iteration(hip, orc, es):
         out[mode] = (s.get_particles(), s.get_trace()["corr"], s.get_iterations_run())
     assert np.array_equal(out["fused"][1], out["split"][1]) and out["fused"][2] == out["split"][2] == o.iterations_run()
     assert np.allclose(out["fused"][0], out["split"][0], rtol=0, atol=1e-12)
-    if es and mode == "svn":
+    if es:
         assert o.iterations_run() < I
 
 
