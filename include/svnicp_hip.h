@@ -359,6 +359,10 @@ int svnicp_finish(svnicp_ctx *ctx);
 int svnicp_stopped(svnicp_ctx *ctx);     /* 1 once the early-stop flag is set (syncs the stream) */
 void *svnicp_candidates_devptr(svnicp_ctx *ctx); /* int32 [B][K] */
 void *svnicp_sums_devptr(svnicp_ctx *ctx);       /* double [P][SVNICP_NSUMS] */
+/* the total poses stage B reads (test tap, no device work): double [P][12], R_total row-major then t_total
+ * (SVNICP.cpp:58-59).  Valid after svnicp_align_begin; a test may overwrite it before svnicp_iter_accumulate, and the
+ * next svnicp_iter_update or svnicp_set_particles rewrites it.  NULL before svnicp_set_particles. */
+void *svnicp_total_pose_devptr(svnicp_ctx *ctx);
 #define SVNICP_NSUMS 22
 
 /* ---- local map in HBM: svnicp::VoxelHashMap — src/core/VoxelHashMap.cpp:22-101, include/core/VoxelHashMap.h ----------

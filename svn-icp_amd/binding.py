@@ -163,6 +163,8 @@ def load_library():
     L.svnicp_candidates_devptr.restype = vp
     L.svnicp_sums_devptr.argtypes = [vp]
     L.svnicp_sums_devptr.restype = vp
+    L.svnicp_total_pose_devptr.argtypes = [vp]
+    L.svnicp_total_pose_devptr.restype = vp
     L.svnicp_set_minibatch.argtypes = [vp, C.c_int, C.c_uint64]
     L.svnicp_set_minibatch_indices.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.svnicp_get_minibatch_indices.argtypes = [vp, ip]

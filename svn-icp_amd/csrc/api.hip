@@ -880,6 +880,7 @@ int svnicp_stopped(svnicp_ctx* c) {
 
 void* svnicp_candidates_devptr(svnicp_ctx* c) { return c ? (void*)c->sa.cand_idx.p : nullptr; }
 void* svnicp_sums_devptr(svnicp_ctx* c) { return c ? (void*)c->sb.sums.p : nullptr; }
+void* svnicp_total_pose_devptr(svnicp_ctx* c) { return c ? (void*)c->st.Rtot.p : nullptr; }   // AccumArgs::Rtot, [P][12]
 
 // follow_stop: the caller is going to wait for the result anyway (svnicp_align) — with early stop on, the host then enqueues
 // the iterations in chunks and waits for the stop flag of the chunk before the previous one before it goes on: after the

@@ -303,7 +303,12 @@ __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a) {
 // approximates d²_k − |x'|², so argmin_k S_k is the nearest candidate unless two scores are closer
 // than the rounding error.  Bound (u = 2^-24, C = C_b, X = |x'|∞):
 //   |cc − |c'|²_real| <= 10uC²,  cross-term inputs 12.6uXC,  three fma roundings 3u(3C²+6XC)
-//   => |S_k − s_k| <= 19.1uC² + 30.8uXC  <  EPS := 40·u·C·(C+X).
+//   the reference's own float64 evaluation of d²_k: <= 5·2^-53·|T − q_k|² <= 2^-49·(C+X)²
+//   => |S_k − d²_k(reference)| <= 19.1uC² + 30.8uXC + 2^-49(C+X)²  <  EPS := 40·u·Cq·(Cq+X),  Cq = C + u·X.
+//   (The u·X in Cq is what covers the last term when the candidates lie closer together than 2^-24 of their distance to
+//   the point: there float64 itself no longer tells them apart, the reference sees a tie and takes the first index, and a
+//   float32 pick "decided" against 40uC(C+X) alone — the bound until tests/test_stage_b_gpu.py fed candidates 1e-25 m
+//   apart — named another candidate.  DESIGN.md §4.2.)
 // A lane keeps (min, argmin, second-min) of S; if second-min − min > 2·EPS its argmin is the
 // exact f64 argmin (every other candidate is strictly farther in exact arithmetic, so the
 // reference's first-index tie rule cannot matter).  Otherwise — exact ties, padded duplicates,
@@ -400,7 +405,7 @@ __global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a) {
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
       }
       const float X = __builtin_fmaxf(__builtin_fabsf(xf0), __builtin_fmaxf(__builtin_fabsf(xf1), __builtin_fabsf(xf2)));
-      const float C = cmx[pt];
+      const float C = __builtin_fmaf(5.9604644775390625e-08f, X, cmx[pt]);   // Cq = C + u·X
       const float eps2 = 2.0f * kEpsScale * C * (C + X);
       const bool ambiguous = valid && !(best2 - best1 > eps2);
       const int64_t b = b0 + pt;

@@ -109,3 +109,12 @@ def test_map_table_info_is_declared_and_mirrored(pkg):
     assert L.svnicp_map_table_info.argtypes[1:] == [C.POINTER(C.c_int64)] * 3
     assert L.svnicp_map_table_info(None, None, None, None) == -1      # SVNICP_ERR_INVALID, and no device is touched
     assert callable(pkg.pipeline.DeviceVoxelHashMap.table_info)
+
+
+def test_total_pose_tap_is_declared_and_mirrored(pkg):
+    """svnicp_total_pose_devptr (the tap tests/test_stage_b_gpu.py writes exact poses through): declared, bound as a pointer,
+    NULL without a context and without touching a device."""
+    assert "svnicp_total_pose_devptr" in pkg.declared_symbols()
+    L = pkg.load_library()
+    assert L.svnicp_total_pose_devptr.restype is C.c_void_p and L.svnicp_total_pose_devptr.argtypes == [C.c_void_p]
+    assert L.svnicp_total_pose_devptr(None) is None
