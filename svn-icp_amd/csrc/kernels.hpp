@@ -82,6 +82,10 @@ struct KnnTilesArgs {
   const int32_t* torig;
   const float* tile_box;          // [6][n_tiles]: lo xyz, hi xyz (outward rounded)
   const unsigned long long* emax_bits;
+  // tile-local rows of the matrix-pipe pre-filter (spatial_prep.hip: k_targets_sorted)
+  const float4* tile_a;           // [n_tiles][8][64]: (x', y', z', |t'|²) of the tile's 512 slots in MFMA A-operand order
+  const float4* tile_o;           // [n_tiles]: the tile's origin (float32) | C_t = max |t'|₂, rounded up (+inf: no bound)
+  int prefilter_mfma;             // 1: the scan kernel scores on the bf16 matrix pipe, 0: the float32 VALU loop
   int64_t M, Mp;
   int n_tiles;
   int64_t b_lo, b_hi;
@@ -110,7 +114,7 @@ hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int tra
                                int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_targets_sorted(const double* tgt, int64_t M, int64_t Mp, const int32_t* order, double* tx, double* ty,
                                  double* tz, float* txf, float* tyf, float* tzf, int32_t* torig, float* tile_box,
-                                 unsigned long long* emax_bits, hipStream_t st);
+                                 unsigned long long* emax_bits, float4* tile_a, float4* tile_o, hipStream_t st);
 
 // ---------------- Stage B (stein_iter.hip) ----------------
 struct AccumArgs {

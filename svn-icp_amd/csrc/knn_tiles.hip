@@ -16,7 +16,8 @@
 //  2. scan   Tiles whose box-to-box lower bound exceeds the wave's largest threshold are skipped
 //     (one vector test per 64 tiles); inside a kept tile, queries whose point-to-box bound exceeds
 //     their own threshold are skipped (one vector test per tile).  The surviving (query, tile)
-//     pairs run the f32 pre-filter loop of knn_scan.hip; survivors go to the per-query pools.
+//     pairs run a float32 pre-filter — on the bf16 matrix pipe in tile-local coordinates (default, see k_knn_scan_tiles)
+//     or the VALU loop of knn_scan.hip (option knn_prefilter = valu); survivors go to the per-query pools.
 //  3. select exact f64 d² of the pool; when a query has many survivors its threshold is first
 //     tightened from the survivors themselves (same two-minima guarantee); keep d² <= τ, bitonic
 //     sort by (d², original index), write the K best to the query's ORIGINAL row.  Pool overflow
@@ -25,6 +26,7 @@
 // All bounds are conservative: boxes are rounded outward, f32 lower bounds are shrunk by 1e-6
 // relative, thresholds are inflated by the error terms derived in knn_scan.hip.
 #include "kernels.hpp"
+#include "stein_split_device.hpp"   // split_a3 / split_b3, fmin3_raw: the bf16x3 operand construction of the stage-B search
 
 namespace svnicp {
 
@@ -40,6 +42,7 @@ constexpr int NSQ = 4;            // seed tiles chosen per query (the wave scans
 constexpr int MAX_TILES = 8192;   // bitmap capacity (M <= 4M points)
 constexpr int QB = 16;            // queries per seed batch (LDS: QB*64*2 floats)
 constexpr double kU = 5.9604644775390625e-08;  // 2^-24
+constexpr float kEpsTile = 56.0f * 5.9604644775390625e-08f;   // matrix-pipe pre-filter: 54u of DESIGN §4.2 (i)-(iii) + 2u for the roundings of EPS_t itself
 
 struct alignas(16) QF { float x, y, z, thr; };
 struct alignas(16) QD { double x, y, z, tau; };
@@ -529,12 +532,25 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
 // workgroups could share a group, cost more than they balanced).  Inside a tile, queries whose point-to-box bound exceeds
 // their own threshold are skipped (one vector test per tile); the rest run the f32 pre-filter and the survivors go to the
 // query's pool.
-template <int SW>
-__global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
+//
+// MF = true: the pre-filter runs on the bf16 matrix pipe (DESIGN §4.1 "pre-filter on the matrix pipe").  The tile's rows
+// are tile-local (spatial_prep.hip: t' = fl32(t - o), cc = fl32(|t'|²), in A-operand order), the live queries of the tile
+// are compacted into batches of 16 columns (x' = fl32(q_f32 - o); B = -2x' and 1.0), and one v_mfma_f32_16x16x32_bf16 on
+// the exact bf16x3 splits gives the 256 scores S = cc - 2 t'.x' of 16 rows x 16 queries.  A pair survives when
+// S <= theta_q = (thr_q - |x'|²) + EPS_t; EPS_t bounds every rounding between S and |t - q_f32|² - |x'|² by worst cases,
+// so the survivors are a superset of those the exact threshold admits, and the select kernel decides in float64 as before.
+// A result quad (4 rows x 1 query per lane) with a survivor is queued as ONE entry carrying its four results, and
+// flush_quads reserves the pool positions per entry: one ballot and one LDS write per row block instead of four.
+template <int SW, bool MF>
+__global__ __launch_bounds__(64 * SW) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_knn_scan_tiles(KnnTilesArgs a) {
   __shared__ __align__(16) QF s_qf[QW];
   __shared__ int s_cnt[QW];
   __shared__ int s_ticket;
   __shared__ __align__(16) int2 s_queue[SW][QCAP];
+  // MF: the tile's live queries, compacted (per wave): B-operand values, threshold, query index
+  __shared__ __align__(16) float4 s_lb[MF ? SW : 1][QW];
+  __shared__ float s_lth[MF ? SW : 1][QW];
+  __shared__ int s_lq[MF ? SW : 1][QW];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int S2 = a.S2, n_tiles = a.n_tiles;
@@ -555,7 +571,7 @@ __global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
     tphase = now;
   };
   // every wave keeps the group's queries in registers (lane = query) for the box tests; the pair loop reads them from LDS
-  float gx = 0.f, gy = 0.f, gz = 0.f, gtb = -1.0f;
+  float gx = 0.f, gy = 0.f, gz = 0.f, gtb = -1.0f, gthr = -1.0f;
   float wlo0, wlo1, wlo2, whi0, whi1, whi2, tmax;
   {
     const bool act = lane < nq;
@@ -565,7 +581,7 @@ __global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
     if (act) {
       const QRec rec = recs[q0 + lane];
       f.x = (float)rec.x; f.y = (float)rec.y; f.z = (float)rec.z; f.thr = rec.thr;
-      gtb = rec.tb;
+      gtb = rec.tb; gthr = rec.thr;
       wlo0 = f32_floor(rec.x); wlo1 = f32_floor(rec.y); wlo2 = f32_floor(rec.z);
       whi0 = f32_ceil(rec.x); whi1 = f32_ceil(rec.y); whi2 = f32_ceil(rec.z);
     }
@@ -637,6 +653,56 @@ __global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
     qcount = 0;
     wave_sync();
   };
+  // the matrix-pipe path queues result quads (see there): every entry reserves the positions of its 1-4 survivors itself
+  auto flush_quads = [&]() {
+    wave_sync();
+    for (int e0 = 0; e0 < qcount; e0 += kWave) {
+      const int e = e0 + lane;
+      const bool on = e < qcount;
+      const int2 ent = on ? queue[e] : make_int2(0, 0);
+      const int q = ent.y & (QW - 1);
+      const unsigned int bits = ((unsigned int)ent.y >> 8) & 15u;
+      const int n = __popc(bits);
+      int pos = 0;
+      if (n) pos = atomicAdd(&s_cnt[q], n);
+      const int64_t r = q0 + q;
+      // Positions past the query's own row: as in put, but in two passes over the entry's survivors — every chunk whose
+      // first position falls to this wave is allocated and published before any lane of the wave waits for an id (an
+      // entry's later survivor may open the chunk that another lane's first survivor already waits for).
+      const bool ovf = n > 0 && pos + n > kTilesBase && pos < S2;
+      const bool any_ovf = __ballot(ovf) != 0ull;
+      if (ovf) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int o = pos + j - kTilesBase;
+          if (j < n && o >= 0 && pos + j < S2 && (o % kTilesChunk) == 0) {
+            int id = atomicAdd(a.chunk_tab + a.tab_rows * (int64_t)kTilesChunks, 1) + 1;
+            if (id >= a.arena_cap) id = -2;
+            __hip_atomic_store(a.chunk_tab + r * kTilesChunks + o / kTilesChunk, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool hit = (bits >> i) & 1u;
+        if (hit && pos < kTilesBase) a.pool[r * kTilesBase + pos] = ent.x + i;
+        if (any_ovf && hit && pos >= kTilesBase && pos < S2) {
+          const int o = pos - kTilesBase;
+          int32_t* tab = a.chunk_tab + r * kTilesChunks + o / kTilesChunk;
+          int id = -1;
+          for (int spin = 0; spin < (1 << 22) && id == -1; ++spin) {
+            id = __hip_atomic_load(tab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (id == -1) __builtin_amdgcn_s_sleep(2);
+          }
+          if (id >= 0) a.arena[(int64_t)id * kTilesChunk + (o % kTilesChunk)] = ent.x + i;
+          else atomicMax(&s_cnt[q], 1 << 24);  // no chunk: the select phase hands the query to the fallback
+        }
+        pos += hit ? 1 : 0;
+      }
+    }
+    qcount = 0;
+    wave_sync();
+  };
   {
     auto next_ticket = [&]() { int v = 0; if (lane == 0) v = atomicAdd(&s_ticket, 1); return __builtin_amdgcn_readfirstlane(v); };
     int my = next_ticket(), seen = 0;
@@ -658,6 +724,75 @@ __global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
         if (!qmask) continue;
         if (a.phase_cycles) pacc[6] += __popcll(qmask);
         const int64_t tb = (int64_t)tile * STEP;
+        if constexpr (MF) {
+          const int mj = lane & 15, mk = lane >> 4;
+          const float4* rowp = a.tile_a + (size_t)tile * STEP + lane;
+          v4f ra = *reinterpret_cast<const v4f*>(rowp), rb_ = *reinterpret_cast<const v4f*>(rowp + kWave);   // chunk 0
+          const float4 org = a.tile_o[tile];   // wave-uniform: origin | C_t
+          const int nlive = __popcll(qmask), nbat = (nlive + 15) >> 4;
+          {
+            // lane = query: x' and the threshold of this (query, tile) pair
+            const float x0 = gx - org.x, x1 = gy - org.y, x2 = gz - org.z;
+            const float X2 = __builtin_fmaf(x2, x2, __builtin_fmaf(x1, x1, x0 * x0));
+            const float Xn = __builtin_amdgcn_sqrtf(X2) * 1.000002f;
+            const float eps = __builtin_fmaf(kEpsTile * org.w, __builtin_fmaf(2.0f, Xn, org.w),
+                                             __builtin_fmaf(12.0f * (float)kU, X2, __builtin_fmaf(4.0f * (float)kU, gthr, 1e-30f * (1.0f + Xn + org.w))));
+            float th = (gthr - X2) + eps;
+            th = th < __builtin_huge_valf() ? th : __builtin_huge_valf();   // NaN (a non-finite row or query) or overflow: everything survives
+            const bool live = (qmask >> lane) & 1ull;
+            const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(qmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)qmask, 0u));
+            if (live) { s_lb[wave][pos] = make_float4(-2.0f * x0, -2.0f * x1, -2.0f * x2, 1.0f); s_lth[wave][pos] = th; s_lq[wave][pos] = lane; }
+            const int padi = nlive + lane;   // the unused columns of the last batch: zero operands; masked out below
+            if (padi < 16 * nbat) { s_lb[wave][padi] = make_float4(0.f, 0.f, 0.f, 0.f); s_lth[wave][padi] = -__builtin_huge_valf(); s_lq[wave][padi] = 0; }
+          }
+          wave_sync();
+#pragma nounroll
+          for (int c = 0; c < 4; ++c) {   // chunks of 8 row blocks = 128 slots
+            bf8 afr[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { afr[k] = split_a3(ra[k]); afr[4 + k] = split_a3(rb_[k]); }
+            if (c < 3) { ra = *reinterpret_cast<const v4f*>(rowp + (2 * c + 2) * kWave); rb_ = *reinterpret_cast<const v4f*>(rowp + (2 * c + 3) * kWave); }
+#pragma nounroll
+            for (int b = 0; b < nbat; ++b) {
+              const int col = 16 * b + mj;
+              const float bv = reinterpret_cast<const float*>(&s_lb[wave][col])[mk];
+              const float th = s_lth[wave][col];
+              const bool valid = col < nlive;   // the unused columns of the last batch never survive
+              const unsigned long long vmask = __ballot(valid);
+              const bf8 bfr = split_b3(bv);
+              const v4f zero = {0.0f, 0.0f, 0.0f, 0.0f};
+              const int q = s_lq[wave][col];
+              // first slot of the chunk as a scalar: the entries' slots are one add away, nothing is precomputed per row block
+              // (the kernel is held to the 128 registers of four waves per SIMD)
+              const int srow = __builtin_amdgcn_readfirstlane((int)tb + 128 * c);
+              v4f dcur = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[0], bfr, zero, 0, 0, 0);
+              v4f dnext = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[1], bfr, zero, 0, 0, 0);
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {   // row blocks k + 1, k + 2 are on the matrix pipe while the VALU tests row block k
+                v4f dn2 = dnext;
+                if (k + 2 < 8) dn2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[k + 2 < 8 ? k + 2 : 0], bfr, zero, 0, 0, 0);
+                const v4f dk = dcur;
+                dcur = dnext; dnext = dn2;
+                // one test per result quad; a NaN score (non-finite rows: theta = +inf) counts as a survivor.  A quad with a
+                // survivor becomes ONE queue entry: its first slot, and the query with the four per-score results in bits 8-11
+                const float m4 = fmin_raw(fmin3_raw(dk[0], dk[1], dk[2]), dk[3]);
+                const bool any4 = !(m4 > th);
+                const unsigned long long m = __ballot(any4) & vmask;
+                if (m) {
+                  const unsigned int bits = (!(dk[0] > th) ? 0x100u : 0u) | (!(dk[1] > th) ? 0x200u : 0u) |
+                                            (!(dk[2] > th) ? 0x400u : 0u) | (!(dk[3] > th) ? 0x800u : 0u);
+                  const int pos = qcount + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+                  if (any4 && valid) queue[pos] = make_int2(srow + 16 * k + 4 * mk, q | (int)bits);   // result rows 4·mk … 4·mk + 3 of row block 8c + k
+                  qcount += __popcll(m);
+                }
+              }
+              qcount = __builtin_amdgcn_readfirstlane(qcount);
+              if (qcount > QCAP - 8 * kWave) flush_quads();   // a (batch, chunk) step adds at most 512 entries
+            }
+          }
+          wave_sync();   // the next tile rewrites the wave's query list
+          continue;
+        }
         float x[T], y[T], z[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) { x[t] = a.txf[tb + t * kWave + lane]; y[t] = a.tyf[tb + t * kWave + lane]; z[t] = a.tzf[tb + t * kWave + lane]; }
@@ -693,7 +828,7 @@ __global__ __launch_bounds__(64 * SW) void k_knn_scan_tiles(KnnTilesArgs a) {
       }
       seen += n_here;
     }
-    flush();
+    if constexpr (MF) flush_quads(); else flush();
   }
   phase_mark(2);
   __syncthreads();  // every wave's survivors are counted before the counts are published
@@ -736,8 +871,14 @@ hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_knn_seed, dim3((unsigned)nb), dim3(256), smem, st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (a.scan_split == 4) hipLaunchKernelGGL(k_knn_scan_tiles<4>, dim3((unsigned)((nq + QW - 1) / QW)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_knn_scan_tiles<8>, dim3((unsigned)((nq + QW - 1) / QW)), dim3(512), 0, st, a);
+  const dim3 sgrid((unsigned)((nq + QW - 1) / QW));
+  if (a.prefilter_mfma) {
+    if (a.scan_split == 4) hipLaunchKernelGGL((k_knn_scan_tiles<4, true>), sgrid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_knn_scan_tiles<8, true>), sgrid, dim3(512), 0, st, a);
+  } else {
+    if (a.scan_split == 4) hipLaunchKernelGGL((k_knn_scan_tiles<4, false>), sgrid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_knn_scan_tiles<8, false>), sgrid, dim3(512), 0, st, a);
+  }
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   int64_t nbs = (nq + WAVES - 1) / WAVES;

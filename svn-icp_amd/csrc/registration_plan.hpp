@@ -15,6 +15,7 @@ namespace svnicp {
 // test / profiling knobs of a context (svnicp_set_option); the defaults are the product configuration
 struct Tuning {
   KnnOption knn;                 // stage A kernel: automatic, or v1 | v2 | tiles | brute (stage_a_plan.hpp: plan_stage_a)
+  int knn_prefilter_mfma = 1;    // stage A tile scan: 1 = pre-filter on the bf16 matrix pipe (knn_prefilter = mfma), 0 = float32 VALU loop (valu)
   int fallback_sliced_max = -1;  // stage A: failed queries redone by target slices up to this many (-1 default)
   int accum = 3;                 // stage B: 0 f64 baseline, 1 f32 VALU search (fused), 3 search + accumulate kernels
   int update_fused = 0;          // Stein update: 1 = one fused kernel for 2 <= P <= fused_update_max_p

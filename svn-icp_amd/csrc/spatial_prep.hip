@@ -4,7 +4,8 @@
 // sort; the pair loop, not the sort, is the hot op).  Targets are then stored tile-wise: 512
 // consecutive curve points form a tile with a float32 bounding box rounded OUTWARD, so that a
 // box-to-box / point-to-box distance is a rigorous lower bound of every pair distance inside.
-// Nothing here changes results: the ordering only decides which tiles can be skipped.
+// Nothing here changes results: the ordering only decides which tiles can be skipped.  Each tile is also written in
+// tile-local float32 rows in MFMA A-operand order, for the scan kernel's pre-filter on the matrix pipe.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -116,13 +117,20 @@ __global__ __launch_bounds__(256) void k_targets_sorted(const double* __restrict
                                                         float* __restrict__ txf, float* __restrict__ tyf,
                                                         float* __restrict__ tzf, int32_t* __restrict__ torig,
                                                         float* __restrict__ tile_box /* [6][n_tiles] */, int n_tiles,
-                                                        unsigned long long* __restrict__ emax_bits) {
+                                                        unsigned long long* __restrict__ emax_bits,
+                                                        float4* __restrict__ tile_a /* [n_tiles][8][64] */,
+                                                        float4* __restrict__ tile_o /* [n_tiles] */) {
   __shared__ float red[4][6];
+  __shared__ float s_org[3], s_c[4];
+  __shared__ __align__(16) float s_rows[2048];
   const int tile = blockIdx.x;
   float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
   float hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
   double e = 0.0;
-  for (int r = threadIdx.x; r < 512; r += 256) {
+  double px[2], py[2], pz[2];   // this thread's two slots, kept for the tile-local rows below
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int r = threadIdx.x + 256 * h;
     const int64_t j = (int64_t)tile * 512 + r;
     const double nan = __builtin_nan("");
     double x = nan, y = nan, z = nan;
@@ -139,6 +147,7 @@ __global__ __launch_bounds__(256) void k_targets_sorted(const double* __restrict
     tx[j] = x; ty[j] = y; tz[j] = z;
     txf[j] = (float)x; tyf[j] = (float)y; tzf[j] = (float)z;
     torig[j] = o;
+    px[h] = x; py[h] = y; pz[h] = z;
   }
   for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
@@ -160,7 +169,46 @@ __global__ __launch_bounds__(256) void k_targets_sorted(const double* __restrict
     float v = red[0][d];
     for (int w = 1; w < 4; ++w) v = d < 3 ? __builtin_fminf(v, red[w][d]) : __builtin_fmaxf(v, red[w][d]);
     tile_box[(size_t)d * n_tiles + tile] = v;  // empty tile: lo = +inf, hi = -inf  => never needed
+    red[0][d] = v;
   }
+  // ---- tile-local rows for the matrix-pipe pre-filter (knn_tiles.hip) ----
+  // origin o = the box centre in float32 (any finite float32 serves: the bound is written in |t - o|); row of a target =
+  // t' = fl32(t - o) (float64 subtraction, rounded once), cc = fl32(|t'|²); C_t = max |t'|₂ rounded up, +inf when a row is
+  // not finite.  Padding slots: zero coordinates and cc = 1e30 — finite, never below a finite threshold.
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int d = threadIdx.x;
+    const float c = (float)(0.5 * ((double)red[0][d] + (double)red[0][3 + d]));
+    s_org[d] = (c - c == 0.0f) ? c : 0.0f;   // empty or unbounded box: any origin
+  }
+  __syncthreads();
+  const float o0 = s_org[0], o1 = s_org[1], o2 = s_org[2];
+  float cmax = 0.0f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int r = threadIdx.x + 256 * h;
+    const int64_t j = (int64_t)tile * 512 + r;
+    float v[4] = {0.0f, 0.0f, 0.0f, 1e30f};
+    if (j < M) {
+      v[0] = (float)(px[h] - (double)o0); v[1] = (float)(py[h] - (double)o1); v[2] = (float)(pz[h] - (double)o2);
+      const double n2 = ((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1]) + (double)v[2] * (double)v[2];
+      v[3] = (float)n2;
+      const float n = next_up(f32_ceil(sqrt(n2)));
+      cmax = (n - n == 0.0f) ? __builtin_fmaxf(cmax, n) : __builtin_huge_valf();   // NaN or inf row: no finite bound
+    }
+    // A-operand order: lane = 16 * component + (row mod 16), float4 index = row block / 4, element = row block mod 4
+    const int rb = r >> 4, mj = r & 15;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s_rows[(((rb >> 2) * 64) + c * 16 + mj) * 4 + (rb & 3)] = v[c];
+  }
+  for (int off = 32; off > 0; off >>= 1) cmax = __builtin_fmaxf(cmax, __shfl_xor(cmax, off, kWave));
+  if (lane == 0) s_c[wave] = cmax;
+  __syncthreads();
+  const float4* rows4 = reinterpret_cast<const float4*>(s_rows);
+  tile_a[(size_t)tile * 512 + threadIdx.x] = rows4[threadIdx.x];
+  tile_a[(size_t)tile * 512 + 256 + threadIdx.x] = rows4[256 + threadIdx.x];
+  if (threadIdx.x == 0)
+    tile_o[tile] = make_float4(o0, o1, o2, __builtin_fmaxf(__builtin_fmaxf(s_c[0], s_c[1]), __builtin_fmaxf(s_c[2], s_c[3])));
 }
 
 }  // namespace
@@ -197,12 +245,12 @@ hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, h
 
 hipError_t launch_targets_sorted(const double* tgt, int64_t M, int64_t Mp, const int32_t* order, double* tx, double* ty,
                                  double* tz, float* txf, float* tyf, float* tzf, int32_t* torig, float* tile_box,
-                                 unsigned long long* emax_bits, hipStream_t st) {
+                                 unsigned long long* emax_bits, float4* tile_a, float4* tile_o, hipStream_t st) {
   hipError_t e = hipMemsetAsync(emax_bits, 0, sizeof(unsigned long long), st);
   if (e != hipSuccess) return e;
   const int n_tiles = (int)(Mp / 512);
   hipLaunchKernelGGL(k_targets_sorted, dim3(n_tiles), dim3(256), 0, st, tgt, M, order, tx, ty, tz, txf, tyf, tzf, torig,
-                     tile_box, n_tiles, emax_bits);
+                     tile_box, n_tiles, emax_bits, tile_a, tile_o);
   return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@ struct StageA {
   TargetLayout held = TargetLayout::None;
   DevBuf<double> tx, ty, tz;
   DevBuf<float> txf, tyf, tzf, tile_box;
+  DevBuf<float4> tile_a, tile_o;         // Morton layout: tile-local rows in MFMA A-operand order, origin | C_t per tile (knn_prefilter = mfma)
   DevBuf<int32_t> torig;
   DevBuf<unsigned long long> emax, bbox;
   DevBuf<double> cand_d2;                // the result: [rows][K], ascending by (d², index)
@@ -95,6 +96,7 @@ struct StageA {
       HIPCHK(o, keys_a.ensure(nmax)); HIPCHK(o, keys_b.ensure(nmax)); HIPCHK(o, vals_a.ensure(nmax));
       HIPCHK(o, order_t.ensure(M)); HIPCHK(o, qorder.ensure(B));
       HIPCHK(o, bbox.ensure(6)); HIPCHK(o, tile_box.ensure(6 * (Mp / kTileSlots)));
+      HIPCHK(o, tile_a.ensure(Mp)); HIPCHK(o, tile_o.ensure(Mp / kTileSlots));
       if (nmax > sort_n) { sort_tmp_bytes = sort_temp_bytes(nmax); HIPCHK(o, sort_tmp.ensure(sort_tmp_bytes)); sort_n = nmax; }
     }
     if (held == plan.layout) return SVNICP_OK;
@@ -103,7 +105,7 @@ struct StageA {
     } else {
       HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, e.stream));
       HIPCHK(o, launch_morton_order(e.tgt, 0, e.M, 0, e.pose0, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes, e.stream));
-      HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, e.stream));
+      HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, tile_a.p, tile_o.p, e.stream));
     }
     held = plan.layout;
     return SVNICP_OK;
@@ -189,6 +191,7 @@ struct StageA {
       k.src = qsrc; k.pose = pose; k.qorder = qorder.p + b_lo;
       k.tx = tx.p; k.ty = ty.p; k.tz = tz.p; k.txf = txf.p; k.tyf = tyf.p; k.tzf = tzf.p;
       k.torig = torig.p; k.tile_box = tile_box.p; k.emax_bits = emax.p;
+      k.tile_a = tile_a.p; k.tile_o = tile_o.p; k.prefilter_mfma = e.tune.knn_prefilter_mfma;
       k.M = e.M; k.Mp = plan.Mp; k.n_tiles = (int)(plan.Mp / kTileSlots); k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = plan.S2;
       k.pool = pool2.p; k.out_idx = out_idx; k.out_d2 = out_d2;
       k.arena = arena.p; k.chunk_tab = chunk_tab.p; k.arena_cap = plan.arena_cap; k.tab_rows = plan.rows;
