@@ -138,7 +138,11 @@ struct DebugCounters {   // option debug (stage A keeps its own: StageA::dbg_pha
   DevBuf<unsigned long long> upd;     // phase cycles of k_particle_update
 };
 
-struct Progress { bool particles_set = false, began = false, have_candidates = false, have_result = false; };   // of the registration
+struct Progress {   // of the registration
+  bool particles_set = false, began = false, have_candidates = false, have_result = false;
+  bool table_built = false;   // stage A's select kernel has written the search table: svnicp_build_candidate_table launches nothing
+  bool d2_due = false;        // … and stored no distances: svnicp_get_candidate_dist2 recomputes them first, once
+};
 
 }  // namespace
 
@@ -438,6 +442,8 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   else if (k == "chain") { if (v == "auto") { t.small_chain = 1; t.persistent = 0; } else if (v == "persistent") { t.small_chain = 1; t.persistent = 1; }
                            else if (v == "general") { t.small_chain = 0; t.persistent = 0; } else ok = false; }
   else if (k == "median") { if (v == "auto") t.median_inline = -1; else if (v == "stream") t.median_inline = 0; else if (v == "inline") t.median_inline = 1; else ok = false; }
+  else if (k == "sort") { if (v == "joint") t.sort_joint = 1; else if (v == "separate") t.sort_joint = 0; else ok = false; }
+  else if (k == "table") { if (v == "select") t.table_select = 1; else if (v == "gather") t.table_select = 0; else ok = false; }
   else if (k == "correspondence") { if (v == "fast") t.full_corr = 0; else if (v == "full") t.full_corr = 1; else ok = false; }
   else return fail(c, SVNICP_ERR_INVALID, "svnicp_set_option: unknown option '" + k + "'");
   if (!ok) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_option: bad value '" + v + "' for option '" + k + "'");
@@ -512,7 +518,10 @@ int svnicp_align_begin(svnicp_ctx* c) {
   c->mb.nq = r.mb ? r.Bq : 0;
   HIPCHK(c, hipEventRecord(c->prof.ev[0], c->stream));
   // stage A: kernel, scratch for every search of this registration (its own, the normal pass, correspondence = full), layout
-  if (const int rc = c->sa.begin(c, stage_a_env(c), r.Bq, c->K, {c->K, normal_pass_due(c) ? c->pl.normal_k : c->K, c->tune.full_corr ? 1 : c->K})) return rc;
+  const bool joint = joint_morton_sort(f, c->tune, StageA::plan_for(stage_a_env(c), r.Bq, c->K));
+  if (const int rc = c->sa.begin(c, stage_a_env(c), r.Bq, c->K, {c->K, normal_pass_due(c) ? c->pl.normal_k : c->K, c->tune.full_corr ? 1 : c->K}, joint)) return rc;
+  c->sa.writes_table = select_writes_table(f, c->tune, c->sa.plan, shape);   // decided here, once; the calls below only follow it
+  c->run.table_built = false; c->run.d2_due = false;
   if (r.mb) {
     HIPCHK(c, c->mb.idx.ensure((size_t)r.Bt)); HIPCHK(c, c->mb.flag.ensure((size_t)B)); HIPCHK(c, c->mb.pos.ensure((size_t)B));
     HIPCHK(c, c->mb.bsum.ensure((size_t)minibatch_scan_blocks(B))); HIPCHK(c, c->mb.ctl.ensure(2));
@@ -649,7 +658,13 @@ int svnicp_stage_candidates(svnicp_ctx* c, int64_t b_lo, int64_t b_hi) {
     return SVNICP_OK;
   }
   HIPCHK(c, prof_begin(c, KC_KNN));
-  if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.src.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, b_lo, b_hi)) return rc;
+  // the whole source in one search, planned to hand the table over (a part of the rows is the sharded flow: gather)
+  const bool whole = b_lo == 0 && b_hi == c->B;
+  const bool hand_over = c->sa.writes_table && whole;
+  const TableOut tbl{c->sb.tablea.p, c->sb.anchor.p, c->sb.cmaxb.p};
+  if (const int rc = c->sa.search(c, stage_a_env(c), c->cloud.src.p, c->pose0, c->K, c->sa.cand_idx.p, c->sa.cand_d2.p, b_lo, b_hi,
+                                  hand_over ? &tbl : nullptr, whole)) return rc;
+  c->run.table_built = hand_over; c->run.d2_due = hand_over;
   if (c->tune.full_corr)   // the per-particle searches of every iteration reuse stage A's fallback list
     if (const int rc = c->sa.keep_stage_fallbacks(c, stage_a_env(c))) return rc;
   HIPCHK(c, prof_end(c));
@@ -665,7 +680,8 @@ int svnicp_build_candidate_table(svnicp_ctx* c) {
   HIPCHK(c, prof_begin(c, KC_TABLE));
   const int32_t* cand = c->mb.on ? c->mb.cand.p : c->sa.cand_idx.p;   // mini-batch: one table row per drawn position
   const int64_t rows = c->mb.on ? c->mb.rows : c->B;
-  if (const int rc = c->sb.build_table(c, cand, rows, c->K, c->cloud.tgt.p, c->M, c->stream)) return rc;
+  if (!c->run.table_built)
+    if (const int rc = c->sb.build_table(c, cand, rows, c->K, c->cloud.tgt.p, c->M, c->stream)) return rc;
   HIPCHK(c, prof_end(c));
   HIPCHK(c, hipEventRecord(c->prof.ev[1], c->stream));
   c->run.have_candidates = true;
@@ -1131,6 +1147,11 @@ int svnicp_get_candidate_dist2(svnicp_ctx* c, double* out) {
   CTX_CHECK(c);
   if (!c->run.have_candidates) return fail(c, SVNICP_ERR_INVALID, "no candidates yet");
   if (c->mb.on) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_get_candidate_dist2: ") + kMbCandMsg);
+  if (c->run.d2_due) {   // the select kernel stored none: the same distances again from cand_idx (rows of the fallback kernels included)
+    if (bind(c)) return SVNICP_ERR_HIP;
+    HIPCHK(c, launch_candidate_dist2(c->cloud.src.p, c->pose0, c->cloud.tgt.p, c->M, c->sa.cand_idx.p, c->B, c->K, c->sa.cand_d2.p, c->stream));
+    c->run.d2_due = false;
+  }
   return fetch(c, out, c->sa.cand_d2.p, (size_t)c->B * c->K * 8);
 }
 

@@ -15,6 +15,15 @@ struct Mat3 { double m[9]; };
 struct Vec3 { double v[3]; };
 struct Pose0 { double R0[9]; double t0[3]; };  // initial mean, SVGDICP.h:102-110
 
+// stage A's query: q = R0·s + t0 (SVGDICP.cpp:204), as the tile kernels' seed forms it and as the distances recomputed
+// on demand (k_candidate_dist2) must form it again
+__device__ __forceinline__ void stage_a_query(const Pose0& pose, double sx, double sy, double sz, double* x, double* y, double* z) {
+  const double* R = pose.R0;
+  *x = (sx * R[0] + sy * R[1] + sz * R[2]) + pose.t0[0];
+  *y = (sx * R[3] + sy * R[4] + sz * R[5]) + pose.t0[1];
+  *z = (sx * R[6] + sy * R[7] + sz * R[8]) + pose.t0[2];
+}
+
 // C = A*B, evaluation order of torch.matmul restated in oracle/svnicp_oracle.c mat3_mul
 __device__ __forceinline__ void mat3_mul(const double* A, const double* B, double* C) {
 #pragma unroll

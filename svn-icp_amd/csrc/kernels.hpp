@@ -98,7 +98,13 @@ struct KnnTilesArgs {
   int scan_split;                 // waves per 64-query workgroup of the scan kernel: 4 or 8
   unsigned int group_stride;      // scan kernel: workgroup i serves group (i * group_stride) mod n_groups (coprime to n_groups)
   int32_t* out_idx;
-  double* out_d2;
+  double* out_d2;                 // nullptr: the distances are not stored (svnicp_get_candidate_dist2 recomputes them: launch_candidate_dist2)
+  // the select kernel writes the split variant's search table rows itself (registration_plan.hpp: select_writes_table), as
+  // k_build_table3 (stein_split.hip) would from out_idx; tbl_a == nullptr: it does not
+  const double* tgt;              // [M][3] as given
+  float4* tbl_a;                  // [B][2][64]
+  double* tbl_anchor;             // [B][3]
+  float* tbl_cmax;                // [B]
   int32_t* fail_list;
   int* fail_count;
   int32_t* stat_n;                // optional [B]: survivors of the f32 filter per query (first pass)
@@ -107,11 +113,18 @@ struct KnnTilesArgs {
   double* fail_tau;   // optional [B]: a valid threshold (>= K-th distance) of each failed query, +inf if none
 };
 hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st);
-size_t sort_temp_bytes(size_t n);
+// d2[b][k] of idx [B][K] again, for a stage A that did not store it: the query as the seed kernel forms it, the unfused
+// ((dx·dx)+dy·dy)+dz·dz, and 0.0 for the entries a row was padded with (knn_cpu.cpp:25-26)
+hipError_t launch_candidate_dist2(const double* src, const Pose0& pose, const double* tgt, int64_t M, const int32_t* idx, int64_t B, int K,
+                                  double* d2, hipStream_t st);
+size_t sort_temp_bytes(size_t n, int key_bits);   // 30: one cloud's Morton keys, 31: the joint sort of target and queries
 hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, hipStream_t st);
 hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int transform, const Pose0& pose,
                                const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
                                int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_morton_order_joint(const double* tgt, int64_t M, const double* qsrc, int64_t n, const Pose0& pose,
+                                     const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
+                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_targets_sorted(const double* tgt, int64_t M, int64_t Mp, const int32_t* order, double* tx, double* ty,
                                  double* tz, float* txf, float* tyf, float* tzf, int32_t* torig, float* tile_box,
                                  unsigned long long* emax_bits, float4* tile_a, float4* tile_o, hipStream_t st);
@@ -167,6 +180,9 @@ void split_occupancy_blocks(int PW, int WP, int K, size_t smem, int* search, int
 // table may be nullptr (split variant): then only anchor / tablea / cmax are written
 hipError_t launch_build_table3(const int32_t* idx, int64_t B, int K, const double* tgt, int64_t M, double* table,
                                double* anchor, float4* tablea, float* cmax, hipStream_t st);
+// the rows list[0 … *count) only, both read on the device (stage A's fallback rows behind a select kernel that writes the table)
+hipError_t launch_build_table3_list(const int32_t* idx, const int32_t* list, const int* count, int64_t B, int K, const double* tgt,
+                                    int64_t M, double* anchor, float4* tablea, float* cmax, hipStream_t st);
 hipError_t launch_build_table2(const int32_t* idx, int64_t B, int K, const double* tgt, int64_t M, double* table,
                                float4* tablef, float* cmax, hipStream_t st);
 // q[b] = (s·R^T) + t with the stage-B expression (SVNICP.cpp:62-64); pose12 = device [R row-major | t]

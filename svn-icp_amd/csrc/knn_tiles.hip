@@ -118,6 +118,45 @@ __device__ __forceinline__ int pool_read(const KnnTilesArgs& a, int64_t r, int e
   return a.arena[(int64_t)id * kTilesChunk + (o % kTilesChunk)];
 }
 
+// The search table row of query b (stein_split_device.hpp: what k_build_table3 would gather from out_idx[b]) from the
+// entries the wave has just ranked.  A lane holds up to two of them: target i0 at rank r0, i1 at rank r1; a rank that is
+// negative or >= K (ties and whatever the threshold kept beyond K) is no row.  Their coordinates c0, c1 are tgt[3·i], the
+// same bits as tx/ty/tz[slot]; the caller requests them as soon as it knows i, ahead of the ranking.  (Measured and
+// dropped: the slots carried through the compaction, in LDS behind the rank flags, and tx/ty/tz[slot] read instead —
+// k_knn_select 348 against 335 us at C3.)  The rows are staged at their rank in the
+// first 2 KB of the wave's sd, which every lane has finished reading; the anchor goes through sd[256 … 258].  Each lane then
+// folds the C_b terms of rows lane and lane + 64 from the staged rows, the order k_build_table3 folds them in.
+struct P3 { double x, y, z; };
+__device__ __forceinline__ P3 target_row(const KnnTilesArgs& a, bool on, int i) {
+  P3 c{0.0, 0.0, 0.0};
+  if (on) { const double* p = a.tgt + 3 * (int64_t)i; c.x = p[0]; c.y = p[1]; c.z = p[2]; }
+  return c;
+}
+__device__ __forceinline__ void write_table_row(const KnnTilesArgs& a, int64_t b, int r0, const P3 c0, int r1, const P3 c1, double* sd, int lane) {
+  const int K = a.K;
+  const bool on0 = r0 >= 0 && r0 < K, on1 = r1 >= 0 && r1 < K;
+  const double x0 = c0.x, y0 = c0.y, z0 = c0.z, x1 = c1.x, y1 = c1.y, z1 = c1.z;
+  float* rb = reinterpret_cast<float*>(sd);
+  double* anc = sd + 256;
+  wave_sync();
+  if (on0 && r0 == 0) { anc[0] = x0; anc[1] = y0; anc[2] = z0; }
+  if (on1 && r1 == 0) { anc[0] = x1; anc[1] = y1; anc[2] = z1; }
+  wave_sync();
+  const double a0 = anc[0], a1 = anc[1], a2 = anc[2];
+  if (on0) *reinterpret_cast<float4*>(rb + 4 * r0) = table_row(x0, y0, z0, a0, a1, a2);
+  if (on1) *reinterpret_cast<float4*>(rb + 4 * r1) = table_row(x1, y1, z1, a0, a1, a2);
+  for (int k = K + lane; k < 128; k += kWave) *reinterpret_cast<float4*>(rb + 4 * k) = table_sentinel_row();
+  wave_sync();
+  float cm = 0.0f;
+  for (int k = lane; k < K; k += kWave) cm = table_row_cmax(cm, *reinterpret_cast<const float4*>(rb + 4 * k));
+  cm = table_cmax_wave(cm);
+  if (lane == 0) {
+    a.tbl_cmax[b] = cm;
+    a.tbl_anchor[3 * b] = a0; a.tbl_anchor[3 * b + 1] = a1; a.tbl_anchor[3 * b + 2] = a2;
+  }
+  table_store_rows(rb, a.tbl_a, b, lane);
+}
+
 // select: exact f64 distances of the survivors of query position r, keep d² <= tau, order by (d², original
 // index), write the K best to the query's original row.  One wave; sd/si = SL-entry LDS scratch of that wave.
 __device__ void select_query(const KnnTilesArgs& a, int64_t r, const QRec& rec, double* sd, int* si, int lane) {
@@ -248,6 +287,7 @@ __device__ void select_query(const KnnTilesArgs& a, int64_t r, const QRec& rec, 
     const int e0 = lane, e1 = lane + kWave;
     const double d0 = e0 < m ? sd[e0] : 0.0, d1 = e1 < m ? sd[e1] : 0.0;
     const int i0 = e0 < m ? si[e0] : 0, i1 = e1 < m ? si[e1] : 0;
+    const P3 c0 = target_row(a, a.tbl_a && e0 < m, i0), c1 = target_row(a, a.tbl_a && e1 < m, i1);   // in flight behind the ranking
     // rank = #(d_j < d) + #(d_j == d and i_j < i).  The first count is compare + add-with-carry per entry (no scalar
     // mask logic, which is slow behind vector compares on this chip).  Exact ties are rare: they show up as two entries
     // with the same first count (a flag per rank in LDS), and only then does the second count run.
@@ -276,8 +316,9 @@ __device__ void select_query(const KnnTilesArgs& a, int64_t r, const QRec& rec, 
         r1 += (dj == d1 && ij < i1) ? 1 : 0;
       }
     }
-    if (e0 < m && r0 < K) { a.out_idx[b * K + r0] = i0; a.out_d2[b * K + r0] = d0; }
-    if (e1 < m && r1 < K) { a.out_idx[b * K + r1] = i1; a.out_d2[b * K + r1] = d1; }
+    if (e0 < m && r0 < K) { a.out_idx[b * K + r0] = i0; if (a.out_d2) a.out_d2[b * K + r0] = d0; }
+    if (e1 < m && r1 < K) { a.out_idx[b * K + r1] = i1; if (a.out_d2) a.out_d2[b * K + r1] = d1; }
+    if (a.tbl_a) write_table_row(a, b, e0 < m ? r0 : -1, c0, e1 < m ? r1 : -1, c1, sd, lane);
     wave_sync();
   } else {
     int S = 256;
@@ -285,7 +326,11 @@ __device__ void select_query(const KnnTilesArgs& a, int64_t r, const QRec& rec, 
     for (int e = m + lane; e < S; e += kWave) { sd[e] = __builtin_huge_val(); si[e] = 0x7fffffff; }
     wave_sync();
     bitonic_sort(sd, si, S, lane);
-    for (int e = lane; e < K; e += kWave) { a.out_idx[b * K + e] = si[e]; a.out_d2[b * K + e] = sd[e]; }
+    for (int e = lane; e < K; e += kWave) { a.out_idx[b * K + e] = si[e]; if (a.out_d2) a.out_d2[b * K + e] = sd[e]; }
+    if (a.tbl_a) {   // sorted: entry e is rank e (m >= K, so the first K are survivors)
+      const int e1 = lane + kWave;
+      write_table_row(a, b, lane, target_row(a, lane < K, si[lane]), e1, target_row(a, e1 < K, e1 < K ? si[e1] : 0), sd, lane);
+    }
     wave_sync();
   }
 }
@@ -333,11 +378,7 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
     const int64_t b = act ? (int64_t)a.qorder[q0 - a.b_lo + lane] : 0;
     QD s; s.x = s.y = s.z = 0.0; s.tau = 0.0;
     if (act) {
-      const double sx = a.src[3 * b], sy = a.src[3 * b + 1], sz = a.src[3 * b + 2];
-      const double* R = a.pose.R0;
-      s.x = (sx * R[0] + sy * R[1] + sz * R[2]) + a.pose.t0[0];   // SVGDICP.cpp:204
-      s.y = (sx * R[3] + sy * R[4] + sz * R[5]) + a.pose.t0[1];
-      s.z = (sx * R[6] + sy * R[7] + sz * R[8]) + a.pose.t0[2];
+      stage_a_query(a.pose, a.src[3 * b], a.src[3 * b + 1], a.src[3 * b + 2], &s.x, &s.y, &s.z);   // SVGDICP.cpp:204
     }
     qd[lane] = s;
     QF f; f.x = (float)s.x; f.y = (float)s.y; f.z = (float)s.z; f.thr = -1.0f;
@@ -854,7 +895,43 @@ __global__ __launch_bounds__(256) void k_knn_select(KnnTilesArgs a) {
   }
 }
 
+// The distances of stage A's result again, for a select kernel that did not store them: one wave per query row, the same
+// query and the same unfused sum as the kernels that ranked by them, so the same bits.  A row with fewer than K neighbours
+// was padded with (index 0, 0.0) by the fallback kernels (knn_cpu.cpp:25-26): a NaN distance is never a neighbour, and a
+// second index 0 behind the row's first cannot be one either, so both read as padding.
+__global__ __launch_bounds__(256) void k_candidate_dist2(const double* __restrict__ src, Pose0 pose, const double* __restrict__ tgt, int64_t M,
+                                                         const int32_t* __restrict__ idx, int64_t B, int K, double* __restrict__ d2) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int64_t b = (int64_t)blockIdx.x * WAVES + wave; b < B; b += (int64_t)gridDim.x * WAVES) {
+    double qx, qy, qz;
+    stage_a_query(pose, src[3 * b], src[3 * b + 1], src[3 * b + 2], &qx, &qy, &qz);
+    int first0 = 0x7fffffff;   // rank of the row's first index 0
+    for (int k0 = 0; k0 < K && first0 == 0x7fffffff; k0 += kWave) {
+      const unsigned long long z = __ballot(k0 + lane < K && idx[b * K + k0 + lane] == 0);
+      if (z) first0 = k0 + (int)__builtin_ctzll(z);
+    }
+    for (int k = lane; k < K; k += kWave) {
+      int64_t i = idx[b * K + k];
+      const bool pad = i == 0 && k > first0;
+      i = i < 0 ? 0 : (i >= M ? M - 1 : i);
+      const double dx = qx - tgt[3 * i], dy = qy - tgt[3 * i + 1], dz = qz - tgt[3 * i + 2];
+      const double d = (dx * dx + dy * dy) + dz * dz;  // knn_cpu.cpp:43-50 order, unfused
+      d2[b * K + k] = (pad || d != d) ? 0.0 : d;
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_candidate_dist2(const double* src, const Pose0& pose, const double* tgt, int64_t M, const int32_t* idx, int64_t B, int K,
+                                  double* d2, hipStream_t st) {
+  if (B <= 0 || K <= 0) return hipSuccess;
+  int64_t nb = (B + WAVES - 1) / WAVES;
+  if (nb > 65536) nb = 65536;  // grid-stride beyond
+  hipLaunchKernelGGL(k_candidate_dist2, dim3((unsigned)nb), dim3(256), 0, st, src, pose, tgt, M, idx, B, K, d2);
+  return hipGetLastError();
+}
 
 static_assert(STEP == kTileSlots && MAX_TILES == kMaxTiles, "knn_tiles_applicable (stage_a_plan.hpp) speaks of this kernel's tiles");
 

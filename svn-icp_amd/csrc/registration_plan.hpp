@@ -32,6 +32,8 @@ struct Tuning {
                                  // measured SLOWER than the four launches per iteration on this eight-XCD part: off by default, option chain=persistent)
   int median_inline = -1;        // pair statistics in the prepare kernel's launch on the main stream also in the general chain: -1 automatic (P <= 128), 0 never (second stream), 1 the same as automatic
   int brute_qb = 0;              // brute-force stage A: queries per workgroup, 0 automatic (knn_brute_queries_per_block)
+  int sort_joint = 1;            // 1: ONE Morton sort for target and queries where joint_morton_sort allows (sort = joint), 0: two (separate, A/B)
+  int table_select = 1;          // 1: stage A's select kernel writes the search table where select_writes_table allows (table = select), 0: k_build_table3 always (gather, A/B)
   int full_corr = 0;             // 1: correspondence = full — per-particle exact NN over the whole target (SVGDICP.cpp:274-298)
 };
 
@@ -181,6 +183,25 @@ inline AccumPlan plan_stage_b(const RegistrationFacts& f, const Tuning& t, int64
   AccumPlan pl = stage_b_shape(stage_b_variant(t.accum, f.K, f.nshard(), t.full_corr != 0, f.plane), f.nshard(), f.K);
   pl.small = small_registration(pl, f, t, Bi) ? 1 : 0;
   return pl;
+}
+
+// ---------------- stage A hands its result to stage B ----------------
+// Does the select kernel of the tile family write the split variant's search table (rows, anchor, C_b) from the entries it
+// has just ranked, instead of k_build_table3 gathering them again from cand_idx?  Only where the registration's own search
+// covers the table's rows in one call: the tile kernels, the split stage B, no mini-batch (its table has one row per drawn
+// position) and no particle shard (the host gathers the candidate rows of other contexts before the table is built).  The
+// select kernel then stores no distances either: svnicp_get_candidate_dist2 recomputes them.  A call of
+// svnicp_stage_candidates for a part of the rows is the sharded flow and keeps the gather.
+inline bool select_writes_table(const RegistrationFacts& f, const Tuning& t, const StageAPlan& a, const AccumPlan& b) {
+  return t.table_select && a.kernel == KnnKernel::Tiles && a.K == f.K && b.f32 == 3 && f.batch == 0 && !f.shard_set;
+}
+
+// Are the target and the registration's queries Morton-sorted by ONE radix sort (spatial_prep.hip:
+// launch_morton_order_joint)?  Where the tile kernels' target layout has to be (re)built for this registration and its own
+// search takes the whole source in one call; StageA then leaves the layout to that search.  Any other search that comes
+// first (the plane residual's normal pass), a held target, row ranges of a sharded flow and mini-batch sort separately.
+inline bool joint_morton_sort(const RegistrationFacts& f, const Tuning& t, const StageAPlan& a) {
+  return t.sort_joint && a.kernel == KnnKernel::Tiles && a.rows == f.B && f.batch == 0 && !f.shard_set;
 }
 
 // ---------------- the Stein step ----------------

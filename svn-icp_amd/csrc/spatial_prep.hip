@@ -82,18 +82,17 @@ __device__ __forceinline__ unsigned int spread10(unsigned int v) {  // 10 bits -
 }
 
 // 30-bit Morton key of point i (optionally transformed by R0,t0) inside the encoded bbox
+// (key_or: bits set in every key — bit 30 puts a joint sort's queries behind its targets)
 __global__ void k_morton_keys(const double* __restrict__ pts, int64_t i0, int64_t n, int transform, Pose0 pose,
                               const unsigned long long* __restrict__ bbox, unsigned int* __restrict__ keys,
-                              int32_t* __restrict__ vals) {
+                              int32_t* __restrict__ vals, unsigned int key_or) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   const int64_t i = i0 + e;
   double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
   if (transform) {
-    const double* R = pose.R0;
-    const double x = (p[0] * R[0] + p[1] * R[1] + p[2] * R[2]) + pose.t0[0];
-    const double y = (p[0] * R[3] + p[1] * R[4] + p[2] * R[5]) + pose.t0[1];
-    const double z = (p[0] * R[6] + p[1] * R[7] + p[2] * R[8]) + pose.t0[2];
+    double x, y, z;
+    stage_a_query(pose, p[0], p[1], p[2], &x, &y, &z);
     p[0] = x; p[1] = y; p[2] = z;
   }
   unsigned int c[3];
@@ -105,7 +104,7 @@ __global__ void k_morton_keys(const double* __restrict__ pts, int64_t i0, int64_
     if (u > 0.999999) u = 0.999999;
     c[d] = (unsigned int)(u * 1024.0);
   }
-  keys[e] = spread10(c[0]) | (spread10(c[1]) << 1) | (spread10(c[2]) << 2);
+  keys[e] = spread10(c[0]) | (spread10(c[1]) << 1) | (spread10(c[2]) << 2) | key_or;
   vals[e] = (int32_t)i;
 }
 
@@ -213,10 +212,10 @@ __global__ __launch_bounds__(256) void k_targets_sorted(const double* __restrict
 
 }  // namespace
 
-size_t sort_temp_bytes(size_t n) {
+size_t sort_temp_bytes(size_t n, int key_bits) {
   size_t bytes = 0;
   (void)rocprim::radix_sort_pairs(nullptr, bytes, (unsigned int*)nullptr, (unsigned int*)nullptr, (int32_t*)nullptr,
-                                  (int32_t*)nullptr, n, 0, 30, (hipStream_t)0);
+                                  (int32_t*)nullptr, n, 0, key_bits, (hipStream_t)0);
   return bytes;
 }
 
@@ -226,10 +225,26 @@ hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int tra
                                int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pts, i0, n, transform, pose, bbox,
-                     keys_a, vals_a);
+                     keys_a, vals_a, 0u);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, order, (size_t)n, 0, 30, st);
+}
+
+// One sort for both clouds: the target's keys in [0, M), the keys of the n queries (pose · qsrc[0, n), inside the target's
+// box like every query key) behind them with bit 30 set, one stable 31-bit sort of the M + n pairs.  Every query key sorts
+// behind every target key and equal keys keep their input order, so order[0, M) is launch_morton_order's permutation of
+// the target and order[M, M + n) its permutation of the queries (values are row indices of their own cloud).
+hipError_t launch_morton_order_joint(const double* tgt, int64_t M, const double* qsrc, int64_t n, const Pose0& pose,
+                                     const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
+                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st) {
+  if (M <= 0 || n <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, tgt, 0, M, 0, pose, bbox, keys_a, vals_a, 0u);
+  hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, qsrc, 0, n, 1, pose, bbox, keys_a + M,
+                     vals_a + M, 1u << 30);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, order, (size_t)(M + n), 0, 31, st);
 }
 
 hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, hipStream_t st) {

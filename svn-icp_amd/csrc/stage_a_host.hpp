@@ -25,10 +25,17 @@ struct StageAEnv {
   const Pose0& pose0;
 };
 
+// where the select kernel of the tile family writes the split stage B's search table (registration_plan.hpp: select_writes_table)
+struct TableOut { float4* rows; double* anchor; float* cmax; };
+
 struct StageA {
   StageAPlan plan;   // of the registration begun last (begin)
+  bool writes_table = false;   // … and select_writes_table of it: its whole-range search writes the search table and stores no distances
   // target SoA copies in the order plan.layout names; `held` is what they hold now (None: nothing, build at the next begin)
   TargetLayout held = TargetLayout::None;
+  // registration_plan.hpp: joint_morton_sort — begin() has left the Morton layout to the registration's own search, which
+  // sorts target and queries in one pass; any other search that comes first builds it on its own (ensure_layout)
+  bool layout_pending = false;
   DevBuf<double> tx, ty, tz;
   DevBuf<float> txf, tyf, tzf, tile_box;
   DevBuf<float4> tile_a, tile_o;         // Morton layout: tile-local rows in MFMA A-operand order, origin | C_t per tile (knn_prefilter = mfma)
@@ -48,6 +55,7 @@ struct StageA {
   DevBuf<int32_t> vals_a, order_t, qorder;
   DevBuf<unsigned char> sort_tmp;
   size_t sort_n = 0, sort_tmp_bytes = 0;
+  int sort_bits = 0;
   DevBuf<int32_t> arena, chunk_tab;      // tile kernels: overflow chunks of the survivor pools and their table
   DevBuf<unsigned long long> dbg_phase;  // option debug: per-phase wave cycles of k_knn_tiles / k_knn_brute
   static constexpr size_t kDbgPhaseWaves = 65536;   // per-wave records dbg_phase has room for, behind its 8 totals
@@ -58,9 +66,10 @@ struct StageA {
   // the buffer is large enough, so a steady state allocates nothing.
   static StageAPlan plan_for(const StageAEnv& e, int64_t rows, int K) { return plan_stage_a(rows, e.M, K, e.tune.knn, e.tune.fallback_sliced_max); }
   template <class Obj>
-  int begin(Obj* o, const StageAEnv& e, int64_t rows, int K, std::initializer_list<int> Ks) {
+  int begin(Obj* o, const StageAEnv& e, int64_t rows, int K, std::initializer_list<int> Ks, bool joint_sort = false) {
     plan = plan_for(e, rows, K);
     stage_kept = false;
+    layout_pending = false;
     const size_t Bq = (size_t)rows, B = (size_t)e.B, M = (size_t)e.M, Mp = (size_t)plan.Mp;
     size_t S = 0, slice_entries = 0;
     for (const int k : Ks) { S = std::max<size_t>(S, knn_pool_size(k)); slice_entries = std::max<size_t>(slice_entries, (size_t)knn_slice_count(k) * k); }
@@ -92,14 +101,28 @@ struct StageA {
     HIPCHK(o, txf.ensure(Mp)); HIPCHK(o, tyf.ensure(Mp)); HIPCHK(o, tzf.ensure(Mp));
     HIPCHK(o, torig.ensure(Mp)); HIPCHK(o, emax.ensure(1));
     if (plan.layout == TargetLayout::Morton) {   // both clouds are sorted along the curve: the target once, the queries per search
-      const size_t nmax = std::max(M, B);
+      const bool joint = joint_sort && held != plan.layout;   // one sort of M + B pairs with 31-bit keys: order_t holds both permutations
+      const size_t nmax = joint ? M + B : std::max(M, B);
+      const int bits = joint ? 31 : 30;
       HIPCHK(o, keys_a.ensure(nmax)); HIPCHK(o, keys_b.ensure(nmax)); HIPCHK(o, vals_a.ensure(nmax));
-      HIPCHK(o, order_t.ensure(M)); HIPCHK(o, qorder.ensure(B));
+      HIPCHK(o, order_t.ensure(joint ? M + B : M)); HIPCHK(o, qorder.ensure(B));
       HIPCHK(o, bbox.ensure(6)); HIPCHK(o, tile_box.ensure(6 * (Mp / kTileSlots)));
       HIPCHK(o, tile_a.ensure(Mp)); HIPCHK(o, tile_o.ensure(Mp / kTileSlots));
-      if (nmax > sort_n) { sort_tmp_bytes = sort_temp_bytes(nmax); HIPCHK(o, sort_tmp.ensure(sort_tmp_bytes)); sort_n = nmax; }
+      if (nmax > sort_n || bits > sort_bits) {   // rocPRIM's scratch for the larger of the two sorts seen so far
+        sort_n = std::max(sort_n, nmax); sort_bits = std::max(sort_bits, bits);
+        sort_tmp_bytes = std::max(sort_temp_bytes(sort_n, sort_bits), sort_temp_bytes(sort_n, 30));
+        HIPCHK(o, sort_tmp.ensure(sort_tmp_bytes));
+      }
+      if (joint) { layout_pending = true; return SVNICP_OK; }
     }
-    if (held == plan.layout) return SVNICP_OK;
+    return ensure_layout(o, e);
+  }
+
+  // the target copies in the plan's layout, built on their own when they are not held
+  template <class Obj>
+  int ensure_layout(Obj* o, const StageAEnv& e) {
+    layout_pending = false;
+    if (held == plan.layout || plan.layout == TargetLayout::None) return SVNICP_OK;
     if (plan.layout == TargetLayout::Hashed) {
       HIPCHK(o, launch_targets_soa2(e.tgt, e.M, plan.Mp, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, emax.p, e.stream));
     } else {
@@ -163,11 +186,16 @@ struct StageA {
 
   // exact top-K of pose·qsrc[b_lo, b_hi) against the whole target into out_idx / out_d2 ([rows][K]).  K is the plan's for
   // stage A proper; a caller with a K of its own (normal pass, correspondence = full) asks plan.can_search(K) first and
-  // words the refusal itself.  At most plan.rows query rows.
+  // words the refusal itself.  At most plan.rows query rows.  tbl (tile kernels only, writes_table): the select kernel also
+  // writes these rows' search table and leaves out_d2 to the rows the fallback kernels redo.  whole_source: the
+  // registration's own search over all of its source rows — the one a pending layout was left to (joint sort).
   template <class Obj>
   int search(Obj* o, const StageAEnv& e, const double* qsrc, const Pose0& pose, int K, int32_t* out_idx, double* out_d2, int64_t b_lo,
-             int64_t b_hi) {
+             int64_t b_hi, const TableOut* tbl = nullptr, bool whole_source = false) {
     const int64_t n = b_hi - b_lo;
+    const bool joint = layout_pending && whole_source && plan.kernel == KnnKernel::Tiles && b_lo == 0 && n == e.B && n > 0;
+    if (layout_pending && !joint)
+      if (const int rc = ensure_layout(o, e)) return rc;
     KnnArgs a{};
     a.src = qsrc; a.pose = pose; a.tx = tx.p; a.ty = ty.p; a.tz = tz.p; a.torig = torig.p;
     a.M = e.M; a.Mp = plan.Mp; a.b_lo = b_lo; a.b_hi = b_hi; a.K = K; a.S = knn_pool_size(K);
@@ -186,14 +214,25 @@ struct StageA {
     }
     case KnnKernel::Tiles: {
       if (n <= 0) return SVNICP_OK;
-      HIPCHK(o, launch_morton_order(qsrc, b_lo, n, 1, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, qorder.p + b_lo, sort_tmp.p, sort_tmp_bytes, e.stream));
+      const int32_t* qord = qorder.p + b_lo;
+      if (joint) {   // target and queries in one sort: order_t[0, M) is the target's permutation, order_t[M, M + n) the queries'
+        HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, e.stream));
+        HIPCHK(o, launch_morton_order_joint(e.tgt, e.M, qsrc, n, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes, e.stream));
+        HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, tile_a.p, tile_o.p, e.stream));
+        held = plan.layout; layout_pending = false;
+        qord = order_t.p + e.M;
+      } else {
+        HIPCHK(o, launch_morton_order(qsrc, b_lo, n, 1, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, qorder.p + b_lo, sort_tmp.p, sort_tmp_bytes, e.stream));
+      }
       KnnTilesArgs k{};
-      k.src = qsrc; k.pose = pose; k.qorder = qorder.p + b_lo;
+      k.src = qsrc; k.pose = pose; k.qorder = qord;
       k.tx = tx.p; k.ty = ty.p; k.tz = tz.p; k.txf = txf.p; k.tyf = tyf.p; k.tzf = tzf.p;
       k.torig = torig.p; k.tile_box = tile_box.p; k.emax_bits = emax.p;
       k.tile_a = tile_a.p; k.tile_o = tile_o.p; k.prefilter_mfma = e.tune.knn_prefilter_mfma;
       k.M = e.M; k.Mp = plan.Mp; k.n_tiles = (int)(plan.Mp / kTileSlots); k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = plan.S2;
-      k.pool = pool2.p; k.out_idx = out_idx; k.out_d2 = out_d2;
+      k.pool = pool2.p; k.out_idx = out_idx; k.out_d2 = tbl ? nullptr : out_d2;
+      k.tgt = e.tgt;
+      if (tbl) { k.tbl_a = tbl->rows; k.tbl_anchor = tbl->anchor; k.tbl_cmax = tbl->cmax; }
       k.arena = arena.p; k.chunk_tab = chunk_tab.p; k.arena_cap = plan.arena_cap; k.tab_rows = plan.rows;
       k.scan_split = e.tune.scan_split == 4 ? 4 : 8;
       {  // a small stride coprime to n_groups: 17 sweeps over the curve (C3 1.04 -> 0.98 ms, C5 1.83 -> 1.65 ms against natural order)
@@ -219,6 +258,8 @@ struct StageA {
       if (dbg)
         if (const int rc = print_phases(o, e, n, dbg_waves)) return rc;
       HIPCHK(o, launch_fallback(a, e.stream));
+      if (tbl)   // the rows the fallback kernels rewrote: gathered from out_idx, as k_build_table3 does for every row elsewhere
+        HIPCHK(o, launch_build_table3_list(out_idx, fail_list.p, fail_count.p, e.B, K, e.tgt, e.M, tbl->anchor, tbl->rows, tbl->cmax, e.stream));
       return SVNICP_OK;
     }
     case KnnKernel::SeededScan: {   // f32 pre-filter (knn_scan.hip) with knn_topk.hip as fallback
@@ -261,7 +302,10 @@ struct StageA {
   }
 
   // svnicp_get_knn_fallbacks / _rows describe STAGE A, not a later K = 1 search through the same working set: called behind
-  // stage A when such searches follow (correspondence = full), or ahead of the first one (svnicp_evaluate, unless kept already)
+  // stage A when such searches follow (correspondence = full), or ahead of the first one (svnicp_evaluate, unless kept already).
+  // The list is copied whole, plan.rows entries whatever the count says: the count lives on the device, so a copy of only
+  // the listed rows would be a kernel of its own (the same launch for at most 0.5 MB less at C3), and neither caller is on
+  // the path of a default registration.
   template <class Obj>
   int keep_stage_fallbacks(Obj* o, const StageAEnv& e) {
     if (!plan.has_fallback()) return SVNICP_OK;

@@ -25,22 +25,16 @@ namespace {
 // blocks; rows past K are finite sentinels), the origin of the local frame and C_b = max |c'|₂ rounded up (the error
 // bound's C2).  (Candidates 96…99 — the tile the owner lanes score themselves when K is 97…100 — are row block 6 like any other.)  Replaces the I copies of target_batch [B,K,3] of SVGDICP.cpp:191-198.
 // ---------------------------------------------------------------------------------------------
-constexpr float kSentinelCC = 1.0e30f; // padded rows: finite, so packed words never become NaN patterns
-__global__ __launch_bounds__(256) void k_build_table3(const int32_t* __restrict__ idx, int64_t B, int K,
-                                                      const double* __restrict__ tgt, int64_t M, double* __restrict__ table,
-                                                      double* __restrict__ anchor, float4* __restrict__ tablea,
-                                                      float* __restrict__ cmax) {
-  __shared__ float rowbuf[4][128 * 4];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
-  if (b >= B) return;  // whole wave
+// one wave: rows of source point b from its K indices
+__device__ __forceinline__ void build_table3_row(const int32_t* __restrict__ idx, int64_t b, int K, const double* __restrict__ tgt, int64_t M,
+                                                 double* __restrict__ table, double* __restrict__ anchor, float4* __restrict__ tablea,
+                                                 float* __restrict__ cmax, float* rb, int lane) {
   int64_t i0 = idx[b * K];
   i0 = i0 < 0 ? 0 : (i0 >= M ? M - 1 : i0);  // clamped: a corrupted candidate list must never become a wild gather
   const double a0 = tgt[3 * i0], a1 = tgt[3 * i0 + 1], a2 = tgt[3 * i0 + 2];
   float cm = 0.0f;
-  float* rb = rowbuf[wave];
   for (int k = lane; k < 128; k += kWave) {
-    float cx = 0.f, cy = 0.f, cz = 0.f, cc = kSentinelCC;
+    float4 row = table_sentinel_row();
     if (k < K) {
       int64_t i = idx[b * K + k];
       i = i < 0 ? 0 : (i >= M ? M - 1 : i);
@@ -49,33 +43,46 @@ __global__ __launch_bounds__(256) void k_build_table3(const int32_t* __restrict_
         double* o = table + ((size_t)b * K + k) * 3;
         o[0] = x; o[1] = y; o[2] = z;
       }
-      cx = (float)(x - a0); cy = (float)(y - a1); cz = (float)(z - a2);
-      cc = (float)(((double)cx * cx + (double)cy * cy) + (double)cz * cz);
-      // C_b = max |c'|_2 over the point's candidates, rounded up (>= max |c'|_inf, which is all the f32 kernels' bounds need;
-      // the bf16 search kernel's bound is written in the 2-norm, stein_split.hip)
-      cm = __builtin_fmaxf(cm, (float)sqrt(((double)cx * cx + (double)cy * cy) + (double)cz * cz) * 1.0000002f);
-      if (!(cc < kSentinelCC)) cm = __builtin_nanf("");  // huge or NaN rows: every step of this point takes the exact path
+      row = table_row(x, y, z, a0, a1, a2);
+      cm = table_row_cmax(cm, row);
     }
-    rb[4 * k] = cx; rb[4 * k + 1] = cy; rb[4 * k + 2] = cz; rb[4 * k + 3] = cc;
+    *reinterpret_cast<float4*>(rb + 4 * k) = row;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    const float o = __shfl_xor(cm, off, kWave);
-    cm = (cm != cm || o != o) ? __builtin_nanf("") : __builtin_fmaxf(cm, o);
-  }
+  cm = table_cmax_wave(cm);
   if (lane == 0) {
     cmax[b] = cm;
     anchor[3 * b] = a0; anchor[3 * b + 1] = a1; anchor[3 * b + 2] = a2;
   }
   __builtin_amdgcn_wave_barrier();
-  const int mi = lane & 15, mk = lane >> 4;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float4 v;
-    v.x = rb[4 * (16 * (4 * h + 0) + mi) + mk];
-    v.y = rb[4 * (16 * (4 * h + 1) + mi) + mk];
-    v.z = rb[4 * (16 * (4 * h + 2) + mi) + mk];
-    v.w = rb[4 * (16 * (4 * h + 3) + mi) + mk];
-    tablea[((size_t)b * 2 + h) * 64 + lane] = v;
+  table_store_rows(rb, tablea, b, lane);
+}
+
+__global__ __launch_bounds__(256) void k_build_table3(const int32_t* __restrict__ idx, int64_t B, int K,
+                                                      const double* __restrict__ tgt, int64_t M, double* __restrict__ table,
+                                                      double* __restrict__ anchor, float4* __restrict__ tablea,
+                                                      float* __restrict__ cmax) {
+  __shared__ __align__(16) float rowbuf[4][128 * 4];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+  if (b >= B) return;  // whole wave
+  build_table3_row(idx, b, K, tgt, M, table, anchor, tablea, cmax, rowbuf[wave], lane);
+}
+
+// list variant: the rows list[0 … *count) only (the queries stage A's fallback kernels redid behind a select kernel that
+// writes the table itself); a fixed grid strides over the list, and an empty list costs one early-exiting launch
+constexpr int kTableListGrid = 64;
+__global__ __launch_bounds__(256) void k_build_table3_list(const int32_t* __restrict__ idx, const int32_t* __restrict__ list,
+                                                           const int* __restrict__ count, int64_t B, int K,
+                                                           const double* __restrict__ tgt, int64_t M, double* __restrict__ anchor,
+                                                           float4* __restrict__ tablea, float* __restrict__ cmax) {
+  __shared__ __align__(16) float rowbuf[4][128 * 4];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int64_t n = *count;
+  for (int64_t e = (int64_t)blockIdx.x * 4 + wave; e < n && e < B; e += (int64_t)gridDim.x * 4) {
+    const int64_t b = list[e];
+    if (b < 0 || b >= B) continue;  // whole wave
+    build_table3_row(idx, b, K, tgt, M, nullptr, anchor, tablea, cmax, rowbuf[wave], lane);
+    __builtin_amdgcn_wave_barrier();   // the next row rewrites the wave's staging buffer
   }
 }
 
@@ -150,6 +157,13 @@ hipError_t launch_build_table3(const int32_t* idx, int64_t B, int K, const doubl
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_build_table3, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, idx, B, K, tgt, M, table, anchor, tablea,
                      cmax);
+  return hipGetLastError();
+}
+
+hipError_t launch_build_table3_list(const int32_t* idx, const int32_t* list, const int* count, int64_t B, int K, const double* tgt,
+                                    int64_t M, double* anchor, float4* tablea, float* cmax, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_build_table3_list, dim3(kTableListGrid), dim3(256), 0, st, idx, list, count, B, K, tgt, M, anchor, tablea, cmax);
   return hipGetLastError();
 }
 

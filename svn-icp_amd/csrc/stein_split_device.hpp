@@ -28,6 +28,48 @@ __device__ __forceinline__ float imax_f(float a, float b) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// One row of the search kernel's candidate table, stated once for the kernels that write it: k_build_table3 and its list
+// variant (stein_split.hip) gather the row from stage A's indices, k_knn_select (knn_tiles.hip) writes it from the entries
+// it has just ranked.  A wave stages the 128 rows of a source point in 2 KB of LDS (row k at rb + 4k) and stores them in
+// MFMA A-operand order.
+// ---------------------------------------------------------------------------------------------
+constexpr float kSentinelCC = 1.0e30f; // padded rows: finite, so packed words never become NaN patterns
+// candidate (x, y, z) relative to the point's first candidate (a0, a1, a2): (c'x, c'y, c'z, |c'|²) in float32
+__device__ __forceinline__ float4 table_row(double x, double y, double z, double a0, double a1, double a2) {
+  const float cx = (float)(x - a0), cy = (float)(y - a1), cz = (float)(z - a2);
+  const float cc = (float)(((double)cx * cx + (double)cy * cy) + (double)cz * cz);
+  return make_float4(cx, cy, cz, cc);
+}
+__device__ __forceinline__ float4 table_sentinel_row() { return make_float4(0.f, 0.f, 0.f, kSentinelCC); }
+// C_b = max |c'|_2 over the point's candidates, rounded up (>= max |c'|_inf, which is all the f32 kernels' bounds need;
+// the bf16 search kernel's bound is written in the 2-norm): a lane folds its rows k = lane, lane + 64 in this order
+__device__ __forceinline__ float table_row_cmax(float cm, const float4 r) {
+  cm = __builtin_fmaxf(cm, (float)sqrt(((double)r.x * r.x + (double)r.y * r.y) + (double)r.z * r.z) * 1.0000002f);
+  if (!(r.w < kSentinelCC)) cm = __builtin_nanf("");  // huge or NaN rows: every step of this point takes the exact path
+  return cm;
+}
+__device__ __forceinline__ float table_cmax_wave(float cm) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const float o = __shfl_xor(cm, off, kWave);
+    cm = (cm != cm || o != o) ? __builtin_nanf("") : __builtin_fmaxf(cm, o);
+  }
+  return cm;
+}
+// the staged rows of source point b leave as two transposed float4 per lane (lane = 16·component + candidate mod 16)
+__device__ __forceinline__ void table_store_rows(const float* rb, float4* __restrict__ tablea, int64_t b, int lane) {
+  const int mi = lane & 15, mk = lane >> 4;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float4 v;
+    v.x = rb[4 * (16 * (4 * h + 0) + mi) + mk];
+    v.y = rb[4 * (16 * (4 * h + 1) + mi) + mk];
+    v.z = rb[4 * (16 * (4 * h + 2) + mi) + mk];
+    v.w = rb[4 * (16 * (4 * h + 3) + mi) + mk];
+    tablea[((size_t)b * 2 + h) * 64 + lane] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // search on the bf16 matrix pipe
 // ---------------------------------------------------------------------------------------------
 // Measured on gfx950 (tests/microbench/search_loop.hip, valu_ops.hip): v_mfma_f32_16x16x4_f32 holds the SIMD's
