@@ -324,7 +324,7 @@ static int upload_cloud(svnicp_ctx* c, DevBuf<double>& buf, const double* xyz, i
 int svnicp_set_source(svnicp_ctx* c, const double* src, int64_t B, int mem_kind) {
   CTX_CHECK(c);
   if (!src || B < 1) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_source: need B >= 1");
-  if (B > 0x7fffffffLL) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_source: cloud too large");
+  if (const char* why = cloud_rows_refusal(B)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_set_source: ") + why);
   if (const int rc = upload_cloud(c, c->cloud.src, src, B, mem_kind)) return rc;
   c->B = B;
   c->cloud.src_set = true;
@@ -334,7 +334,7 @@ int svnicp_set_source(svnicp_ctx* c, const double* src, int64_t B, int mem_kind)
 int svnicp_set_target(svnicp_ctx* c, const double* tgt, int64_t M, int mem_kind) {
   CTX_CHECK(c);
   if (!tgt || M < 1) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target: need M >= 1");
-  if (M > 0x7fffffffLL) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_target: cloud too large");
+  if (const char* why = cloud_rows_refusal(M)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_set_target: ") + why);
   if (const int rc = upload_cloud(c, c->cloud.tgt, tgt, M, mem_kind)) return rc;
   c->M = M;
   c->sa.held = TargetLayout::None;  // the SoA copies are (re)built in svnicp_align_begin, once K is final
@@ -346,7 +346,7 @@ int svnicp_set_target(svnicp_ctx* c, const double* tgt, int64_t M, int mem_kind)
 int svnicp_set_clouds(svnicp_ctx* c, const double* src, int64_t B, const double* tgt, int64_t M, int mem_kind) {
   CTX_CHECK(c);
   if (!src || !tgt || B < 1 || M < 1) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_clouds: need B >= 1, M >= 1");
-  if (M > 0x7fffffffLL || B > 0x7fffffffLL) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_clouds: cloud too large");
+  if (const char* why = cloud_rows_refusal(M > B ? M : B)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_set_clouds: ") + why);
   if (const int rc = svnicp_set_source(c, src, B, mem_kind)) return rc;
   return svnicp_set_target(c, tgt, M, mem_kind);
 }
@@ -443,6 +443,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
                            else if (v == "general") { t.small_chain = 0; t.persistent = 0; } else ok = false; }
   else if (k == "median") { if (v == "auto") t.median_inline = -1; else if (v == "stream") t.median_inline = 0; else if (v == "inline") t.median_inline = 1; else ok = false; }
   else if (k == "sort") { if (v == "joint") t.sort_joint = 1; else if (v == "separate") t.sort_joint = 0; else ok = false; }
+  else if (k == "sort_kernel") { if (v == "radix") t.sort_merge = 0; else if (v == "merge") t.sort_merge = 1; else ok = false; }
   else if (k == "table") { if (v == "select") t.table_select = 1; else if (v == "gather") t.table_select = 0; else ok = false; }
   else if (k == "correspondence") { if (v == "fast") t.full_corr = 0; else if (v == "full") t.full_corr = 1; else ok = false; }
   else return fail(c, SVNICP_ERR_INVALID, "svnicp_set_option: unknown option '" + k + "'");
@@ -568,9 +569,17 @@ int svnicp_align_begin(svnicp_ctx* c) {
     HIPCHK(c, c->st.small_bar.ensure(8));
     add(c->st.small_bar.p, 8 * sizeof(unsigned int));
     if (c->prm.mode == SVNICP_MODE_SVGD) add(c->st.opt.p, (size_t)P * 18 * sizeof(double));
+    // stage A's joint search comes next (StageA::begin left the layout to it): the bounding box's minima (all ones) and maxima,
+    // the largest coordinate and the fallback count start here too, instead of four fills between its kernels
+    const bool sa_words = c->sa.layout_pending;
+    if (sa_words) {
+      add(c->sa.bbox.p + 3, 3 * sizeof(unsigned long long)); add(c->sa.emax.p, sizeof(unsigned long long)); add(c->sa.fail_count.p, sizeof(int));
+      z.ones = reinterpret_cast<unsigned int*>(c->sa.bbox.p); z.ones_dwords = 6;
+    }
     z.ctl = c->st.ctl.p; z.iterations = I;
     HIPCHK(c, launch_init_particles(c->st.init_pose.p, P, c->pose0, 2, c->st.R.p, c->st.t.p, c->st.Rtot.p, c->st.pose_out.p, 0,
                                     nullptr, c->stream, &z));
+    c->sa.start_words_set = sa_words;
   }
   if (c->mb.batch > 0 && !c->mb.explicit_tab) {   // the table of the n-th registration after svnicp_set_minibatch
     c->mb.base = minibatch_stream_base(c->mb.seed, c->mb.n);

@@ -118,16 +118,20 @@ hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st);
 hipError_t launch_candidate_dist2(const double* src, const Pose0& pose, const double* tgt, int64_t M, const int32_t* idx, int64_t B, int K,
                                   double* d2, hipStream_t st);
 size_t sort_temp_bytes(size_t n, int key_bits);   // 30: one cloud's Morton keys, 31: the joint sort of target and queries
-hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, hipStream_t st);
+hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, bool cleared, hipStream_t st);
+// rocprim_sort: rocprim::radix_sort_pairs (option sort_kernel = merge) instead of the file's own radix chain; fill_ff[0, fill_words): set
+// to -1 by the (query) key kernel on the way
 hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int transform, const Pose0& pose,
                                const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
-                               int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
+                               int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, bool rocprim_sort, int32_t* fill_ff,
+                               size_t fill_words, hipStream_t st);
 hipError_t launch_morton_order_joint(const double* tgt, int64_t M, const double* qsrc, int64_t n, const Pose0& pose,
                                      const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
-                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
+                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, bool rocprim_sort, int32_t* fill_ff,
+                                     size_t fill_words, hipStream_t st);
 hipError_t launch_targets_sorted(const double* tgt, int64_t M, int64_t Mp, const int32_t* order, double* tx, double* ty,
                                  double* tz, float* txf, float* tyf, float* tzf, int32_t* torig, float* tile_box,
-                                 unsigned long long* emax_bits, float4* tile_a, float4* tile_o, hipStream_t st);
+                                 unsigned long long* emax_bits, bool emax_cleared, float4* tile_a, float4* tile_o, hipStream_t st);
 
 // ---------------- Stage B (stein_iter.hip) ----------------
 struct AccumArgs {
@@ -219,7 +223,8 @@ struct UpdateArgs {
 };
 size_t update_workspace_doubles(int P);
 // areas k_init_particles clears at the start of a registration (whole 32-bit words), and the control words it resets
-struct BeginZero { unsigned int* ptr[6]; unsigned int dwords[6]; int n; int* ctl; int iterations; };
+// (ones: an area set to all ones instead — stage A's bounding-box minima)
+struct BeginZero { unsigned int* ptr[10]; unsigned int dwords[10]; int n; int* ctl; int iterations; unsigned int* ones; unsigned int ones_dwords; };
 hipError_t launch_init_particles(const double* init6xP, int P, const Pose0& pose, int mode, double* R, double* t,
                                  double* Rtot, double* pose_out, int refresh_pose, double* eul, hipStream_t st, const BeginZero* zero = nullptr);
 // stage B accumulate (fused variants: whole stage B); single: see stein_iter.hip — the one-particle iteration in one launch

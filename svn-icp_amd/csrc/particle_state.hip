@@ -14,6 +14,7 @@ __global__ void k_init_particles(const double* __restrict__ init, int P, Pose0 p
   // launch instead of five fill / copy launches of their own (each one costs a small registration 5-8 us)
   for (int a = 0; a < z.n; ++a)
     for (unsigned int e = (unsigned int)p; e < z.dwords[a]; e += gridDim.x * blockDim.x) z.ptr[a][e] = 0u;
+  for (unsigned int e = (unsigned int)p; e < z.ones_dwords; e += gridDim.x * blockDim.x) z.ones[e] = 0xffffffffu;
   if (z.ctl && p == 0) { z.ctl[0] = 0; z.ctl[1] = z.iterations; z.ctl[2] = 0; z.ctl[3] = 0; }   // stop flag, finish_iter (SVGDICP.cpp:42)
   if (p >= P) return;
   double r[3] = {0, 0, 0}, tv[3], Rm[9];

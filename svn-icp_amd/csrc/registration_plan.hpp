@@ -33,6 +33,8 @@ struct Tuning {
   int median_inline = -1;        // pair statistics in the prepare kernel's launch on the main stream also in the general chain: -1 automatic (P <= 128), 0 never (second stream), 1 the same as automatic
   int brute_qb = 0;              // brute-force stage A: queries per workgroup, 0 automatic (knn_brute_queries_per_block)
   int sort_joint = 1;            // 1: ONE Morton sort for target and queries where joint_morton_sort allows (sort = joint), 0: two (separate, A/B)
+  int sort_merge = 0;            // Morton sorts: 0 = the project's three-pass radix chain (spatial_prep.hip), 1 = rocPRIM's radix_sort_pairs, its merge
+                                 // path at these sizes (sort_kernel = radix | merge: A/B and the tests' second opinion)
   int table_select = 1;          // 1: stage A's select kernel writes the search table where select_writes_table allows (table = select), 0: k_build_table3 always (gather, A/B)
   int full_corr = 0;             // 1: correspondence = full — per-particle exact NN over the whole target (SVGDICP.cpp:274-298)
 };
@@ -83,6 +85,11 @@ constexpr const char* kMinibatchRefusal = "svnicp_align: mini-batch mode (svnicp
 constexpr const char* kPlaneRefusal = "svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ";
 constexpr const char* kWeightingRefusal = "svnicp_align: particle weighting (svnicp_set_particle_weighting) is not available here: ";
 constexpr const char* kScoringRefusal = "svnicp_score_particles: the last registration cannot be scored: ";
+
+// A cloud's row count: row indices are int32 everywhere behind stage A (cand, kidx, torig, full_idx, the Morton sorts'
+// values); a row's byte offset 24 * index is formed in 64 bits.
+constexpr int64_t kMaxCloudRows = 0x7fffffffLL;   // 2^31 - 1: 24 * (kMaxCloudRows - 1) < 2^36
+inline const char* cloud_rows_refusal(int64_t rows) { return rows > kMaxCloudRows ? "cloud too large" : nullptr; }
 
 // mini-batch: what it is not combined with (nullptr: nothing, or mini-batch is off)
 inline const char* minibatch_refusal(const RegistrationFacts& f, const Tuning& t) {

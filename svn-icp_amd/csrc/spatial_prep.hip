@@ -1,7 +1,7 @@
 // spatial_prep.hip — spatial ordering for the pruned stage-A kernel (knn_tiles.hip).
 //
-// Targets and (transformed) queries are sorted along a 30-bit Morton curve (rocPRIM device radix
-// sort; the pair loop, not the sort, is the hot op).  Targets are then stored tile-wise: 512
+// Targets and (transformed) queries are sorted along a 30-bit Morton curve (a three-pass radix sort
+// of this file, or rocPRIM's device radix sort; the pair loop, not the sort, is the hot op).  Targets are then stored tile-wise: 512
 // consecutive curve points form a tile with a float32 bounding box rounded OUTWARD, so that a
 // box-to-box / point-to-box distance is a rigorous lower bound of every pair distance inside.
 // Nothing here changes results: the ordering only decides which tiles can be skipped.  Each tile is also written in
@@ -83,10 +83,12 @@ __device__ __forceinline__ unsigned int spread10(unsigned int v) {  // 10 bits -
 
 // 30-bit Morton key of point i (optionally transformed by R0,t0) inside the encoded bbox
 // (key_or: bits set in every key — bit 30 puts a joint sort's queries behind its targets)
+// fill_ff[0, fill_words): set to -1 on the way, grid-stride (the tile kernels' chunk table, instead of a fill launch of its own)
 __global__ void k_morton_keys(const double* __restrict__ pts, int64_t i0, int64_t n, int transform, Pose0 pose,
                               const unsigned long long* __restrict__ bbox, unsigned int* __restrict__ keys,
-                              int32_t* __restrict__ vals, unsigned int key_or) {
+                              int32_t* __restrict__ vals, unsigned int key_or, int32_t* __restrict__ fill_ff, size_t fill_words) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t w = (size_t)e; w < fill_words; w += (size_t)gridDim.x * blockDim.x) fill_ff[w] = -1;
   if (e >= n) return;
   const int64_t i = i0 + e;
   double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
@@ -210,25 +212,195 @@ __global__ __launch_bounds__(256) void k_targets_sorted(const double* __restrict
     tile_o[tile] = make_float4(o0, o1, o2, __builtin_fmaxf(__builtin_fmaxf(s_c[0], s_c[1]), __builtin_fmaxf(s_c[2], s_c[3])));
 }
 
+// ---------------- stable LSD radix sort of (key, index) pairs: three passes, two launches each ----------------
+// The pairs are one or two segments that are sorted apart in the same launches: one cloud, or the target's pairs followed
+// by the queries' (the joint sort: bit 30 of a query key only says "behind every target key", which the segments do by
+// position, so every pass sorts a 10-bit digit of the 30-bit Morton key).  A workgroup owns kSortBlockItems consecutive
+// pairs of one segment, a wave 256 of them, 64 per round.  k_sort_hist counts the workgroup's digits into
+// hist[workgroup][digit]; k_sort_scatter ranks every pair among the equal digits ahead of it in its workgroup (wave rounds
+// in order, lanes in order: stable), sums the table's columns over its segment for its own start per digit — all
+// workgroups ahead, all smaller digits — and writes.  No scan launch: a workgroup reads its segment's rows of 4 KB from L2
+// (C3: 64 + 32 rows).  The ranks come from one ballot per digit bit, not from contended LDS atomics, and the counts take a
+// wave whose 64 digits are equal in one add, so a cloud in one Morton cell (or all NaN: key 0) costs what a spread one does.
+#ifndef SVNICP_SORT_ITEMS
+#define SVNICP_SORT_ITEMS 4
+#endif
+constexpr int kSortThreads = 1024, kSortItems = SVNICP_SORT_ITEMS, kSortWaves = kSortThreads / kWave;   // pairs per thread (8 and 2 measured slower: DESIGN §4.1)
+constexpr int kSortBlockItems = kSortThreads * kSortItems;   // 4096 pairs
+constexpr int kSortBits = 10, kSortBins = 1 << kSortBits;    // one digit per thread
+constexpr int kSortMaxBlocks = 512;                          // 2 M pairs; the column sums grow with the square (larger sorts: rocPRIM)
+static_assert(kSortBins == kSortThreads, "k_sort_scatter: thread t owns digit t");
+
+// segment 0: pairs [0, n0) in workgroups [0, nb0); segment 1: pairs [n0, n0 + n1) in workgroups [nb0, gridDim.x)
+struct SortSegs { unsigned int n0, n1; int nb0; };
+struct SortBlock { unsigned int lo, n, first; int b0, b1; };   // the segment's pairs [lo, lo + n), its workgroups [b0, b1), this one's first pair
+__device__ __forceinline__ SortBlock sort_block(const SortSegs& s) {
+  SortBlock k;
+  const int b = (int)blockIdx.x;
+  if (b < s.nb0) { k.lo = 0u; k.n = s.n0; k.b0 = 0; k.b1 = s.nb0; }
+  else { k.lo = s.n0; k.n = s.n1; k.b0 = s.nb0; k.b1 = (int)gridDim.x; }
+  k.first = k.lo + (unsigned int)(b - k.b0) * (unsigned int)kSortBlockItems;
+  return k;
+}
+
+__device__ __forceinline__ unsigned long long digit_peers(unsigned int d, unsigned long long live) {   // live lanes whose digit equals d
+  unsigned long long m = live;
+#pragma unroll
+  for (int k = 0; k < kSortBits; ++k) {
+    const unsigned int bit = (d >> k) & 1u;
+    m &= __ballot(bit) ^ ((unsigned long long)bit - 1ull);   // the lanes that have the bit, or those that do not
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(kSortThreads) void k_sort_hist(const unsigned int* __restrict__ keys, SortSegs segs, int shift,
+                                                            unsigned int* __restrict__ hist /* [gridDim.x][kSortBins] */) {
+  __shared__ unsigned int h[kSortBins];
+  h[threadIdx.x] = 0u;
+  __syncthreads();
+  const SortBlock blk = sort_block(segs);
+  const int lane = threadIdx.x & (kWave - 1);
+  const unsigned int base = blk.first + (threadIdx.x >> 6) * (unsigned int)(kWave * kSortItems) + lane;
+  unsigned int key[kSortItems];
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const unsigned int i = base + r * kWave;
+    key[r] = i - blk.lo < blk.n ? keys[i] : 0u;
+  }
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {   // wave-uniform
+    const bool live = base + r * kWave - blk.lo < blk.n;
+    const unsigned int d = (key[r] >> shift) & (kSortBins - 1);
+    const unsigned int d0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)d);
+    if (__all(live && d == d0)) {   // 64 equal digits: one add, not 64 on one address
+      if (lane == 0) atomicAdd(&h[d0], (unsigned int)kWave);
+    } else if (live) {
+      atomicAdd(&h[d], 1u);
+    }
+  }
+  __syncthreads();
+  hist[(size_t)blockIdx.x * kSortBins + threadIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kSortThreads) void k_sort_scatter(const unsigned int* __restrict__ keys_in, const int32_t* __restrict__ vals_in,
+                                                               unsigned int* __restrict__ keys_out /* or nullptr */, int32_t* __restrict__ vals_out,
+                                                               SortSegs segs, int shift, const unsigned int* __restrict__ hist) {
+  __shared__ unsigned short cnt[kSortWaves][kSortBins];   // per wave and digit: pairs so far, then the pairs of the waves ahead
+  __shared__ unsigned int off[kSortBins];                 // where the workgroup's first pair of a digit goes, from the segment's start
+  __shared__ unsigned int wsum[kSortWaves];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  for (int w = 0; w < kSortWaves; ++w) cnt[w][tid] = 0;
+  __syncthreads();
+  const SortBlock blk = sort_block(segs);
+  // ranks inside the wave's 256 pairs; a wave touches only its own row of cnt, and its LDS operations keep their order
+  volatile unsigned short* mine = cnt[wave];
+  const unsigned int base = blk.first + wave * (unsigned int)(kWave * kSortItems) + lane;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  unsigned int key[kSortItems];
+  int32_t val[kSortItems];
+  unsigned short rank[kSortItems];
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const unsigned int i = base + r * kWave;
+    const bool live = i - blk.lo < blk.n;
+    key[r] = live ? keys_in[i] : 0u;
+    val[r] = live ? vals_in[i] : 0;
+  }
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const bool live = base + r * kWave - blk.lo < blk.n;
+    const unsigned int d = (key[r] >> shift) & (kSortBins - 1);
+    const unsigned long long m = digit_peers(d, __ballot(live));
+    const unsigned int prior = mine[d];
+    rank[r] = (unsigned short)(prior + (unsigned int)__popcll(m & lt));
+    if (live && lane == __ffsll((long long)m) - 1) mine[d] = (unsigned short)(prior + (unsigned int)__popcll(m));
+  }
+  __syncthreads();
+  // digit tid: the table's column sums over the segment's workgroups, all of them and those ahead of this one
+  unsigned int tot = 0u, pre = 0u;
+  for (int b = blk.b0; b < blk.b1; ++b) {
+    const unsigned int v = hist[(size_t)b * kSortBins + tid];
+    tot += v;
+    pre += b < (int)blockIdx.x ? v : 0u;
+  }
+  unsigned int inc = tot;   // inclusive scan over the digits: wave, then the waves' totals
+  for (int o = 1; o < kWave; o <<= 1) { const unsigned int x = __shfl_up(inc, o, kWave); if (lane >= o) inc += x; }
+  if (lane == kWave - 1) wsum[wave] = inc;
+  __syncthreads();
+  unsigned int start = inc - tot;
+  for (int w = 0; w < wave; ++w) start += wsum[w];
+  off[tid] = start + pre;
+  unsigned int run = 0u;
+  for (int w = 0; w < kSortWaves; ++w) { const unsigned int c = cnt[w][tid]; cnt[w][tid] = (unsigned short)run; run += c; }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kSortItems; ++r) {
+    const bool live = base + r * kWave - blk.lo < blk.n;
+    const unsigned int d = (key[r] >> shift) & (kSortBins - 1);
+    const unsigned int dst = off[d] + cnt[wave][d] + rank[r];
+    if (live && dst < blk.n) {   // (dst < n holds whenever the table was counted from these keys)
+      if (keys_out) keys_out[blk.lo + dst] = key[r];
+      vals_out[blk.lo + dst] = val[r];
+    }
+  }
+}
+
+size_t lsd_sort_blocks(size_t n) { return (n + kSortBlockItems - 1) / kSortBlockItems; }
+size_t lsd_sort_temp_bytes(size_t n) { return (lsd_sort_blocks(n) + 1) * kSortBins * sizeof(unsigned int); }   // two segments: one more workgroup
+bool lsd_sort_serves(size_t n0, size_t n1, size_t temp_bytes) {
+  return n0 > 0 && lsd_sort_blocks(n0) + lsd_sort_blocks(n1) <= (size_t)kSortMaxBlocks && temp_bytes >= lsd_sort_temp_bytes(n0 + n1);
+}
+
+hipError_t lsd_sort_pass(const unsigned int* keys_in, const int32_t* vals_in, unsigned int* keys_out, int32_t* vals_out, const SortSegs& segs, int nb,
+                         int shift, unsigned int* hist, hipStream_t st) {
+  hipLaunchKernelGGL(k_sort_hist, dim3(nb), dim3(kSortThreads), 0, st, keys_in, segs, shift, hist);
+  hipLaunchKernelGGL(k_sort_scatter, dim3(nb), dim3(kSortThreads), 0, st, keys_in, vals_in, keys_out, vals_out, segs, shift, (const unsigned int*)hist);
+  return hipGetLastError();
+}
+
+// vals_a[0, n0) sorted by keys_a (stable, 30 bits) into order[0, n0), and vals_a[n0, n0 + n1) into order[n0, n0 + n1); keys_a,
+// keys_b and vals_a are scratch.  Six launches whatever the keys are.
+hipError_t lsd_sort_pairs(unsigned int* keys_a, unsigned int* keys_b, int32_t* vals_a, int32_t* order, size_t n0, size_t n1, void* temp,
+                          hipStream_t st) {
+  unsigned int* hist = static_cast<unsigned int*>(temp);
+  const SortSegs segs{(unsigned int)n0, (unsigned int)n1, (int)lsd_sort_blocks(n0)};
+  const int nb = segs.nb0 + (int)lsd_sort_blocks(n1);
+  hipError_t e = lsd_sort_pass(keys_a, vals_a, keys_b, order, segs, nb, 0, hist, st);
+  if (e != hipSuccess) return e;
+  e = lsd_sort_pass(keys_b, order, keys_a, vals_a, segs, nb, kSortBits, hist, st);
+  if (e != hipSuccess) return e;
+  return lsd_sort_pass(keys_a, vals_a, nullptr, order, segs, nb, 2 * kSortBits, hist, st);
+}
+
+// the Morton sorts' one entry: n0 pairs, or n0 target pairs and n1 query pairs whose keys carry bit 30 — the chain above
+// (Tuning::sort_merge = 0, sizes it serves) or rocPRIM's radix_sort_pairs over all of them
+hipError_t sort_pairs(bool rocprim_sort, unsigned int* keys_a, unsigned int* keys_b, int32_t* vals_a, int32_t* order, size_t n0, size_t n1,
+                      void* temp, size_t temp_bytes, hipStream_t st) {
+  if (!rocprim_sort && lsd_sort_serves(n0, n1, temp_bytes)) return lsd_sort_pairs(keys_a, keys_b, vals_a, order, n0, n1, temp, st);
+  return rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, order, n0 + n1, 0, n1 ? 31 : 30, st);
+}
+
 }  // namespace
 
 size_t sort_temp_bytes(size_t n, int key_bits) {
   size_t bytes = 0;
   (void)rocprim::radix_sort_pairs(nullptr, bytes, (unsigned int*)nullptr, (unsigned int*)nullptr, (int32_t*)nullptr,
                                   (int32_t*)nullptr, n, 0, key_bits, (hipStream_t)0);
-  return bytes;
+  return bytes > lsd_sort_temp_bytes(n) ? bytes : lsd_sort_temp_bytes(n);
 }
 
 // order[0..n) = indices i0..i0+n of pts sorted along the Morton curve of `bbox`
+// (fill_ff, fill_words: words the key kernel sets to -1 on the way, or nullptr)
 hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int transform, const Pose0& pose,
                                const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
-                               int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
+                               int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, bool rocprim_sort, int32_t* fill_ff,
+                               size_t fill_words, hipStream_t st) {
+  if (n <= 0) return fill_words ? hipMemsetAsync(fill_ff, 0xff, fill_words * sizeof(int32_t), st) : hipSuccess;
   hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pts, i0, n, transform, pose, bbox,
-                     keys_a, vals_a, 0u);
+                     keys_a, vals_a, 0u, fill_ff, fill_words);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, order, (size_t)n, 0, 30, st);
+  return sort_pairs(rocprim_sort, keys_a, keys_b, vals_a, order, (size_t)n, 0, temp, temp_bytes, st);
 }
 
 // One sort for both clouds: the target's keys in [0, M), the keys of the n queries (pose · qsrc[0, n), inside the target's
@@ -237,21 +409,26 @@ hipError_t launch_morton_order(const double* pts, int64_t i0, int64_t n, int tra
 // the target and order[M, M + n) its permutation of the queries (values are row indices of their own cloud).
 hipError_t launch_morton_order_joint(const double* tgt, int64_t M, const double* qsrc, int64_t n, const Pose0& pose,
                                      const unsigned long long* bbox, unsigned int* keys_a, unsigned int* keys_b,
-                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, hipStream_t st) {
+                                     int32_t* vals_a, int32_t* order, void* temp, size_t temp_bytes, bool rocprim_sort, int32_t* fill_ff,
+                                     size_t fill_words, hipStream_t st) {
   if (M <= 0 || n <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, tgt, 0, M, 0, pose, bbox, keys_a, vals_a, 0u);
+  hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, tgt, 0, M, 0, pose, bbox, keys_a, vals_a, 0u,
+                     (int32_t*)nullptr, (size_t)0);
   hipLaunchKernelGGL(k_morton_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, qsrc, 0, n, 1, pose, bbox, keys_a + M,
-                     vals_a + M, 1u << 30);
+                     vals_a + M, 1u << 30, fill_ff, fill_words);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, order, (size_t)(M + n), 0, 31, st);
+  return sort_pairs(rocprim_sort, keys_a, keys_b, vals_a, order, (size_t)M, (size_t)n, temp, temp_bytes, st);
 }
 
-hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(bbox, 0xff, 3 * sizeof(unsigned long long), st);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(bbox + 3, 0, 3 * sizeof(unsigned long long), st);
-  if (e != hipSuccess) return e;
+// cleared: the six words already hold their start values (min: all ones, max: zero) — the launch that begins a registration wrote them
+hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, bool cleared, hipStream_t st) {
+  if (!cleared) {
+    hipError_t e = hipMemsetAsync(bbox, 0xff, 3 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(bbox + 3, 0, 3 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+  }
   int64_t nb = (n + 255) / 256;
   if (nb > 256) nb = 256;  // grid-stride; one set of atomics per workgroup (1024 workgroups: 27 us, most of it the 6 x 1024 same-address atomics)
   hipLaunchKernelGGL(k_bbox, dim3((unsigned)nb), dim3(256), 0, st, pts, n, bbox);
@@ -260,9 +437,11 @@ hipError_t launch_bbox(const double* pts, int64_t n, unsigned long long* bbox, h
 
 hipError_t launch_targets_sorted(const double* tgt, int64_t M, int64_t Mp, const int32_t* order, double* tx, double* ty,
                                  double* tz, float* txf, float* tyf, float* tzf, int32_t* torig, float* tile_box,
-                                 unsigned long long* emax_bits, float4* tile_a, float4* tile_o, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(emax_bits, 0, sizeof(unsigned long long), st);
-  if (e != hipSuccess) return e;
+                                 unsigned long long* emax_bits, bool emax_cleared, float4* tile_a, float4* tile_o, hipStream_t st) {
+  if (!emax_cleared) {
+    hipError_t e = hipMemsetAsync(emax_bits, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+  }
   const int n_tiles = (int)(Mp / 512);
   hipLaunchKernelGGL(k_targets_sorted, dim3(n_tiles), dim3(256), 0, st, tgt, M, order, tx, ty, tz, txf, tyf, tzf, torig,
                      tile_box, n_tiles, emax_bits, tile_a, tile_o);

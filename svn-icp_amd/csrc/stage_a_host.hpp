@@ -36,6 +36,9 @@ struct StageA {
   // registration_plan.hpp: joint_morton_sort — begin() has left the Morton layout to the registration's own search, which
   // sorts target and queries in one pass; any other search that comes first builds it on its own (ensure_layout)
   bool layout_pending = false;
+  // the launch that begins the registration (k_init_particles) has put bbox, emax and fail_count at their start values for
+  // the pending joint search, which then fills none of them; any search or layout build consumes the promise
+  bool start_words_set = false;
   DevBuf<double> tx, ty, tz;
   DevBuf<float> txf, tyf, tzf, tile_box;
   DevBuf<float4> tile_a, tile_o;         // Morton layout: tile-local rows in MFMA A-operand order, origin | C_t per tile (knn_prefilter = mfma)
@@ -70,6 +73,7 @@ struct StageA {
     plan = plan_for(e, rows, K);
     stage_kept = false;
     layout_pending = false;
+    start_words_set = false;
     const size_t Bq = (size_t)rows, B = (size_t)e.B, M = (size_t)e.M, Mp = (size_t)plan.Mp;
     size_t S = 0, slice_entries = 0;
     for (const int k : Ks) { S = std::max<size_t>(S, knn_pool_size(k)); slice_entries = std::max<size_t>(slice_entries, (size_t)knn_slice_count(k) * k); }
@@ -122,13 +126,15 @@ struct StageA {
   template <class Obj>
   int ensure_layout(Obj* o, const StageAEnv& e) {
     layout_pending = false;
+    start_words_set = false;
     if (held == plan.layout || plan.layout == TargetLayout::None) return SVNICP_OK;
     if (plan.layout == TargetLayout::Hashed) {
       HIPCHK(o, launch_targets_soa2(e.tgt, e.M, plan.Mp, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, emax.p, e.stream));
     } else {
-      HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, e.stream));
-      HIPCHK(o, launch_morton_order(e.tgt, 0, e.M, 0, e.pose0, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes, e.stream));
-      HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, tile_a.p, tile_o.p, e.stream));
+      HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, false, e.stream));
+      HIPCHK(o, launch_morton_order(e.tgt, 0, e.M, 0, e.pose0, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes,
+                                    e.tune.sort_merge != 0, nullptr, 0, e.stream));
+      HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, false, tile_a.p, tile_o.p, e.stream));
     }
     held = plan.layout;
     return SVNICP_OK;
@@ -196,6 +202,8 @@ struct StageA {
     const bool joint = layout_pending && whole_source && plan.kernel == KnnKernel::Tiles && b_lo == 0 && n == e.B && n > 0;
     if (layout_pending && !joint)
       if (const int rc = ensure_layout(o, e)) return rc;
+    const bool words_set = start_words_set && joint;
+    start_words_set = false;
     KnnArgs a{};
     a.src = qsrc; a.pose = pose; a.tx = tx.p; a.ty = ty.p; a.tz = tz.p; a.torig = torig.p;
     a.M = e.M; a.Mp = plan.Mp; a.b_lo = b_lo; a.b_hi = b_hi; a.K = K; a.S = knn_pool_size(K);
@@ -215,14 +223,17 @@ struct StageA {
     case KnnKernel::Tiles: {
       if (n <= 0) return SVNICP_OK;
       const int32_t* qord = qorder.p + b_lo;
+      const size_t tab_words = tiles_chunk_tab_words(plan.rows);   // all -1: written by the queries' key kernel on its way
       if (joint) {   // target and queries in one sort: order_t[0, M) is the target's permutation, order_t[M, M + n) the queries'
-        HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, e.stream));
-        HIPCHK(o, launch_morton_order_joint(e.tgt, e.M, qsrc, n, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes, e.stream));
-        HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, tile_a.p, tile_o.p, e.stream));
+        HIPCHK(o, launch_bbox(e.tgt, e.M, bbox.p, words_set, e.stream));
+        HIPCHK(o, launch_morton_order_joint(e.tgt, e.M, qsrc, n, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, order_t.p, sort_tmp.p, sort_tmp_bytes,
+                                            e.tune.sort_merge != 0, chunk_tab.p, tab_words, e.stream));
+        HIPCHK(o, launch_targets_sorted(e.tgt, e.M, plan.Mp, order_t.p, tx.p, ty.p, tz.p, txf.p, tyf.p, tzf.p, torig.p, tile_box.p, emax.p, words_set, tile_a.p, tile_o.p, e.stream));
         held = plan.layout; layout_pending = false;
         qord = order_t.p + e.M;
       } else {
-        HIPCHK(o, launch_morton_order(qsrc, b_lo, n, 1, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, qorder.p + b_lo, sort_tmp.p, sort_tmp_bytes, e.stream));
+        HIPCHK(o, launch_morton_order(qsrc, b_lo, n, 1, pose, bbox.p, keys_a.p, keys_b.p, vals_a.p, qorder.p + b_lo, sort_tmp.p, sort_tmp_bytes,
+                                      e.tune.sort_merge != 0, chunk_tab.p, tab_words, e.stream));
       }
       KnnTilesArgs k{};
       k.src = qsrc; k.pose = pose; k.qorder = qord;
@@ -243,11 +254,10 @@ struct StageA {
         if (ng <= 2 || st >= ng) st = 1;
         k.group_stride = st;
       }
-      HIPCHK(o, hipMemsetAsync(chunk_tab.p, 0xff, tiles_chunk_tab_words(plan.rows) * sizeof(int32_t), e.stream));
       k.fail_list = fail_list.p; k.fail_count = fail_count.p; k.fail_tau = fail_tau.p; k.qrec = qrec.p;
       a.qthr = fail_tau.p;
       if (e.record_trace) k.stat_n = stat_n.p;
-      HIPCHK(o, hipMemsetAsync(fail_count.p, 0, sizeof(int), e.stream));
+      if (!words_set) HIPCHK(o, hipMemsetAsync(fail_count.p, 0, sizeof(int), e.stream));
       const size_t dbg_waves = (size_t)((n + 63) / 64) * 4;   // seed kernel: four waves per 64-query group
       const bool dbg = e.tune.debug && dbg_waves <= kDbgPhaseWaves;   // larger launches are simply not instrumented
       if (dbg) {
