@@ -274,6 +274,78 @@ const int32_t *svnicp_eval_index_devptr(svnicp_ctx *ctx);   /* int32 [B]: neares
 const double *svnicp_eval_dist2_devptr(svnicp_ctx *ctx);    /* double [B]: its d2, NaN = not evaluated */
 int svnicp_get_eval_pairs(svnicp_ctx *ctx, int32_t *idxB, double *d2B);   /* host copy of the two; either may be NULL */
 
+/* ---- information matrix of a registration: the Gauss-Newton normal equations at an evaluated pose, their eigen-structure
+ * and what follows from it (an extension: the reference meant to hand a "Hessian_for_KF" to its filter, include/core/SVNICP.h:45,
+ * and left it commented out) ---------------------------------------------------------------------
+ * svnicp_eval_information(ctx, form, huber_delta, eig_floor_ratio, out): the sums on the device, then
+ * svnicp_information_solve on the host; blocking.
+ *   rows         those of the LAST svnicp_evaluate: its pose T = (R, t) (returned in out->R, out->t), its gate
+ *                (out->max_corr_dist), its per-row nearest target index and d2, and the q = R s + t it left on the device.  No
+ *                second search.
+ *   tangent      right perturbation T * Exp([v ; omega]), translation first: the solver's order (svnicp_get_trace H).  GTSAM's
+ *                Pose3 orders [omega ; v]: swap the two 3-blocks of H, b, step and cov before handing them to GTSAM.
+ *   terms        s = the source row, p = its nearest target row, e = q - p.
+ *   point form   rows: evaluate's inliers.  d = sqrt(d2), w = 1 if d <= delta else delta / d; c = R^T e;
+ *   (form 0)     H += w [[I, -hat(s)], [hat(s), |s|^2 I - s s^T]];  b += w [c ; s x c];  sum_wr2 += w d2.
+ *                H[0:3,0:3] is sum_w * I whatever the scene: this form can never show a translational degeneracy.
+ *   plane form   rows: evaluate's plane inliers (inlier, and the target's normal n != 0).  r = (n0 e0 + n1 e1) + n2 e2,
+ *   (form 1)     w = 1 if |r| <= delta else delta / |r|;  m = R^T n, j = [m ; s x m];
+ *                H += w j j^T;  b += w r j;  sum_wr2 += w r^2.
+ *                The form is the caller's choice, independent of the residual the solver ran (as evaluate's plane figures).
+ *   both         huber_delta = +inf: unweighted.  pairs = the exact count of contributing rows, sum_w = sum of w.  H is the
+ *                CLEAN normal matrix: no + 1e-6 I and no terms for rejected pairs -- not the solver's quirk-compatible H that
+ *                svnicp_get_trace returns.  Operands of rows that do not contribute are selected to zero, never multiplied:
+ *                a NaN or inf row reaches no sum.
+ *   determinism  the same context state and arguments give bit-identical structs: each workgroup owns a fixed range of rows
+ *                and every addition happens in an order that depends on B alone (no atomics).
+ *   when         SVNICP_ERR_INVALID, with the reason in svnicp_last_error, unless a svnicp_evaluate has succeeded since the
+ *                source, the target or the target normals were last set and since the last registration began
+ *                (svnicp_align_begin, so also svnicp_align and svnicp_align_async).  Also refused: an unknown form;
+ *                huber_delta not > 0 (NaN included); eig_floor_ratio outside [0, 1); a wrong struct_size; the plane form when
+ *                that evaluate had has_normals = 0.
+ *   side         none: no existing getter changes -- svnicp_get_eval_pairs and the two eval device pointers included -- and the
+ *   effects      next registration is bit for bit that of a context that never asked.
+ *   sharded      a row-sharded context returns the sums of its own rows.  H, b, pairs, sum_w and sum_wr2 ADD across ranks;
+ *                svnicp_information_solve on the added struct finishes it (every derived field of a rank's own struct
+ *                describes that rank's rows only).  No collective is run here.
+ * svnicp_information_solve(io): host only -- no context, no device.  From form, pairs, sum_wr2, eig_floor_ratio, H and b it
+ * fills rank, sigma2, eigval, eigvec, eig_t, vec_t, eig_r, vec_r, step and cov; every other field is left as it is.
+ *   eigen        cyclic Jacobi in float64 with a fixed sweep count on (H + H^T) / 2 and on its two diagonal 3x3 blocks.
+ *                Eigenvalues ascending; row i of eigvec is the unit eigenvector of eigval[i], its largest-magnitude component
+ *                positive (the lowest index decides a tie).
+ *   floor        f = eig_floor_ratio in [0, 1); 0 means 1e-12.  Jacobi's eigenvalues carry an ABSOLUTE error of about
+ *                6 u |H| (u = 2^-53, |H| the largest eigenvalue), i.e. 7e-16 |H|: a true zero comes back as +-1e-15 |H|.  The
+ *                default sits three orders above that, so rounding never counts as rank, and far below any direction a scan
+ *                does constrain (lambda_min / lambda_max of a real scene: 1e-4 .. 1e-2).
+ *   rank         the number of eigval[i] > f * eigval[5].
+ *   H+, step     H+ = sum over the `rank` largest of v v^T / lambda;  step = -H+ b (the Gauss-Newton step in the tangent
+ *                above: a stationary result has |step| near 0);  no component along a direction below the floor.
+ *   sigma2, cov  dof = dim * pairs - rank with dim = 3 (point) or 1 (plane);  sigma2 = sum_wr2 / dof if dof > 0 else 0;
+ *                cov = sigma2 * H+: the Gauss-Newton covariance of the pose AT this one pose, in the tangent above -- not
+ *                svnicp_get_cov_matrix, which is the particle spread in correction coordinates.
+ *   edge cases   a zero H gives rank 0, zero eigenvalues, step, sigma2 and cov (the eigenvectors are the unit axes) and no
+ *                NaN.  A non-finite entry of H or b (or sum_wr2), a form, floor or struct_size as above: SVNICP_ERR_INVALID. */
+#define SVNICP_INFO_POINT 0
+#define SVNICP_INFO_PLANE 1
+typedef struct svnicp_information {
+  int32_t struct_size;     /* in: sizeof(svnicp_information) */
+  int32_t form;            /* SVNICP_INFO_POINT | SVNICP_INFO_PLANE */
+  int64_t pairs;           /* contributing rows, exact */
+  int32_t rank;            /* eigenvalues above the floor */
+  int32_t reserved;
+  double huber_delta, eig_floor_ratio;   /* as passed */
+  double max_corr_dist;    /* the gate of the evaluate the rows came from */
+  double sum_w, sum_wr2;   /* sum of the weights; of w d2 (point) or w r^2 (plane) */
+  double sigma2;           /* sum_wr2 / dof, 0 when dof <= 0 */
+  double H[36], b[6];      /* row-major, order [v ; omega] */
+  double eigval[6], eigvec[36];   /* ascending; row i = unit eigenvector i */
+  double eig_t[3], vec_t[9], eig_r[3], vec_r[9];   /* of the blocks H[0:3,0:3] and H[3:6,3:6] */
+  double step[6], cov[36]; /* -H+ b; sigma2 * H+ */
+  double R[9], t[3];       /* the evaluated pose (row-major) */
+} svnicp_information;
+int svnicp_eval_information(svnicp_ctx *ctx, int form, double huber_delta, double eig_floor_ratio, svnicp_information *out);
+int svnicp_information_solve(svnicp_information *io);   /* host only: no context, no device */
+
 /* ---- score and weight the particles (an extension: the reference declares ParticleWeightOpt::use_weight_mean,
  * include/core/SVNICP.h:25-27, and writes its getters for arbitrary weights, SVNICP.cpp:286-308, but particle_weight_ never
  * becomes anything but ones / P) --------------------------------------------------------------------

@@ -39,6 +39,19 @@ class EvalStruct(C.Structure):
                 ("t", C.c_double * 3)]
 
 
+class InformationStruct(C.Structure):
+    """struct svnicp_information (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("form", C.c_int32), ("pairs", C.c_int64), ("rank", C.c_int32), ("reserved", C.c_int32),
+                ("huber_delta", C.c_double), ("eig_floor_ratio", C.c_double), ("max_corr_dist", C.c_double), ("sum_w", C.c_double),
+                ("sum_wr2", C.c_double), ("sigma2", C.c_double), ("H", C.c_double * 36), ("b", C.c_double * 6),
+                ("eigval", C.c_double * 6), ("eigvec", C.c_double * 36), ("eig_t", C.c_double * 3), ("vec_t", C.c_double * 9),
+                ("eig_r", C.c_double * 3), ("vec_r", C.c_double * 9), ("step", C.c_double * 6), ("cov", C.c_double * 36),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+INFO_POINT, INFO_PLANE = 0, 1   # SVNICP_INFO_POINT, SVNICP_INFO_PLANE
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -179,6 +192,8 @@ def load_library():
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = vp
     L.svnicp_get_eval_pairs.argtypes = [vp, ip, dp]
+    L.svnicp_eval_information.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(InformationStruct)]
+    L.svnicp_information_solve.argtypes = [C.POINTER(InformationStruct)]
     L.svnicp_score_particles.argtypes = [vp, C.c_double, dp, dp]
     L.svnicp_set_particle_weighting.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     L.svnicp_get_particle_scores.argtypes = [vp, dp, dp]

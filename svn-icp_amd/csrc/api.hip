@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device_buffer.hpp"
+#include "information_solve.hpp"
 #include "kernels.hpp"
 #include "stage_a_host.hpp"
 #include "stage_b_host.hpp"
@@ -108,6 +109,17 @@ struct EvalState {
   PinnedBuf<double> h_result;              // pinned [kEvalResult]
   bool have = false;                       // idx / d2 hold the rows of an evaluation of `rows` source rows
   int64_t rows = 0;
+  // svnicp_eval_information (csrc/information.hip) reads the rows of the last evaluate: `have` is never
+  // cleared (svnicp_get_eval_pairs keeps answering), `fresh` is — by the source, target and normals setters and by
+  // svnicp_align_begin — and holds again once an evaluate has succeeded
+  bool fresh = false;
+  const char* stale = "no svnicp_evaluate yet";   // why not, for the refusal
+  void mark_stale(const char* why) { fresh = false; if (have) stale = why; }
+  bool normals = false;                    // that evaluate's has_normals
+  double max_corr_dist = 0.0;              // its gate
+  EvalPose T{};                            // its pose
+  DevBuf<double> info_partial, info_result;   // [evaluate_blocks(B)][record of the form], [kInfoResult]
+  PinnedBuf<double> h_info;                // pinned [kInfoResult]
 };
 
 // svnicp_score_particles / svnicp_set_particle_weighting (csrc/particle_score.hip): its own buffers
@@ -328,6 +340,7 @@ int svnicp_set_source(svnicp_ctx* c, const double* src, int64_t B, int mem_kind)
   if (const int rc = upload_cloud(c, c->cloud.src, src, B, mem_kind)) return rc;
   c->B = B;
   c->cloud.src_set = true;
+  c->ev.mark_stale("the source changed since the last svnicp_evaluate");
   return SVNICP_OK;
 }
 
@@ -340,6 +353,7 @@ int svnicp_set_target(svnicp_ctx* c, const double* tgt, int64_t M, int mem_kind)
   c->sa.held = TargetLayout::None;  // the SoA copies are (re)built in svnicp_align_begin, once K is final
   c->cloud.tgt_set = true;
   c->pl.supplied = false; c->pl.estimated = false;   // normals belong to the target they were given or estimated for
+  c->ev.mark_stale("the target changed since the last svnicp_evaluate");
   return SVNICP_OK;
 }
 
@@ -513,6 +527,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   const bool stage_a_k1 = StageA::plan_for(stage_a_env(c), r.Bq, c->K).can_search(1);
   if (const char* why = full_corr_refusal(f, c->tune, shape.f32, stage_a_k1)) return fail(c, SVNICP_ERR_INVALID, why);
   c->pl.on = plane;
+  c->ev.mark_stale("a registration began after the last svnicp_evaluate");   // svnicp_eval_information wants one afterwards
   c->sc.on = f.weighting != 0; c->sc.reg_refusal = scoring_refusal(f, c->tune);
   c->mb.on = r.mb; c->mb.have = false; c->mb.check = false;
   c->mb.rows = r.mb ? r.Bt : 0;
@@ -1242,6 +1257,7 @@ int svnicp_set_target_normals(svnicp_ctx* c, const double* n_xyz, int64_t M, int
   HIPCHK(c, launch_pack_normals(c->cloud.tgt.p, c->pl.nsup.p, M, c->pl.rec.p, c->stream));
   if (mem_kind != SVNICP_MEM_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may reuse its host buffer
   c->pl.supplied = true; c->pl.estimated = false;
+  c->ev.mark_stale("the target normals changed since the last svnicp_evaluate");
   return SVNICP_OK;
 }
 
@@ -1314,7 +1330,7 @@ int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_
   }
   const int64_t B = c->B, M = c->M, nblk = evaluate_blocks(B);
   EvalState& ev = c->ev;
-  ev.have = false;
+  ev.have = false; ev.fresh = false; ev.stale = "the last svnicp_evaluate did not finish";
   HIPCHK(c, ev.q.ensure((size_t)B * 3)); HIPCHK(c, ev.idx.ensure((size_t)B)); HIPCHK(c, ev.d2.ensure((size_t)B));
   HIPCHK(c, ev.partial.ensure((size_t)nblk * kEvalRecord)); HIPCHK(c, ev.result.ensure(kEvalResult));
   if (!ev.h_result.p) HIPCHK(c, ev.h_result.alloc(kEvalResult));
@@ -1339,6 +1355,7 @@ int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_
   out->sum_d2 = r[3]; out->sum_r2 = r[4]; out->fitness = r[5]; out->inlier_rmse = r[6]; out->plane_rmse = r[7];
   std::memcpy(out->R, T.R, sizeof T.R); std::memcpy(out->t, T.t, sizeof T.t);
   ev.have = true; ev.rows = B;
+  ev.fresh = true; ev.normals = normals; ev.max_corr_dist = max_corr_dist; ev.T = T;
   return SVNICP_OK;
 }
 
@@ -1352,6 +1369,45 @@ int svnicp_get_eval_pairs(svnicp_ctx* c, int32_t* idxB, double* d2B) {
     if (const int rc = fetch(c, idxB, c->ev.idx.p, (size_t)c->ev.rows * 4)) return rc;
   if (d2B)
     if (const int rc = fetch(c, d2B, c->ev.d2.p, (size_t)c->ev.rows * 8)) return rc;
+  return SVNICP_OK;
+}
+
+// ---- information matrix of a registration ----
+int svnicp_information_solve(svnicp_information* io) { return svnicp_info::solve(io, nullptr); }
+
+int svnicp_eval_information(svnicp_ctx* c, int form, double huber_delta, double eig_floor_ratio, svnicp_information* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: null result struct");
+  if (out->struct_size != (int32_t)sizeof(svnicp_information)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: svnicp_information.struct_size mismatch");
+  if (form != SVNICP_INFO_POINT && form != SVNICP_INFO_PLANE) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: unknown form (SVNICP_INFO_POINT or SVNICP_INFO_PLANE)");
+  if (!(huber_delta > 0.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: huber_delta must be positive and not NaN (+inf: unweighted)");
+  if (!(eig_floor_ratio >= 0.0 && eig_floor_ratio < 1.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: eig_floor_ratio must lie in [0, 1) (0: the default, 1e-12)");
+  EvalState& ev = c->ev;
+  if (!ev.fresh || !ev.have || ev.rows != c->B)
+    return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_eval_information: ") + ev.stale + ": call svnicp_evaluate first (the sums run over its rows; it "
+                                       "must have succeeded since the source, the target or the target normals last changed and since the last registration began)");
+  if (form == SVNICP_INFO_PLANE && !ev.normals)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: the plane form needs target normals, and the last svnicp_evaluate had has_normals = 0");
+  if (bind(c)) return SVNICP_ERR_HIP;
+  const int64_t B = c->B, nblk = evaluate_blocks(B);
+  HIPCHK(c, ev.info_partial.ensure((size_t)nblk * kInfoPlaneRecord)); HIPCHK(c, ev.info_result.ensure(kInfoResult));
+  if (!ev.h_info.p) HIPCHK(c, ev.h_info.alloc(kInfoResult));
+  InfoArgs a{};
+  a.src = c->cloud.src.p; a.q = ev.q.p; a.tgt = c->cloud.tgt.p; a.rec = ev.normals ? c->pl.rec.p : nullptr; a.idx = ev.idx.p; a.d2 = ev.d2.p;
+  a.B = B; a.M = c->M; a.thr2 = ev.max_corr_dist * ev.max_corr_dist; a.delta = huber_delta; a.T = ev.T; a.partial = ev.info_partial.p;
+  HIPCHK(c, launch_information(form, a, ev.info_result.p, c->stream));
+  HIPCHK(c, hipMemcpyAsync(ev.h_info.p, ev.info_result.p, kInfoResult * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double* r = ev.h_info.p;
+  svnicp_information o{};
+  o.struct_size = (int32_t)sizeof o; o.form = form;
+  o.huber_delta = huber_delta; o.eig_floor_ratio = eig_floor_ratio; o.max_corr_dist = ev.max_corr_dist;
+  std::memcpy(o.H, r, sizeof o.H); std::memcpy(o.b, r + 36, sizeof o.b);
+  o.pairs = (int64_t)r[42]; o.sum_w = r[43]; o.sum_wr2 = r[44];
+  std::memcpy(o.R, ev.T.R, sizeof o.R); std::memcpy(o.t, ev.T.t, sizeof o.t);
+  const char* why = nullptr;
+  if (const int rc = svnicp_info::solve(&o, &why)) return fail(c, rc, std::string("svnicp_eval_information: ") + (why ? why : "svnicp_information_solve failed"));
+  *out = o;
   return SVNICP_OK;
 }
 

@@ -288,6 +288,25 @@ int64_t evaluate_blocks(int64_t B);
 hipError_t launch_evaluate_transform(const double* src, int64_t B, const EvalPose& T, double* q, hipStream_t st);
 // k_evaluate_pairs + k_evaluate_finalize: result[kEvalResult] in device memory
 hipError_t launch_evaluate_pairs(const EvalArgs& a, double* result, hipStream_t st);
+// ---------------- information matrix of a registration (information.hip) ----------------
+constexpr int kInfoPointRecord = 18;   // per workgroup: pairs, sum w, sum w d2 | sum w s (3) | sum w s s^T (6) | sum w c (3) | sum w s x c (3)
+constexpr int kInfoPlaneRecord = 30;   // per workgroup: pairs, sum w, sum w r^2 | sum w j j^T upper triangle (21) | sum w r j (6)
+constexpr int kInfoResult = 45;        // H[36] row-major | b[6] | pairs, sum w, sum w r^2
+struct InfoArgs {
+  const double* src;    // [B][3] source cloud as given
+  const double* q;      // [B][3] the last evaluate's transformed source
+  const double* tgt;    // [M][3]
+  const double* rec;    // [M][6] target xyz | unit normal when that evaluate had normals, else nullptr (the plane form needs it)
+  const int32_t* idx;   // [B] that evaluate's nearest target row, -1 = not evaluated
+  const double* d2;     // [B] its d2, NaN = not evaluated
+  int64_t B, M;
+  double thr2;          // that evaluate's max_corr_dist^2
+  double delta;         // Huber delta, +inf = unweighted
+  EvalPose T;           // that evaluate's pose
+  double* partial;      // [evaluate_blocks(B)][record of the form]
+};
+// form 0 = point, 1 = plane (SVNICP_INFO_*).  k_information_pairs + k_information_finalize: result[kInfoResult] in device memory
+hipError_t launch_information(int form, const InfoArgs& a, double* result, hipStream_t st);
 // ---------------- score and weight the particles (particle_score.hip) ----------------
 constexpr int kScoreRecord = 5;        // per (workgroup, particle): evaluated, inliers, plane inliers (exact counts), sum d2, sum r2
 constexpr int kScoreFields = 6;        // per particle: the record's five totals | cost  (SVNICP_SCORE_FIELDS)

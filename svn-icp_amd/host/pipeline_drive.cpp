@@ -2,12 +2,14 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist]
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist] [information off|point|plane]
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
 //      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
 //      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2;
 //      eval_dist > 0: PipelineConfig::eval_dist, every registered scan is evaluated and one more line per scan is printed:
-//      "eval <scan>: fitness inlier_rmse plane_rmse plane_inliers" with %.17g, -1 where a figure does not exist)
+//      "eval <scan>: fitness inlier_rmse plane_rmse plane_inliers" with %.17g, -1 where a figure does not exist;
+//      information point|plane: PipelineConfig::information (needs eval_dist > 0), one more line per registered scan:
+//      "info <scan>: pairs rank eigval[0] ... eigval[5]" with %.17g)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -39,6 +41,7 @@ int main(int argc, char** argv) {
   cfg.segmentation = argc > 10 && atoi(argv[10]) != 0;
   cfg.plane = cfg.map_normals = argc > 11 && atoi(argv[11]) != 0;
   cfg.eval_dist = argc > 12 ? atof(argv[12]) : 0.0;
+  if (argc > 13) cfg.information = argv[13];
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;
@@ -75,6 +78,11 @@ int main(int argc, char** argv) {
              (long long)M, pipe.map_voxels(), pipe.bytes_h2d(), r.pose.t[0], r.pose.t[1], r.pose.t[2]);
       if (cfg.eval_dist > 0)
         printf("eval %d: %.17g %.17g %.17g %lld\n", s, r.fitness, r.inlier_rmse, r.plane_rmse, (long long)r.plane_inliers);
+      if (r.information) {
+        const svnicp_information& in = *r.information;
+        printf("info %d: %lld %d %.17g %.17g %.17g %.17g %.17g %.17g\n", s, (long long)in.pairs, (int)in.rank, in.eigval[0], in.eigval[1],
+               in.eigval[2], in.eigval[3], in.eigval[4], in.eigval[5]);
+      }
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "svnicp: %s\n", e.what());

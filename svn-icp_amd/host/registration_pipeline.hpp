@@ -26,7 +26,9 @@
 #include <map>
 #include <memory>
 #include <numeric>
+#include <optional>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "svnicp_hip_shim.hpp"
@@ -587,6 +589,9 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
                                // (DeviceVoxelMap::QueryNormals) instead of the solver's pass over the target
   double eval_dist = 0.0;      // > 0: every registered scan is evaluated at its result pose with this inlier gate
                                // (svnicp_evaluate) before the map update; 0 = off, no call is made
+  std::string information = "off";   // "point" | "plane": after that evaluate, the Gauss-Newton information matrix of its pairs
+                                     // (svnicp_eval_information) in ScanResult::information; needs eval_dist > 0.  "off": no call
+  double info_huber = HUGE_VAL;      // with information: its Huber delta (+inf = unweighted)
   double weight_dist = 0.0;    // > 0: every registration ends with one scoring of the particles at this gate and soft-min weights
                                // (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures
   double weight_temperature = 0.0;   // with weight_dist: the soft-min temperature in m^2, > 0
@@ -603,6 +608,7 @@ struct ScanResult {
   // cfg.eval_dist > 0: the result pose against the whole target (svnicp_evaluate); -1 = off, plane figures -1 without normals
   double fitness = -1, inlier_rmse = -1, plane_rmse = -1;
   int64_t plane_inliers = -1;
+  std::optional<svnicp_information> information;   // cfg.information != "off": H, b, eigen-structure, rank, step, cov at the result pose
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -621,6 +627,10 @@ class RegistrationPipeline {
     if (!(std::isfinite(cfg.weight_dist) && cfg.weight_dist >= 0)) throw std::invalid_argument("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)");
     if (cfg.weight_dist > 0 && !(std::isfinite(cfg.weight_temperature) && cfg.weight_temperature > 0))
       throw std::invalid_argument("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)");
+    if (cfg.information != "off" && cfg.information != "point" && cfg.information != "plane")
+      throw std::invalid_argument("PipelineConfig: information must be \"off\", \"point\" or \"plane\"");
+    if (cfg.information != "off" && !(cfg.eval_dist > 0)) throw std::invalid_argument("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)");
+    if (cfg.information != "off" && !(cfg.info_huber > 0)) throw std::invalid_argument("PipelineConfig: info_huber must be > 0 (+inf = unweighted)");
     if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
     if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
     if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
@@ -727,6 +737,8 @@ class RegistrationPipeline {
       const svnicp_eval ev = solver_->evaluate(cfg_.eval_dist, res.pose.R.data(), res.pose.t.data());
       res.fitness = ev.fitness; res.inlier_rmse = ev.inlier_rmse;
       if (ev.has_normals) { res.plane_rmse = ev.plane_rmse; res.plane_inliers = ev.plane_inliers; }
+      if (cfg_.information != "off")   // what a filter or a gate may read; no policy here either
+        res.information = solver_->information(cfg_.information == "plane" ? SVNICP_INFO_PLANE : SVNICP_INFO_POINT, cfg_.info_huber);
     }
     // … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is updated
     // with the same points the solver registered

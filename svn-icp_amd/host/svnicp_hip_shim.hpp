@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "svnicp_hip.h"
+#include "../csrc/information_solve.hpp"
 
 namespace svnicp {
 
@@ -147,6 +148,22 @@ class SVGDICP {
     if (idx) idx->assign((size_t)B, -1);
     if (d2) d2->assign((size_t)B, 0.0);
     chk(svnicp_get_eval_pairs(h_, idx ? idx->data() : nullptr, d2 ? d2->data() : nullptr));
+  }
+  // information matrix of a registration (svnicp_hip.h): the Gauss-Newton normal equations H, b over the pairs of the last
+  // evaluate, tangent T * Exp([v ; omega]), with their eigen-structure, rank, step -H+ b and covariance; form = SVNICP_INFO_POINT
+  // or SVNICP_INFO_PLANE, independent of the residual the solver ran; huber_delta = +inf: unweighted
+  svnicp_information information(int form = SVNICP_INFO_PLANE, double huber_delta = HUGE_VAL, double eig_floor_ratio = 0.0) {
+    svnicp_information o{};
+    o.struct_size = (int32_t)sizeof o;
+    chk(svnicp_eval_information(h_, form, huber_delta, eig_floor_ratio, &o));
+    return o;
+  }
+  // svnicp_information_solve without the library: every derived field from io.form, pairs, sum_wr2, eig_floor_ratio, H and b
+  // (for instance the sums of several row-sharded contexts added up)
+  static void information_solve(svnicp_information& io) {
+    const char* why = nullptr;
+    io.struct_size = (int32_t)sizeof io;
+    if (svnicp_info::solve(&io, &why) != 0) throw std::runtime_error(std::string("svnicp_information_solve: ") + (why ? why : "invalid input"));
   }
   // score and weight the particles (svnicp_hip.h): [P][SVNICP_SCORE_FIELDS] {evaluated, inliers, plane inliers, sum d2, sum r2,
   // cost} of every particle's final pose through the registration's candidate table; poses: [P][12] (R row-major, t), optional

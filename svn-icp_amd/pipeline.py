@@ -899,6 +899,8 @@ class PipelineConfig:
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
     eval_dist: float = 0.0         # > 0: every registered scan is evaluated at its result pose with this inlier gate (svnicp_evaluate) before the map update; 0 = off, no call is made
+    information: str = "off"       # "point" | "plane": after that evaluate, the Gauss-Newton information matrix of its pairs (svnicp_eval_information) in ScanResult.information; needs eval_dist > 0.  "off": no call is made
+    info_huber: float = float("inf")   # with information: its Huber delta (+inf = unweighted)
     weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
     weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
     map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
@@ -908,6 +910,12 @@ class PipelineConfig:
             raise ValueError("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)")
         if self.weight_dist > 0 and not (np.isfinite(self.weight_temperature) and self.weight_temperature > 0):
             raise ValueError("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)")
+        if self.information not in ("off", "point", "plane"):
+            raise ValueError('PipelineConfig: information must be "off", "point" or "plane"')
+        if self.information != "off" and not self.eval_dist > 0:
+            raise ValueError("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)")
+        if self.information != "off" and not self.info_huber > 0:
+            raise ValueError("PipelineConfig: info_huber must be > 0 (+inf = unweighted)")
         if self.map_normals and not self.gpu_map:
             raise ValueError("PipelineConfig: map_normals needs gpu_map=True (the normals are computed from the device map)")
         if self.map_normals and self.solver.residual != "plane":
@@ -932,6 +940,7 @@ class ScanResult:
     inlier_rmse: float | None = None         # … sqrt(mean d2) over the inliers
     plane_rmse: float | None = None          # … sqrt(mean r2) over the inliers whose target has a normal; None without normals
     plane_inliers: int | None = None
+    information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
 
 
 class RegistrationPipeline:
@@ -1040,6 +1049,8 @@ class RegistrationPipeline:
             res.fitness, res.inlier_rmse = ev.fitness, ev.inlier_rmse
             if ev.has_normals:
                 res.plane_rmse, res.plane_inliers = ev.plane_rmse, ev.plane_inliers
+            if c.information != "off":   # what a filter or a gate may read; no policy here either
+                res.information = s.information(c.information, c.info_huber)
         # … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is
         # updated with the same points the solver registered
         if dev:

@@ -98,6 +98,66 @@ class RegistrationEval:
     pose: np.ndarray           # 4x4, the pose that was evaluated (map <- sensor)
 
 
+@dataclass
+class RegistrationInformation:
+    """struct svnicp_information (include/svnicp_hip.h, "information matrix of a registration"): the Gauss-Newton normal
+    equations of the last ``evaluate``'s pairs, tangent T * Exp([v ; omega]) (translation first), and their eigen-structure."""
+    form: str                  # "point" | "plane"
+    pairs: int                 # contributing rows
+    rank: int                  # eigenvalues above eig_floor_ratio * the largest
+    huber_delta: float
+    eig_floor_ratio: float
+    max_corr_dist: float       # the gate of the evaluate the rows came from
+    sum_w: float
+    sum_wr2: float             # sum of w d2 (point) or w r^2 (plane)
+    sigma2: float              # sum_wr2 / (dim * pairs - rank), 0 when that is not positive
+    H: np.ndarray              # [6, 6]
+    b: np.ndarray              # [6]
+    eigval: np.ndarray         # [6] ascending
+    eigvec: np.ndarray         # [6, 6], row i = unit eigenvector i
+    eig_t: np.ndarray          # [3], of H[0:3, 0:3]
+    vec_t: np.ndarray          # [3, 3]
+    eig_r: np.ndarray          # [3], of H[3:6, 3:6]
+    vec_r: np.ndarray          # [3, 3]
+    step: np.ndarray           # [6] -H+ b
+    cov: np.ndarray            # [6, 6] sigma2 * H+
+    pose: np.ndarray           # 4x4, the evaluated pose
+
+
+_INFO_FORMS = {"point": binding.INFO_POINT, "plane": binding.INFO_PLANE}
+
+
+def _information_from_struct(o) -> RegistrationInformation:
+    arr = lambda name, *shape: np.array(getattr(o, name)[:], np.float64).reshape(shape)   # noqa: E731
+    T = np.eye(4)
+    T[:3, :3] = arr("R", 3, 3)
+    T[:3, 3] = arr("t", 3)
+    return RegistrationInformation("plane" if o.form == binding.INFO_PLANE else "point", int(o.pairs), int(o.rank), float(o.huber_delta),
+                                   float(o.eig_floor_ratio), float(o.max_corr_dist), float(o.sum_w), float(o.sum_wr2), float(o.sigma2),
+                                   arr("H", 6, 6), arr("b", 6), arr("eigval", 6), arr("eigvec", 6, 6), arr("eig_t", 3), arr("vec_t", 3, 3),
+                                   arr("eig_r", 3), arr("vec_r", 3, 3), arr("step", 6), arr("cov", 6, 6), T)
+
+
+def information_solve(form, pairs: int, sum_wr2: float, H, b, eig_floor_ratio: float = 0.0, sum_w: float = 0.0,
+                      huber_delta: float = float("inf"), max_corr_dist: float = 0.0, pose=None) -> RegistrationInformation:
+    """svnicp_information_solve (host only, no device): rank, eigen-structure, step, sigma2 and cov of the normal equations
+    ``H`` [6, 6], ``b`` [6] — for instance the sums of several row-sharded contexts added up."""
+    o = binding.InformationStruct()
+    o.struct_size = C.sizeof(binding.InformationStruct)
+    o.form = int(_INFO_FORMS.get(form, form))
+    o.pairs, o.sum_wr2, o.eig_floor_ratio = int(pairs), float(sum_wr2), float(eig_floor_ratio)
+    o.sum_w, o.huber_delta, o.max_corr_dist = float(sum_w), float(huber_delta), float(max_corr_dist)
+    o.H[:] = np.asarray(H, np.float64).reshape(36).tolist()
+    o.b[:] = np.asarray(b, np.float64).reshape(6).tolist()
+    T = np.eye(4) if pose is None else np.asarray(pose, np.float64).reshape(4, 4)
+    o.R[:] = T[:3, :3].reshape(9).tolist()
+    o.t[:] = T[:3, 3].tolist()
+    if binding.load_library().svnicp_information_solve(C.byref(o)) != 0:
+        raise binding.SvnIcpError("svnicp_information_solve: invalid input (form, eig_floor_ratio outside [0, 1), negative pairs, "
+                                  "or a non-finite entry of H, b or sum_wr2)")
+    return _information_from_struct(o)
+
+
 def initialize_particles(particle_count: int, ub, lb, rng: np.random.Generator | None = None) -> np.ndarray:
     """svnicp::initialize_particles (src/core/ICPUtils.cpp:45-58): uniform in [lb, ub] per row,
     zeros for a single particle.  Returns [6, P] float64."""
@@ -415,6 +475,16 @@ class _SolverBase:
         T[:3, 3] = e.t[:]
         return RegistrationEval(bool(e.has_normals), int(e.rows), int(e.evaluated), int(e.inliers), int(e.plane_inliers),
                                 float(e.sum_d2), float(e.sum_r2), float(e.fitness), float(e.inlier_rmse), float(e.plane_rmse), T)
+
+    def information(self, form="plane", huber_delta: float = float("inf"), eig_floor_ratio: float = 0.0) -> RegistrationInformation:
+        """The Gauss-Newton information matrix H, gradient b, their eigen-structure, rank, step -H+ b and covariance over the
+        pairs of the last ``evaluate`` (include/svnicp_hip.h "information matrix of a registration"); ``form`` "point" or
+        "plane" is independent of the residual the solver ran."""
+        o = binding.InformationStruct()
+        o.struct_size = C.sizeof(binding.InformationStruct)
+        self._check(self._L.svnicp_eval_information(self._h, int(_INFO_FORMS.get(form, form)), float(huber_delta), float(eig_floor_ratio),
+                                                    C.byref(o)), "svnicp_eval_information")
+        return _information_from_struct(o)
 
     def get_eval_pairs(self) -> tuple:
         """Per source row of the last ``evaluate``: (nearest target row, int32 [B], -1 = not evaluated; its d2, float64 [B],
