@@ -401,6 +401,81 @@ int svnicp_score_particles(svnicp_ctx *ctx, double max_corr_dist, double *outPx6
 int svnicp_set_particle_weighting(svnicp_ctx *ctx, int kind, double max_corr_dist, double temperature);
 int svnicp_get_particle_scores(svnicp_ctx *ctx, double *outPx6, double *posesPx12);  /* of the last scoring, whoever ran it */
 
+/* ---- particle modes: the particle set clustered on the device (an extension: the reference publishes particles and weights
+ * and stops there; every getter above collapses the set into one mean, which lies between the peaks of a posterior that has
+ * more than one) -----------------------------------------------------------------------------------
+ * svnicp_particle_modes(ctx, opt, out): blocking; one kernel launch, one copy of about 16 KB.
+ *   input        the particle 6-vectors x_p = (t, omega) that svnicp_get_particles returns (the device's [6][P] block) with the
+ *                weights svnicp_get_particle_weight returns (uniform, or soft-min when weighting is on); or, with
+ *                opt->particles6xP, a caller's host [6][P] block with opt->weightsP (NULL: every weight is 1.0).
+ *   link         p and q are linked iff dt2 <= link_trans * link_trans AND dr2 <= link_rot * link_rot, both squares computed
+ *                once, with d = x_p - x_q per component, dt2 = ((d0*d0) + d1*d1) + d2*d2 and dr2 = ((d3*d3) + d4*d4) + d5*d5:
+ *                float64, unfused.  dr2 is on the COMPONENT DIFFERENCES of the rotation vectors, not a geodesic angle: the
+ *                particles are small corrections about the initial mean, where the two agree to second order.  A particle with
+ *                a non-finite component links to nothing, belongs to no mode and is counted in `nonfinite`.
+ *   modes        the connected components of the link graph over the finite particles; a mode's label is its lowest particle
+ *                index.  (Device: each particle takes the lowest label among its links, pointers are jumped, and the sweep is
+ *                repeated until nothing changes; the pair distances are recomputed every sweep.  The result does not depend on
+ *                the schedule.)
+ *   per mode     count;  W = sum of the members' weights;  mass = W / W_all, W_all the same sum over all finite particles;
+ *                mean_i = (sum w_p * x_ip) / W;  cov_rc = (sum w_p * ((x_rp - mean_r) * (x_cp - mean_c))) / W.  Every sum runs
+ *                over the members in ascending particle order from 0.0, in float64, unfused; no atomics.  The division by W
+ *                is deliberate: the global getters above do not normalise (the reference's float32(1 / P) * P != 1 shows in
+ *                them); a mode's statistics do not depend on the scale of the weights.  A mode of zero weight has NaN
+ *                statistics (0 / 0).
+ *   order        descending W, ties to the lower label.  n_modes counts all modes; the first n_reported = min(n_modes,
+ *                max_modes) are reported in full, the arrays beyond are zero (best: -1).
+ *   total pose   R, t of a mode: T0 * Pose3(Rot3::Expmap(mean[3:6]), mean[0:3]) -- the composition svnicp_evaluate(ctx, NULL,
+ *                NULL, ...) applies to the global mean (the same function), row-major, map <- sensor; hand it to
+ *                svnicp_evaluate to judge a mode instead of the mean.
+ *   scores       has_scores = 1 iff the context holds a scoring of exactly the particles that were clustered: the set of the
+ *                last registration, scored by svnicp_score_particles or by a weighted registration since that registration began
+ *                and since svnicp_set_particles.  Then per mode: best = the member with the lowest cost (strict '<' in particle
+ *                order: ties to the lowest index), cost_min its cost, cost_mean = (sum of the members' costs in particle
+ *                order) / count, unweighted.  Otherwise (always for a caller's set) best = -1 and the costs are 0.
+ *   when         with opt->particles6xP == NULL: after a finished registration of any kind -- SVN or SVGD mode, plane residual,
+ *                mini-batch, particle shards and row shards (the Stein step is replicated: every rank holds all P poses),
+ *                correspondence=full; otherwise SVNICP_ERR_INVALID.  A caller's set needs no registration, no clouds and no
+ *                svnicp_set_particles (clustering an earlier iteration out of svnicp_get_particle_history is the use).
+ *                Synchronises first.
+ *   refused      SVNICP_ERR_INVALID with the reason in svnicp_last_error: a struct_size mismatch of either struct; max_modes
+ *                outside 1..SVNICP_MODES_MAX; a link that is negative or not finite; P < 1 with a caller's set; weightsP without
+ *                particles6xP; a supplied weight that is negative or not finite; more than 2048 particles (one workgroup
+ *                stages the set in LDS; there is no global-memory fallback).
+ *   determinism  the same particles, weights and options give bit-identical structs and labels on every call.
+ *   side         none: every existing getter returns what it returned before, and the next registration is bit for bit that
+ *   effects      of a context that never asked.  The kernel ignores the stop flag.
+ * svnicp_get_mode_labels(ctx, outP): per particle of the last svnicp_particle_modes the rank of its mode in the order above
+ * (0 = the heaviest; ranks beyond n_reported included), -1 for a non-finite particle.  outP holds that call's `particles`
+ * entries.  SVNICP_ERR_INVALID before the first successful call. */
+#define SVNICP_MODES_MAX 32
+typedef struct svnicp_modes_opt {
+  int32_t struct_size;          /* = sizeof(svnicp_modes_opt) */
+  int32_t max_modes;            /* 1..SVNICP_MODES_MAX */
+  double link_trans, link_rot;  /* metres, radians; finite, >= 0 */
+  const double *particles6xP;   /* host [6][P]; NULL: the last registration's set */
+  int32_t P;                    /* with particles6xP only */
+  int32_t reserved;
+  const double *weightsP;       /* host [P], with particles6xP only; NULL: equal weights */
+} svnicp_modes_opt;
+typedef struct svnicp_modes {
+  int32_t struct_size;   /* in: sizeof(svnicp_modes) */
+  int32_t particles;     /* P of the set that was clustered */
+  int32_t nonfinite;     /* particles with a non-finite component: in no mode */
+  int32_t n_modes;       /* all modes */
+  int32_t n_reported;    /* min(n_modes, max_modes): the entries filled below */
+  int32_t has_scores;    /* 1: best, cost_min, cost_mean are filled */
+  int32_t label[SVNICP_MODES_MAX];   /* lowest particle index of the mode */
+  int32_t count[SVNICP_MODES_MAX];   /* members */
+  int32_t best[SVNICP_MODES_MAX];    /* member with the lowest cost, -1 without scores */
+  double mass[SVNICP_MODES_MAX];     /* W / W_all */
+  double cost_min[SVNICP_MODES_MAX], cost_mean[SVNICP_MODES_MAX];
+  double mean[SVNICP_MODES_MAX][6], cov[SVNICP_MODES_MAX][36];   /* in correction coordinates, as svnicp_get_transformation */
+  double R[SVNICP_MODES_MAX][9], t[SVNICP_MODES_MAX][3];         /* the mode's total pose, row-major */
+} svnicp_modes;
+int svnicp_particle_modes(svnicp_ctx *ctx, const svnicp_modes_opt *opt, svnicp_modes *out);
+int svnicp_get_mode_labels(svnicp_ctx *ctx, int32_t *outP);
+
 /* ---- split-phase entry points: one process per GPU, particles sharded across ranks ----------
  * (new functionality; the reference is single-GPU).  Sequence per registration:
  *   svnicp_set_shard -> svnicp_stage_candidates(b_lo,b_hi) -> [host all-gathers rows of

@@ -8,9 +8,9 @@ the compute path is libsvnicp_hip.so (hand-written HIP for gfx950) and it fails 
 library or a gfx950 device is missing — there is no CPU fallback.
 """
 from .binding import (SvnIcpError, abi_version, library_path, load_library, declared_symbols)  # noqa: F401
-from .solver import SVNICP, SVGDICP, SteinICPParam, SteinICPState, ParticleWeightOpt, initialize_particles, minibatch_indices, RegistrationEval, ParticleScores, RegistrationInformation, information_solve  # noqa: F401
+from .solver import SVNICP, SVGDICP, SteinICPParam, SteinICPState, ParticleWeightOpt, initialize_particles, minibatch_indices, RegistrationEval, ParticleScores, RegistrationInformation, information_solve, ParticleModes  # noqa: F401
 from . import scans  # noqa: F401
 from . import pipeline, stein_msgs  # noqa: F401  (caller glue and wire formats, SURVEY.md §8(f)-1,2)
 
-__all__ = ["SVNICP", "SVGDICP", "SteinICPParam", "SteinICPState", "ParticleWeightOpt", "initialize_particles", "minibatch_indices", "RegistrationEval", "ParticleScores", "RegistrationInformation", "information_solve",
+__all__ = ["SVNICP", "SVGDICP", "SteinICPParam", "SteinICPState", "ParticleWeightOpt", "initialize_particles", "minibatch_indices", "RegistrationEval", "ParticleScores", "RegistrationInformation", "information_solve", "ParticleModes",
           "SvnIcpError", "abi_version", "library_path", "load_library", "declared_symbols", "scans", "pipeline", "stein_msgs"]

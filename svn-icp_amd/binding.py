@@ -50,6 +50,22 @@ class InformationStruct(C.Structure):
 
 
 INFO_POINT, INFO_PLANE = 0, 1   # SVNICP_INFO_POINT, SVNICP_INFO_PLANE
+MODES_MAX = 32                  # SVNICP_MODES_MAX
+
+
+class ModesOptStruct(C.Structure):
+    """struct svnicp_modes_opt (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("max_modes", C.c_int32), ("link_trans", C.c_double), ("link_rot", C.c_double),
+                ("particles6xP", C.POINTER(C.c_double)), ("P", C.c_int32), ("reserved", C.c_int32), ("weightsP", C.POINTER(C.c_double))]
+
+
+class ModesStruct(C.Structure):
+    """struct svnicp_modes (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("particles", C.c_int32), ("nonfinite", C.c_int32), ("n_modes", C.c_int32),
+                ("n_reported", C.c_int32), ("has_scores", C.c_int32), ("label", C.c_int32 * MODES_MAX), ("count", C.c_int32 * MODES_MAX),
+                ("best", C.c_int32 * MODES_MAX), ("mass", C.c_double * MODES_MAX), ("cost_min", C.c_double * MODES_MAX),
+                ("cost_mean", C.c_double * MODES_MAX), ("mean", C.c_double * (6 * MODES_MAX)), ("cov", C.c_double * (36 * MODES_MAX)),
+                ("R", C.c_double * (9 * MODES_MAX)), ("t", C.c_double * (3 * MODES_MAX))]
 
 
 def library_path() -> str:
@@ -197,6 +213,8 @@ def load_library():
     L.svnicp_score_particles.argtypes = [vp, C.c_double, dp, dp]
     L.svnicp_set_particle_weighting.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     L.svnicp_get_particle_scores.argtypes = [vp, dp, dp]
+    L.svnicp_particle_modes.argtypes = [vp, C.POINTER(ModesOptStruct), C.POINTER(ModesStruct)]
+    L.svnicp_get_mode_labels.argtypes = [vp, ip]
     for name in declared_symbols():
         getattr(L, name)  # AttributeError here = the header declares a symbol the library does not export
     _lib = L

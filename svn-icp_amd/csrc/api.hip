@@ -131,6 +131,16 @@ struct ScoreState {
   DevBuf<double> partial, scores, poses, w;   // [score_blocks(B)][Ppad][kScoreRecord], [P][kScoreFields], [P][12], [P]
   bool have = false;                       // scores / poses hold a scoring of `P` particles
   int P = 0;
+  bool of_result = false;                  // … of the particles pose_out holds now: cleared by svnicp_align_begin and svnicp_set_particles
+};
+
+// svnicp_particle_modes (csrc/particle_modes.hip): its own buffers
+struct ModesState {
+  DevBuf<double> in_pose, in_w;            // a caller's set: [6][P], [P]
+  DevBuf<double> result;                   // modes_result_bytes(P)
+  PinnedBuf<double> h_in, h_result;        // pinned staging of a caller's set; of the result block and the labels behind it
+  bool have = false;                       // h_result holds the labels of a clustering of `P` particles
+  int P = 0;
 };
 
 struct Trace { DevBuf<double> H, b, N, phi, h; DevBuf<int32_t> corr; };   // record_trace
@@ -173,7 +183,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev; ScoreState sc;
+  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev; ScoreState sc; ModesState md;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -396,6 +406,7 @@ int svnicp_set_particles(svnicp_ctx* c, const double* init, int P) {
   c->st.host_stats_valid = false;
   const bool first = !c->run.particles_set || P != c->P;
   if (P != c->P) c->sc.have = false;   // the last scoring was of another particle count
+  c->sc.of_result = false;
   if (first && c->shard.row_world > 1) { c->shard.row_world = 1; c->shard.row_rank = 0; c->shard.B_total = 0; }   // the record array is sized by P: set the row shard again
   c->P = P;
   if (!c->shard.set || first) { c->shard.p_lo = 0; c->shard.p_hi = P; c->shard.set = false; }
@@ -606,6 +617,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   c->run.began = true;
   c->st.finish_seen = false;
   c->run.have_result = false;
+  c->sc.of_result = false;   // the scoring at hand is of the previous registration's particles
   return SVNICP_OK;
 }
 
@@ -884,7 +896,7 @@ static int enqueue_scoring(svnicp_ctx* c, double gate) {
   a.B = c->B; a.M = c->M; a.K = c->K; a.P = c->P; a.thr2 = gate * gate; a.partial = sc.partial.p;
   HIPCHK(c, launch_particle_score(a, sc.scores.p, c->stream));
   HIPCHK(c, hipMemcpyAsync(sc.poses.p, c->st.Rtot.p, (size_t)c->P * 12 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  sc.have = true; sc.P = c->P;
+  sc.have = true; sc.P = c->P; sc.of_result = true;
   return SVNICP_OK;
 }
 
@@ -1292,6 +1304,18 @@ static void host_so3_exp(const double w[3], double R[9]) {
   for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * K[i] + b * K2[i];
 }
 
+// T0 * Pose3(Rot3::Expmap(x[3:6]), x[0:3]): the total pose of a correction 6-vector -- the global mean (svnicp_evaluate with
+// a NULL pose) or a mode's mean (svnicp_particle_modes)
+static void correction_total_pose(const Pose0& pose0, const double x[6], EvalPose& T) {
+  double Rc[9];
+  host_so3_exp(x + 3, Rc);
+  const double* R0 = pose0.R0;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) T.R[3 * i + j] = R0[3 * i] * Rc[j] + R0[3 * i + 1] * Rc[3 + j] + R0[3 * i + 2] * Rc[6 + j];
+    T.t[i] = (R0[3 * i] * x[0] + R0[3 * i + 1] * x[1] + R0[3 * i + 2] * x[2]) + pose0.t0[i];
+  }
+}
+
 int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_corr_dist, svnicp_eval* out) {
   CTX_CHECK(c);
   if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: null result struct");
@@ -1317,14 +1341,9 @@ int svnicp_evaluate(svnicp_ctx* c, const double* R, const double* t, double max_
   if (R) {
     std::memcpy(T.R, R, sizeof T.R); std::memcpy(T.t, t, sizeof T.t);
   } else {   // T0 * Pose3(Rot3::Expmap(mean[3:6]), mean[0:3])
-    double mean[6], Rc[9];
+    double mean[6];
     if (const int rc = fetch_stats(c, mean, 0, 6)) return rc;
-    host_so3_exp(mean + 3, Rc);
-    const double* R0 = c->pose0.R0;
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) T.R[3 * i + j] = R0[3 * i] * Rc[j] + R0[3 * i + 1] * Rc[3 + j] + R0[3 * i + 2] * Rc[6 + j];
-      T.t[i] = (R0[3 * i] * mean[0] + R0[3 * i + 1] * mean[1] + R0[3 * i + 2] * mean[2]) + c->pose0.t0[i];
-    }
+    correction_total_pose(c->pose0, mean, T);
     for (int i = 0; i < 12; ++i)
       if (!std::isfinite(i < 9 ? T.R[i] : T.t[i - 9])) return fail(c, SVNICP_ERR_INVALID, "svnicp_evaluate: the last registration's result pose is not finite");
   }
@@ -1449,6 +1468,88 @@ int svnicp_set_particle_weighting(svnicp_ctx* c, int kind, double max_corr_dist,
   }
   c->sc.kind = kind;   // an unknown kind is refused by svnicp_align_begin
   c->sc.gate = max_corr_dist; c->sc.temperature = temperature;
+  return SVNICP_OK;
+}
+
+// ---- particle modes ----
+int svnicp_particle_modes(svnicp_ctx* c, const svnicp_modes_opt* opt, svnicp_modes* out) {
+  CTX_CHECK(c);
+  if (!opt || !out) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: null options or result struct");
+  if (opt->struct_size != (int32_t)sizeof(svnicp_modes_opt)) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: svnicp_modes_opt.struct_size mismatch");
+  if (out->struct_size != (int32_t)sizeof(svnicp_modes)) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: svnicp_modes.struct_size mismatch");
+  if (opt->max_modes < 1 || opt->max_modes > SVNICP_MODES_MAX) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: max_modes must lie in 1..SVNICP_MODES_MAX");
+  if (!(opt->link_trans >= 0.0) || !std::isfinite(opt->link_trans) || !(opt->link_rot >= 0.0) || !std::isfinite(opt->link_rot))
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: link_trans and link_rot must be finite and not negative");
+  const bool own = opt->particles6xP != nullptr;
+  if (!own && opt->weightsP) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: weightsP without particles6xP (the registration's set carries its own weights)");
+  if (own && opt->P < 1) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: need P >= 1");
+  if (!own && !c->run.have_result)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: no finished registration yet (pass particles6xP to cluster a set of your own)");
+  const int P = own ? opt->P : c->P;
+  if (P > kModesMaxP) return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: more than 2048 particles (one workgroup stages the set in LDS)");
+  if (own && opt->weightsP)
+    for (int p = 0; p < P; ++p)
+      if (!(opt->weightsP[p] >= 0.0) || !std::isfinite(opt->weightsP[p]))
+        return fail(c, SVNICP_ERR_INVALID, "svnicp_particle_modes: a supplied weight is negative or not finite");
+  if (const int rc = svnicp_synchronize(c)) return rc;   // an asynchronous registration has finished and its checks have run
+  ModesState& md = c->md;
+  md.have = false;
+  const size_t res_doubles = (modes_result_bytes(P) + 7) / 8;
+  HIPCHK(c, md.result.ensure(res_doubles));
+  if (md.h_result.cap < res_doubles) HIPCHK(c, md.h_result.alloc(res_doubles));
+  ModesArgs a{};
+  a.P = P; a.max_modes = opt->max_modes;
+  a.lt2 = opt->link_trans * opt->link_trans; a.lr2 = opt->link_rot * opt->link_rot;
+  a.result = md.result.p;
+  bool scores = false;
+  if (own) {   // the stream is idle and stays so until this call returns: one pinned block carries the set up
+    const size_t n_in = (size_t)P * (opt->weightsP ? 7 : 6);
+    HIPCHK(c, md.in_pose.ensure((size_t)P * 6));
+    if (md.h_in.cap < n_in) HIPCHK(c, md.h_in.alloc(n_in));
+    std::memcpy(md.h_in.p, opt->particles6xP, (size_t)P * 48);
+    HIPCHK(c, hipMemcpyAsync(md.in_pose.p, md.h_in.p, (size_t)P * 48, hipMemcpyHostToDevice, c->stream));
+    a.pose = md.in_pose.p;
+    if (opt->weightsP) {
+      HIPCHK(c, md.in_w.ensure((size_t)P));
+      std::memcpy(md.h_in.p + (size_t)P * 6, opt->weightsP, (size_t)P * 8);
+      HIPCHK(c, hipMemcpyAsync(md.in_w.p, md.h_in.p + (size_t)P * 6, (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+      a.w = md.in_w.p;
+    }
+  } else {
+    a.pose = c->st.pose_out.p;
+    a.w = c->st.stats.p + 48;   // what svnicp_get_particle_weight returns
+    scores = c->sc.have && c->sc.of_result && c->sc.P == P;
+    if (scores) a.scores = c->sc.scores.p;
+  }
+  HIPCHK(c, launch_particle_modes(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(md.h_result.p, md.result.p, modes_result_bytes(P), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double* r = md.h_result.p;
+  svnicp_modes o{};
+  o.struct_size = (int32_t)sizeof o;
+  o.particles = (int32_t)r[0]; o.nonfinite = (int32_t)r[1]; o.n_modes = (int32_t)r[2]; o.n_reported = (int32_t)r[3];
+  o.has_scores = scores ? 1 : 0;
+  for (int k = 0; k < SVNICP_MODES_MAX; ++k) {
+    const double* rec = r + kModesHeader + (size_t)k * kModesRecord;
+    o.label[k] = (int32_t)rec[0]; o.count[k] = (int32_t)rec[1]; o.best[k] = (int32_t)rec[2];
+    o.mass[k] = rec[3]; o.cost_min[k] = rec[4]; o.cost_mean[k] = rec[5];
+    std::memcpy(o.mean[k], rec + 6, sizeof o.mean[k]); std::memcpy(o.cov[k], rec + 12, sizeof o.cov[k]);
+    if (k < o.n_reported) {
+      EvalPose T{};
+      correction_total_pose(c->pose0, o.mean[k], T);
+      std::memcpy(o.R[k], T.R, sizeof T.R); std::memcpy(o.t[k], T.t, sizeof T.t);
+    }
+  }
+  *out = o;
+  md.have = true; md.P = P;
+  return SVNICP_OK;
+}
+
+int svnicp_get_mode_labels(svnicp_ctx* c, int32_t* outP) {
+  CTX_CHECK(c);
+  if (!outP) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_mode_labels: null output");
+  if (!c->md.have) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_mode_labels: no svnicp_particle_modes yet");
+  std::memcpy(outP, c->md.h_result.p + kModesResult, (size_t)c->md.P * sizeof(int32_t));
   return SVNICP_OK;
 }
 

@@ -332,6 +332,24 @@ hipError_t launch_particle_score(ScoreArgs a, double* scores, hipStream_t st);
 // w[p] = exp(-(cost_p - cost_min) / temperature) / Z, Z added in particle order (one workgroup)
 hipError_t launch_particle_weights(const double* scores, int P, double temperature, double* w, hipStream_t st);
 
+// ---------------- particle modes (particle_modes.hip) ----------------
+constexpr int kModesMax = 32;          // SVNICP_MODES_MAX
+constexpr int kModesMaxP = 2048;       // particles one workgroup stages: 72 bytes of LDS each (147 KB); more is refused
+constexpr int kModesHeader = 8;        // particles, nonfinite, n_modes, n_reported, sweeps, W_all, 0, 0
+constexpr int kModesRecord = 48;       // per reported mode: label, count, best, mass, cost_min, cost_mean, mean[6], cov[36]
+constexpr int kModesResult = kModesHeader + kModesMax * kModesRecord;   // doubles; the int32 labels [P] follow them
+struct ModesArgs {
+  const double* pose;    // [6][P] component-major (pose_out)
+  const double* w;       // [P], or nullptr: every weight is 1.0
+  const double* scores;  // [P][kScoreFields] of a scoring of exactly these particles, or nullptr
+  int P, max_modes;
+  double lt2, lr2;       // link_trans^2, link_rot^2
+  double* result;        // [kModesResult] doubles (the integers exact), then int32 [P]: rank of each particle's mode, -1 = non-finite
+};
+inline size_t modes_result_bytes(int P) { return (size_t)kModesResult * sizeof(double) + (size_t)P * sizeof(int32_t); }
+// k_particle_modes: one workgroup; hipErrorInvalidValue for P outside [1, kModesMaxP] or max_modes outside [1, kModesMax]
+hipError_t launch_particle_modes(const ModesArgs& a, hipStream_t st);
+
 // ---------------- mini-batch tables (minibatch.hip) ----------------
 struct MinibatchArgs {
   const int32_t* explicit_idx;  // [n] a caller's table (validated by the draw kernel), or nullptr: generated from `base`

@@ -595,6 +595,12 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   double weight_dist = 0.0;    // > 0: every registration ends with one scoring of the particles at this gate and soft-min weights
                                // (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures
   double weight_temperature = 0.0;   // with weight_dist: the soft-min temperature in m^2, > 0
+  // mode_link_trans >= 0 (with mode_link_rot >= 0): after every registration the particles are grouped into modes
+  // (svnicp_particle_modes) in ScanResult::modes; negative (the default) = off, no call is made
+  double mode_link_trans = -1.0, mode_link_rot = -1.0;
+  int mode_max = 8;                  // with the links: modes reported in full (1..SVNICP_MODES_MAX)
+  bool mode_select_heaviest = false; // the correction is the first mode's mean instead of the global mean, and the pose, the
+                                     // evaluate, the information and the map update follow it; needs the links
 };
 
 struct ScanResult {
@@ -609,6 +615,7 @@ struct ScanResult {
   double fitness = -1, inlier_rmse = -1, plane_rmse = -1;
   int64_t plane_inliers = -1;
   std::optional<svnicp_information> information;   // cfg.information != "off": H, b, eigen-structure, rank, step, cov at the result pose
+  std::optional<svnicp_modes> modes;               // cfg.mode_link_*: the modes of the final particle set, heaviest first
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -633,6 +640,11 @@ class RegistrationPipeline {
     if (cfg.information != "off" && !(cfg.info_huber > 0)) throw std::invalid_argument("PipelineConfig: info_huber must be > 0 (+inf = unweighted)");
     if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
     if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
+    const bool mode_link = !(cfg.mode_link_trans < 0 && cfg.mode_link_rot < 0);
+    if (mode_link && !(std::isfinite(cfg.mode_link_trans) && cfg.mode_link_trans >= 0 && std::isfinite(cfg.mode_link_rot) && cfg.mode_link_rot >= 0))
+      throw std::invalid_argument("PipelineConfig: mode_link must be (link_trans, link_rot), both finite and >= 0");
+    if (mode_link && !(cfg.mode_max >= 1 && cfg.mode_max <= SVNICP_MODES_MAX)) throw std::invalid_argument("PipelineConfig: mode_max must lie in 1..32");
+    if (cfg.mode_select_heaviest && !mode_link) throw std::invalid_argument("PipelineConfig: mode_select \"heaviest\" needs mode_link (the modes are what it selects from)");
     if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
     if (cfg.gpu_map) dmap_ = std::make_unique<DeviceVoxelMap>(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points, cfg.device);
     if (cfg.gpu_map && cfg.gpu_prep) dprep_ = std::make_unique<DevicePrep>(cfg.device);
@@ -732,6 +744,14 @@ class RegistrationPipeline {
     res.cov = solver_->get_cov_matrix();
     res.particles = solver_->get_particles();
     res.weights = solver_->get_particle_weight();
+    if (cfg_.mode_link_trans >= 0) {   // no policy here: "heaviest" is the caller's choice, made once in the configuration
+      res.modes = solver_->particle_modes(cfg_.mode_link_trans, cfg_.mode_link_rot, cfg_.mode_max);
+      const svnicp_modes& m = *res.modes;
+      bool finite = m.n_reported > 0;
+      for (int i = 0; i < 6; ++i) finite = finite && std::isfinite(m.mean[0][i]);
+      if (cfg_.mode_select_heaviest && finite)
+        for (int i = 0; i < 6; ++i) res.correction[i] = m.mean[0][i];
+    }
     res.pose = guess * correction_to_pose(res.correction);                                             // updater_, :37-46
     if (cfg_.eval_dist > 0) {   // the number a caller may gate the map update on (no policy here)
       const svnicp_eval ev = solver_->evaluate(cfg_.eval_dist, res.pose.R.data(), res.pose.t.data());

@@ -182,6 +182,27 @@ class SVGDICP {
   void set_particle_weighting(int kind, double max_corr_dist = 0.0, double temperature = 0.0) {
     chk(svnicp_set_particle_weighting(h_, kind, max_corr_dist, temperature));
   }
+  // particle modes (svnicp_hip.h "particle modes"): the connected components of the particles' link graph, heaviest first, with
+  // mass, mean, covariance, total pose and best-scored member.  particles6xP == nullptr: the last registration's set with its
+  // weights; else a host [6][P] block of the caller's (no registration needed) with weightsP [P] or equal weights
+  svnicp_modes particle_modes(double link_trans, double link_rot, int max_modes = 8, const double* particles6xP = nullptr, int P = 0,
+                              const double* weightsP = nullptr) {
+    svnicp_modes_opt opt{};
+    opt.struct_size = (int32_t)sizeof opt; opt.max_modes = max_modes; opt.link_trans = link_trans; opt.link_rot = link_rot;
+    opt.particles6xP = particles6xP; opt.P = P; opt.weightsP = weightsP;
+    svnicp_modes o{};
+    o.struct_size = (int32_t)sizeof o;
+    chk(svnicp_particle_modes(h_, &opt, &o));
+    modes_P_ = o.particles;
+    return o;
+  }
+  // per particle of the last particle_modes: the rank of its mode (0 = the heaviest), -1 for a non-finite particle
+  std::vector<int32_t> get_mode_labels() {
+    std::vector<int32_t> o((size_t)(modes_P_ > 0 ? modes_P_ : 1), -1);
+    chk(svnicp_get_mode_labels(h_, o.data()));
+    o.resize((size_t)modes_P_);
+    return o;
+  }
   const int32_t* eval_index_ptr() { return svnicp_eval_index_devptr(h_); }
   const double* eval_dist2_ptr() { return svnicp_eval_dist2_devptr(h_); }
   svnicp_ctx* handle() { return h_; }
@@ -192,6 +213,7 @@ class SVGDICP {
   svnicp_ctx* h_ = nullptr;
   int P_, I_;
   int batch_ = 0;
+  int modes_P_ = 0;
 };
 
 class SVNICP final : public SVGDICP {

@@ -904,8 +904,20 @@ class PipelineConfig:
     weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
     weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
     map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
+    mode_link: tuple | None = None  # (link_trans m, link_rot rad): after every registration the particles are grouped into modes (svnicp_particle_modes) in ScanResult.modes; None = off, no call is made
+    mode_max: int = 8              # with mode_link: modes reported in full (1..32)
+    mode_select: str = "mean"      # "heaviest": the correction is the first mode's mean instead of the global mean, and the pose, the evaluate, the information and the map update follow it; needs mode_link
 
     def __post_init__(self):
+        if self.mode_select not in ("mean", "heaviest"):
+            raise ValueError('PipelineConfig: mode_select must be "mean" or "heaviest"')
+        if self.mode_link is not None:
+            if len(tuple(self.mode_link)) != 2 or not all(np.isfinite(v) and v >= 0 for v in self.mode_link):
+                raise ValueError("PipelineConfig: mode_link must be (link_trans, link_rot), both finite and >= 0")
+            if not 1 <= int(self.mode_max) <= 32:
+                raise ValueError("PipelineConfig: mode_max must lie in 1..32")
+        elif self.mode_select == "heaviest":
+            raise ValueError('PipelineConfig: mode_select "heaviest" needs mode_link (the modes are what it selects from)')
         if not (np.isfinite(self.weight_dist) and self.weight_dist >= 0):
             raise ValueError("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)")
         if self.weight_dist > 0 and not (np.isfinite(self.weight_temperature) and self.weight_temperature > 0):
@@ -941,6 +953,7 @@ class ScanResult:
     plane_rmse: float | None = None          # … sqrt(mean r2) over the inliers whose target has a normal; None without normals
     plane_inliers: int | None = None
     information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
+    modes: object | None = None              # cfg.mode_link: solver.ParticleModes of the final particle set, heaviest first
 
 
 class RegistrationPipeline:
@@ -1042,8 +1055,15 @@ class RegistrationPipeline:
                               with_normal=with_normal)
         corr = s.get_transformation()                                                                           # :605
         pose = guess @ correction_to_pose(corr)                                                                 # updater_, :37-46
+        modes = None
+        if c.mode_link is not None:   # no policy here: "heaviest" is the caller's choice, made once in the configuration
+            modes = s.particle_modes(c.mode_link[0], c.mode_link[1], c.mode_max)
+            if c.mode_select == "heaviest" and modes.n_reported > 0 and np.isfinite(modes.mean[0]).all():
+                corr = modes.mean[0].copy()
+                pose = guess @ correction_to_pose(corr)
         res = ScanResult(stamp, pose, guess, corr, s.get_distribution(), s.get_cov_matrix(), s.get_particles().reshape(-1),
                          s.get_particle_weight(), t1 - t0, 0.0, int(state), with_normal)
+        res.modes = modes
         if c.eval_dist > 0:   # the number a caller may gate the map update on (no policy here)
             ev = s.evaluate(c.eval_dist, pose)
             res.fitness, res.inlier_rmse = ev.fitness, ev.inlier_rmse

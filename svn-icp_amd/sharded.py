@@ -234,8 +234,8 @@ class ShardedSVNICP:
         be.synchronize()
         return SteinICPState.ALIGN_SUCCESS
 
-    def __getattr__(self, name):  # getters of the reference interface
-        if name.startswith("get_"):
+    def __getattr__(self, name):  # getters of the reference interface, and the modes of the particle set: every rank holds all P poses
+        if name.startswith("get_") or name == "particle_modes":
             return getattr(self.be.solver, name)
         raise AttributeError(name)
 

@@ -124,6 +124,37 @@ class RegistrationInformation:
     pose: np.ndarray           # 4x4, the evaluated pose
 
 
+@dataclass
+class ParticleModes:
+    """struct svnicp_modes (include/svnicp_hip.h, "particle modes"): the connected components of the particles' link graph,
+    heaviest first; the per-mode arrays hold ``n_reported`` entries."""
+    particles: int             # P of the set that was clustered
+    nonfinite: int             # particles with a non-finite component: in no mode
+    n_modes: int               # all modes
+    n_reported: int            # min(n_modes, max_modes)
+    has_scores: bool           # best / cost_min / cost_mean are filled
+    label: np.ndarray          # [n] lowest particle index of the mode
+    count: np.ndarray          # [n] members
+    best: np.ndarray           # [n] member with the lowest cost, -1 without scores
+    mass: np.ndarray           # [n] W / W_all
+    cost_min: np.ndarray       # [n]
+    cost_mean: np.ndarray      # [n]
+    mean: np.ndarray           # [n, 6] correction coordinates, as get_transformation
+    cov: np.ndarray            # [n, 6, 6]
+    pose: np.ndarray           # [n, 4, 4] the mode's total pose (map <- sensor): what ``evaluate(pose=...)`` takes
+
+
+def _modes_from_struct(o) -> ParticleModes:
+    n = int(o.n_reported)
+    arr = lambda name, dtype, *shape: np.array(getattr(o, name)[:], dtype).reshape((binding.MODES_MAX,) + shape)[:n].copy()   # noqa: E731
+    T = np.tile(np.eye(4), (n, 1, 1))
+    T[:, :3, :3] = arr("R", np.float64, 3, 3)
+    T[:, :3, 3] = arr("t", np.float64, 3)
+    return ParticleModes(int(o.particles), int(o.nonfinite), int(o.n_modes), n, bool(o.has_scores), arr("label", np.int32),
+                         arr("count", np.int32), arr("best", np.int32), arr("mass", np.float64), arr("cost_min", np.float64),
+                         arr("cost_mean", np.float64), arr("mean", np.float64, 6), arr("cov", np.float64, 6, 6), T)
+
+
 _INFO_FORMS = {"point": binding.INFO_POINT, "plane": binding.INFO_PLANE}
 
 
@@ -533,6 +564,38 @@ class _SolverBase:
         self._check(self._L.svnicp_get_particle_scores(self._h, out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
                     "svnicp_get_particle_scores")
         return self._scores(out, poses)
+
+    # -- particle modes (include/svnicp_hip.h "particle modes") --------------------------------------------------------------
+    def particle_modes(self, link_trans: float, link_rot: float, max_modes: int = 8, particles=None, weights=None) -> ParticleModes:
+        """Group the particles into modes: the connected components of the graph that links two particles whose translations
+        differ by at most ``link_trans`` (m) and whose rotation vectors by at most ``link_rot`` (rad), heaviest first.
+        ``particles=None``: the last registration's set with its weights; else a [6, P] array of your own (no registration
+        needed) with ``weights`` [P] or equal weights."""
+        opt, o = binding.ModesOptStruct(), binding.ModesStruct()
+        opt.struct_size, o.struct_size = C.sizeof(binding.ModesOptStruct), C.sizeof(binding.ModesStruct)
+        opt.max_modes, opt.link_trans, opt.link_rot = int(max_modes), float(link_trans), float(link_rot)
+        dp = C.POINTER(C.c_double)
+        keep = []
+        if particles is not None:
+            x = np.ascontiguousarray(np.asarray(particles, np.float64).reshape(6, -1))
+            keep.append(x)
+            opt.particles6xP, opt.P = x.ctypes.data_as(dp), x.shape[1]
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+            if particles is not None and w.size != opt.P:
+                raise ValueError("particle_modes: weights must hold one entry per particle")
+            keep.append(w)
+            opt.weightsP = w.ctypes.data_as(dp)
+        self._check(self._L.svnicp_particle_modes(self._h, C.byref(opt), C.byref(o)), "svnicp_particle_modes")
+        self._modes_P = int(o.particles)
+        return _modes_from_struct(o)
+
+    def get_mode_labels(self) -> np.ndarray:
+        """Per particle of the last ``particle_modes``: the rank of its mode (0 = the heaviest, ranks beyond ``n_reported``
+        included), -1 for a non-finite particle."""
+        out = np.full(max(getattr(self, "_modes_P", 0), 1), -1, np.int32)
+        self._check(self._L.svnicp_get_mode_labels(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "svnicp_get_mode_labels")
+        return out[:getattr(self, "_modes_P", 0)]
 
     def set_threshold(self, max_dist: float):
         self._check(self._L.svnicp_set_max_dist(self._h, float(max_dist)), "svnicp_set_max_dist")
