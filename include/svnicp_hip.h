@@ -715,6 +715,50 @@ int svnicp_prep_download_seg_images(svnicp_prep *prep, int32_t *owner, float *ra
                                     int64_t cap_pixels);   /* test taps: row-major [n_scan][horizon_scan] of the last call; owner
                                                               -1 / range -100000 = empty; label as labelMat_ (-1, 1.., 999999) */
 
+/* ---- visibility-based clearing of the local map (not in the reference): drop the stored points the new scan sees through
+ * A stored map point is deleted when the scan's beam in its direction returned from clearly BEHIND it.  Inputs: the scan (n x 3
+ * float32, sensor frame, host or device), its pose R | t (double, map <- sensor), the sensor geometry (of svnicp_seg_params
+ * only n_scan, horizon_scan, ang_res_x, ang_res_y, ang_bottom and min_range are read) and the options below.
+ *   image       [n_scan][horizon_scan] float32, empty = +inf.  A scan point takes part iff it passes the projection of the
+ *               segmentation block above unchanged (finite coordinates, the row rule, the column rule, r >= min_range), with
+ *               that block's row, column and r = sqrtf((x*x+y*y)+z*z).  A pixel keeps the MINIMUM r of its points (not the
+ *               last point: the conservative choice for a rule that deletes, and independent of the input order).
+ *   map point   p (float32) of every live voxel: d = double(p) - t, s_c = float((R[0][c]*d0 + R[1][c]*d1) + R[2][c]*d2)
+ *               (R^T d, unfused, rounded once), projected by the same function to (row, col, r_m).  The point is KEPT when it
+ *               does not project (outside the vertical field of view, non-finite, r_m < min_range), when r_m > max_range, or
+ *               when its own pixel is empty.  Otherwise r_min = the minimum of the filled pixels over rows row + dr,
+ *               |dr| <= window_rows, inside [0, n_scan) (rows do not wrap) and columns (col + dc) mod horizon_scan,
+ *               |dc| <= window_cols (columns wrap), and the point is REMOVED iff
+ *                   r_m < r_min - fmaxf(margin_abs, margin_rel * r_min)      (float32, unfused; equality keeps the point).
+ *               The window is part of the rule: at grazing incidence one pixel spans metres of range, and a single-pixel test
+ *               eats the ground.
+ *   voxel       survivors keep their order and are compacted to the front; the next survivor becomes the voxel's first point,
+ *               which svnicp_map_add_cloud's range cull and svnicp_map_query(center, r) read as before.  A voxel left empty
+ *               becomes a tombstone exactly as the range cull makes one, and svnicp_map_add_cloud's rebuild rule applies
+ *               unchanged; a later svnicp_map_add_cloud refills freed room in input order.
+ * The call invalidates the last query like svnicp_map_add_cloud (svnicp_map_query_normals refuses until the next query).  It
+ * is complete when it returns (one host synchronisation, for the statistics).  Two calls with the same inputs on equal maps
+ * give bit-identical maps, and the host restatements (pipeline.py / registration_pipeline.hpp: clear_seen_through) follow
+ * the device point for point.
+ * SVNICP_ERR_INVALID, nothing enqueued: a NULL map / R / t / sensor / opt / out, scan_xyz NULL with n > 0, a struct_size that
+ * does not match, n_scan outside 1..128, horizon_scan < 1, n_scan * horizon_scan > 2^19, ang_res_x / ang_res_y not finite and
+ * positive, ang_bottom / min_range not finite, window_rows outside 0..4, window_cols outside 0..8, a negative or non-finite
+ * margin, a non-positive or non-finite max_range, n < 0 or n > 2^31 - 1.  n = 0 or an empty map: success, zero statistics. */
+typedef struct svnicp_visibility_opt {
+  int32_t struct_size;                    /* = sizeof(svnicp_visibility_opt) */
+  int32_t window_rows, window_cols;       /* 0..4, 0..8 */
+  float margin_abs, margin_rel, max_range;   /* m, ratio of r_min, m */
+} svnicp_visibility_opt;
+typedef struct svnicp_visibility_stats {
+  int64_t pixels_filled;     /* pixels of the image that hold a finite range */
+  int64_t points_tested;     /* stored points that reached the comparison */
+  int64_t points_removed;
+  int64_t voxels_emptied;    /* voxels that became tombstones */
+} svnicp_visibility_stats;
+int svnicp_map_clear_seen_through(svnicp_map *map, const float *scan_xyz, int64_t n, int mem_kind, const double R_rowmajor[9],
+                                  const double t[3], const svnicp_seg_params *sensor, const svnicp_visibility_opt *opt,
+                                  svnicp_visibility_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

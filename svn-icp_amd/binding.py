@@ -31,6 +31,18 @@ class SegParamsStruct(C.Structure):
                 ("valid_line_num", C.c_int32)]
 
 
+class VisibilityOptStruct(C.Structure):
+    """struct svnicp_visibility_opt (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("window_rows", C.c_int32), ("window_cols", C.c_int32), ("margin_abs", C.c_float),
+                ("margin_rel", C.c_float), ("max_range", C.c_float)]
+
+
+class VisibilityStatsStruct(C.Structure):
+    """struct svnicp_visibility_stats (include/svnicp_hip.h)."""
+    _fields_ = [("pixels_filled", C.c_int64), ("points_tested", C.c_int64), ("points_removed", C.c_int64),
+                ("voxels_emptied", C.c_int64)]
+
+
 class EvalStruct(C.Structure):
     """struct svnicp_eval (include/svnicp_hip.h)."""
     _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("rows", C.c_int64), ("evaluated", C.c_int64),
@@ -132,6 +144,8 @@ def load_library():
     L.svnicp_map_normals_devptr.argtypes = [vp]
     L.svnicp_map_normals_devptr.restype = vp
     L.svnicp_map_download_normals.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64)]
+    L.svnicp_map_clear_seen_through.argtypes = [vp, vp, C.c_int64, C.c_int, dp, dp, C.POINTER(SegParamsStruct),
+                                                C.POINTER(VisibilityOptStruct), C.POINTER(VisibilityStatsStruct)]
     L.svnicp_prep_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.svnicp_prep_destroy.argtypes = [vp]
     L.svnicp_prep_destroy.restype = None

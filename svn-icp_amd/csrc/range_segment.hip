@@ -30,6 +30,7 @@
 
 #include "../../include/svnicp_hip.h"
 #include "prep_state.hpp"
+#include "range_project_device.hpp"
 
 namespace {
 
@@ -44,10 +45,8 @@ struct SegK {
   int vpn, vln;
 };
 
-// the project's atan2f: float64 atan2 of the float32 operands, rounded once
-__device__ __forceinline__ float atan2_f32(float y, float x) { return (float)::atan2((double)y, (double)x); }
-// float(double(a * 180.0f) / M_PI)
-__device__ __forceinline__ float deg_f32(float a) { return (float)((double)(a * 180.0f) / kPi); }
+using svnicp::atan2_f32;   // range_project_device.hpp: the projection and its two float helpers, shared with voxel_map.hip
+using svnicp::deg_f32;
 
 __device__ __forceinline__ float point_range(const float* __restrict__ in, int o) {
   const float x = in[3 * (size_t)o], y = in[3 * (size_t)o + 1], z = in[3 * (size_t)o + 2];
@@ -57,19 +56,11 @@ __device__ __forceinline__ float point_range(const float* __restrict__ in, int o
 __global__ __launch_bounds__(256) void k_seg_project(const float* __restrict__ in, int64_t n, SegK K, int* __restrict__ owner) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
-  if (!(isfinite(x) && isfinite(y) && isfinite(z))) return;                 // removeNaNFromPointCloud (:240)
-  const float va = deg_f32(atan2_f32(z, sqrtf(x * x + y * y)));
-  const float q = (va + K.bottom) / K.res_y;
-  if (!(q > -1.0f && q < (float)K.N)) return;                               // size_t conversion: (-1, 0) is row 0 (x86-64)
-  const int row = (int)q;
-  const float h = deg_f32(atan2_f32(x, y));
-  double c = -round(((double)h - 90.0) / (double)K.res_x) + (double)(K.H / 2);
-  if (c >= (double)K.H) c -= (double)K.H;
-  if (!(c >= 0.0 && c < (double)K.H)) return;                               // negative: wraps in size_t, dropped
-  const float r = sqrtf((x * x + y * y) + z * z);
-  if (r < K.min_range) return;
-  atomicMax(&owner[row * K.H + (int)c], (int)i);                            // the last point in input order wins
+  const svnicp::RangeSensor S{K.N, K.H, K.res_x, K.res_y, K.bottom, K.min_range};
+  int row, col;
+  float r;
+  if (!svnicp::range_project(in[3 * i], in[3 * i + 1], in[3 * i + 2], S, row, col, r)) return;   // projectPointCloud (:281-325)
+  atomicMax(&owner[row * K.H + col], (int)i);                            // the last point in input order wins
 }
 
 // groundRemoval's pair test: lower pixel owner a, upper pixel owner b, both filled

@@ -7,6 +7,8 @@
 //                                          voxel_size truncated toward zero (:29), append while the voxel has room, then
 //   RemoveFarPointCloud(pos)    (:89-97)  drop every voxel whose FIRST point is farther than max_range,
 //   GetMap(pose, r) / GetMap()  (:44-58)  all points of the voxels whose first point is closer than r (or of all voxels).
+// Not in the reference: the normals of a query's rows from the map's own voxels (svnicp_map_query_normals) and the
+// visibility-based clearing of stored points a new scan sees through (svnicp_map_clear_seen_through), both further down.
 // The reference keeps it in a tsl::robin_map on the host and re-uploads the query result for every scan
 // (OdometryPipeline.cpp:577-582); here the table lives in HBM and a query writes float64 rows straight into a device
 // buffer the solver copies device-to-device (svnicp_set_target, SVNICP_MEM_DEVICE) — per scan only the new points go over
@@ -33,6 +35,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "plane_normal_device.hpp"
+#include "range_project_device.hpp"
 
 namespace {
 
@@ -415,6 +418,111 @@ __global__ __launch_bounds__(64) void k_map_normals(const unsigned long long* __
   if (lane == 0 && nvalid) atomicAdd(with_normal, nvalid);
 }
 
+// ---------------------------------------------------------------------------------------------
+// visibility-based clearing (svnicp_map_clear_seen_through; the contract is in include/svnicp_hip.h)
+// ---------------------------------------------------------------------------------------------
+// The minimum-range image holds the bit patterns of non-negative floats, which order as unsigned integers: one 32-bit atomicMin
+// per scan point, whatever the schedule.  Empty = the pattern of +inf.
+constexpr unsigned int kVisEmpty = 0x7f800000u;
+
+struct VisOpt { int wr, wc; float margin_abs, margin_rel, max_range; };
+
+// the fills of the call in one launch: the image, the selection keys (entries the selection does not fill stay ~0), the
+// selection counter and the call's statistics
+__global__ __launch_bounds__(256) void k_vis_fill(unsigned int* __restrict__ img, int64_t npix, unsigned long long* __restrict__ sel_key,
+                                                  int64_t live, int* __restrict__ nsel, unsigned long long* __restrict__ vstats) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < npix) img[i] = kVisEmpty;
+  if (i < live) sel_key[i] = kEmpty;
+  if (i < 4) vstats[i] = 0ull;
+  if (i == 0) *nsel = 0;
+}
+
+__global__ __launch_bounds__(256) void k_vis_image(const float* __restrict__ in, int64_t n, svnicp::RangeSensor S,
+                                                   unsigned int* __restrict__ img, unsigned long long* __restrict__ vstats) {
+  __shared__ int s_new;
+  if (threadIdx.x == 0) s_new = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    int row, col;
+    float r;
+    if (svnicp::range_project(in[3 * i], in[3 * i + 1], in[3 * i + 2], S, row, col, r)) {
+      const unsigned int bits = __float_as_uint(r);   // r >= +0: the pattern orders as the value
+      // a pixel counts as filled once: for the thread that finds it empty and brings a finite range
+      if (atomicMin(&img[row * S.H + col], bits) == kVisEmpty && bits < kVisEmpty) atomicAdd(&s_new, 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_new) atomicAdd(&vstats[0], (unsigned long long)s_new);   // one global atomic per workgroup
+}
+
+// One wave per live voxel (sel_slot of an "all voxels" selection, any order).  The voxel's points are taken in blocks of 64:
+// a block is read into registers, every lane decides about its point, the survivors' positions are the running base plus the
+// prefix popcount of the keep ballot.  A survivor's write position never passes its read position and a block is read before
+// anything of it is written (the store addresses depend on the ballot, which depends on every lane's loads), so the
+// compaction is in place.  No LDS, no per-thread arrays.
+__global__ __launch_bounds__(64) void k_vis_clear(unsigned long long* __restrict__ keys, int* __restrict__ counts, float* pts,
+                                                  int max_points, const unsigned long long* __restrict__ sel_key,
+                                                  const unsigned int* __restrict__ sel_slot, MapPose pose, svnicp::RangeSensor S, VisOpt O,
+                                                  const unsigned int* __restrict__ img, int* __restrict__ stats,
+                                                  unsigned long long* __restrict__ vstats) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  if (sel_key[j] == kEmpty) return;   // an entry the selection did not fill (workgroup-uniform)
+  const unsigned int slot = sel_slot[j];
+  int cnt = counts[slot];
+  cnt = cnt > max_points ? max_points : cnt;
+  float* P = pts + (size_t)slot * max_points * 3;
+  int base = 0, tested = 0;
+  for (int b0 = 0; b0 < cnt; b0 += 64) {
+    const int i = b0 + lane;
+    const bool have = i < cnt;
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+    if (have) { x = P[3 * i]; y = P[3 * i + 1]; z = P[3 * i + 2]; }
+    bool test = false, remove = false;
+    if (have) {
+      const double d0 = (double)x - pose.t[0], d1 = (double)y - pose.t[1], d2 = (double)z - pose.t[2];
+      const float s0 = (float)((pose.R[0] * d0 + pose.R[3] * d1) + pose.R[6] * d2);   // R^T d, rounded once
+      const float s1 = (float)((pose.R[1] * d0 + pose.R[4] * d1) + pose.R[7] * d2);
+      const float s2 = (float)((pose.R[2] * d0 + pose.R[5] * d1) + pose.R[8] * d2);
+      int row, col;
+      float rm;
+      if (svnicp::range_project(s0, s1, s2, S, row, col, rm) && !(rm > O.max_range) && img[row * S.H + col] < kVisEmpty) {
+        const int r_lo = row - O.wr < 0 ? 0 : row - O.wr, r_hi = row + O.wr > S.N - 1 ? S.N - 1 : row + O.wr;   // rows do not wrap
+        unsigned int mn = kVisEmpty;
+        for (int rr = r_lo; rr <= r_hi; ++rr)
+          for (int dc = -O.wc; dc <= O.wc; ++dc) {
+            int cc = (col + dc) % S.H;   // columns wrap (|dc| may exceed a tiny H: a true modulo)
+            if (cc < 0) cc += S.H;
+            const unsigned int v = img[rr * S.H + cc];
+            mn = v < mn ? v : mn;
+          }
+        const float r_min = __uint_as_float(mn);   // finite: the own pixel is in the window
+        test = true;
+        remove = rm < r_min - fmaxf(O.margin_abs, O.margin_rel * r_min);
+      }
+    }
+    const bool keep = have && !remove;
+    const unsigned long long km = __ballot(keep);
+    const int pos = base + lanes_below(km);
+    if (keep && pos != i) { P[3 * pos] = x; P[3 * pos + 1] = y; P[3 * pos + 2] = z; }
+    base += __popcll(km);
+    tested += __popcll(__ballot(test));
+  }
+  if (lane == 0) {
+    if (base != cnt) {
+      counts[slot] = base;
+      atomicAdd(&vstats[2], (unsigned long long)(cnt - base));
+      if (base == 0) {   // a tombstone, as k_map_remove_far makes one
+        keys[slot] = kTomb;
+        atomicSub(&stats[0], 1); atomicAdd(&stats[1], 1);
+        atomicAdd(&vstats[3], 1ull);
+      }
+    }
+    if (tested) atomicAdd(&vstats[1], (unsigned long long)tested);
+  }
+}
+
 }  // namespace
 
 struct svnicp_map {
@@ -429,9 +537,11 @@ struct svnicp_map {
   GrowBuf<unsigned int> slot, sslot, sel_slot, sel_slot2;
   GrowBuf<double> out, nrm;
   GrowBuf<unsigned char> tmp;
+  GrowBuf<unsigned int> vis_img;           // svnicp_map_clear_seen_through: the minimum-range image (float bit patterns)
+  GrowBuf<unsigned long long> vis_stats;   // ... and its four statistics
   int64_t last_M = 0;
   // svnicp_map_query_normals: the last query's selection (sel_key2 / sel_off / sel_cnt over last_live entries) still describes
-  // the table — set by svnicp_map_query, dropped by svnicp_map_add_cloud and svnicp_map_clear
+  // the table — set by svnicp_map_query, dropped by svnicp_map_add_cloud, svnicp_map_clear_seen_through and svnicp_map_clear
   bool query_valid = false;
   int64_t last_live = 0;
   int64_t nrm_M = 0;     // rows of nrm that belong to the last query (0 until svnicp_map_query_normals ran for it)
@@ -610,6 +720,64 @@ int svnicp_map_add_cloud(svnicp_map* m, const float* xyz, int64_t n, int mem_kin
   return SVNICP_OK;
 }
 
+int svnicp_map_clear_seen_through(svnicp_map* m, const float* scan_xyz, int64_t n, int mem_kind, const double R_rowmajor[9], const double t[3],
+                                  const svnicp_seg_params* sensor, const svnicp_visibility_opt* opt, svnicp_visibility_stats* out) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (!R_rowmajor || !t || !sensor || !opt || !out || n < 0 || (n > 0 && !scan_xyz) || n > 0x7fffffffLL)
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: bad argument");
+  if (sensor->struct_size != (int32_t)sizeof(svnicp_seg_params) || opt->struct_size != (int32_t)sizeof(svnicp_visibility_opt))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: struct_size != sizeof(svnicp_seg_params) / sizeof(svnicp_visibility_opt)");
+  if (!(sensor->n_scan >= 1 && sensor->n_scan <= 128 && sensor->horizon_scan >= 1 &&
+        (int64_t)sensor->n_scan * sensor->horizon_scan <= (int64_t)1 << 19))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: need 1 <= n_scan <= 128, horizon_scan >= 1 and n_scan * horizon_scan <= 2^19");
+  if (!(std::isfinite(sensor->ang_res_x) && sensor->ang_res_x > 0.0f && std::isfinite(sensor->ang_res_y) && sensor->ang_res_y > 0.0f &&
+        std::isfinite(sensor->ang_bottom) && std::isfinite(sensor->min_range)))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: ang_res_x / ang_res_y must be finite and positive, ang_bottom / min_range finite");
+  if (!(opt->window_rows >= 0 && opt->window_rows <= 4 && opt->window_cols >= 0 && opt->window_cols <= 8))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: window_rows must be 0..4 and window_cols 0..8");
+  if (!(std::isfinite(opt->margin_abs) && opt->margin_abs >= 0.0f && std::isfinite(opt->margin_rel) && opt->margin_rel >= 0.0f))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: margin_abs / margin_rel must be finite and >= 0");
+  if (!(std::isfinite(opt->max_range) && opt->max_range > 0.0f))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_clear_seen_through: max_range must be finite and > 0");
+  HIPCHK(m, hipSetDevice(m->device));
+  m->query_valid = false; m->nrm_M = 0;
+  *out = svnicp_visibility_stats{0, 0, 0, 0};
+  // every call that changes the map ends by reading the statistics: the live voxels are known without asking the device
+  const int64_t live = m->h_stats[0] > 0 ? m->h_stats[0] : 0;
+  if (n == 0 || live == 0) return SVNICP_OK;
+  const svnicp::RangeSensor S{sensor->n_scan, sensor->horizon_scan, sensor->ang_res_x, sensor->ang_res_y, sensor->ang_bottom, sensor->min_range};
+  const VisOpt O{opt->window_rows, opt->window_cols, opt->margin_abs, opt->margin_rel, opt->max_range};
+  const int64_t npix = (int64_t)S.N * S.H;
+  const float* din = scan_xyz;
+  if (mem_kind != SVNICP_MEM_DEVICE) {
+    HIPCHK(m, m->in.ensure((size_t)n * 3));
+    HIPCHK(m, hipMemcpyAsync(m->in.p, scan_xyz, (size_t)n * 12, hipMemcpyHostToDevice, m->stream));
+    din = m->in.p;
+  }
+  HIPCHK(m, m->vis_img.ensure((size_t)npix)); HIPCHK(m, m->vis_stats.ensure(4));
+  HIPCHK(m, m->sel_key.ensure((size_t)live)); HIPCHK(m, m->sel_slot.ensure((size_t)live));
+  MapPose ps;
+  for (int i = 0; i < 9; ++i) ps.R[i] = R_rowmajor[i];
+  for (int i = 0; i < 3; ++i) ps.t[i] = t[i];
+  const int64_t nfill = npix > live ? npix : live;
+  hipLaunchKernelGGL(k_vis_fill, dim3((unsigned)((nfill + 255) / 256)), dim3(256), 0, m->stream, m->vis_img.p, npix, m->sel_key.p, live, m->nsel.p,
+                     m->vis_stats.p);
+  // every live voxel (r2 < 0), in any order: each is handled by itself
+  hipLaunchKernelGGL(k_map_select, dim3((unsigned)((m->cap + kSelChunk * 256 - 1) / (kSelChunk * 256))), dim3(256), 0, m->stream, m->keys.p, m->counts.p,
+                     m->pts.p, m->cap, m->max_points, 0.0, 0.0, 0.0, -1.0, m->sel_key.p, m->sel_slot.p, m->nsel.p, (int)live);
+  hipLaunchKernelGGL(k_vis_image, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, din, n, S, m->vis_img.p, m->vis_stats.p);
+  hipLaunchKernelGGL(k_vis_clear, dim3((unsigned)live), dim3(64), 0, m->stream, m->keys.p, m->counts.p, m->pts.p, m->max_points, m->sel_key.p,
+                     m->sel_slot.p, ps, S, O, m->vis_img.p, m->stats.p, m->vis_stats.p);
+  HIPCHK(m, hipGetLastError());
+  unsigned long long vs[4] = {0, 0, 0, 0};
+  HIPCHK(m, hipMemcpyAsync(vs, m->vis_stats.p, sizeof vs, hipMemcpyDeviceToHost, m->stream));
+  const int rc = read_stats(m);   // the only host synchronisation: live voxels and tombstones as the next call needs them
+  if (rc) return rc;
+  out->pixels_filled = (int64_t)vs[0]; out->points_tested = (int64_t)vs[1];
+  out->points_removed = (int64_t)vs[2]; out->voxels_emptied = (int64_t)vs[3];
+  return SVNICP_OK;
+}
+
 int svnicp_map_query(svnicp_map* m, const double center[3], double max_range, int64_t* count_out) {
   if (!m || !count_out) return SVNICP_ERR_INVALID;
   HIPCHK(m, hipSetDevice(m->device));
@@ -659,7 +827,7 @@ int svnicp_map_query_normals(svnicp_map* m, int normal_k, int64_t* with_normal_o
   if (!m) return SVNICP_ERR_INVALID;
   if (with_normal_out) *with_normal_out = 0;
   if (!m->query_valid)
-    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_query_normals: no svnicp_map_query yet, or the map changed (add_cloud / clear) since the last one");
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_query_normals: no svnicp_map_query yet, or the map changed (add_cloud / clear_seen_through / clear) since the last one");
   const int kn = normal_k ? normal_k : 16;
   if (kn < 4 || kn > 64) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_query_normals: normal_k must be 4..64 (0 = 16)");
   HIPCHK(m, hipSetDevice(m->device));

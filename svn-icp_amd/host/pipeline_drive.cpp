@@ -2,7 +2,7 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist] [information off|point|plane] [modes off|mean|heaviest link_trans link_rot]
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist] [information off|point|plane] [modes off|mean|heaviest link_trans link_rot] [clear 0|1]
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
 //      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
 //      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2;
@@ -11,7 +11,9 @@
 //      information point|plane: PipelineConfig::information (needs eval_dist > 0), one more line per registered scan:
 //      "info <scan>: pairs rank eigval[0] ... eigval[5]" with %.17g;
 //      modes mean|heaviest link_trans link_rot: PipelineConfig::mode_link_* / mode_select_heaviest, one more line per registered scan:
-//      "modes <scan>: n_modes n_reported nonfinite has_scores" and per reported mode " | label count best mass mean[0..5]" with %.17g)
+//      "modes <scan>: n_modes n_reported nonfinite has_scores" and per reported mode " | label count best mass mean[0..5]" with %.17g;
+//      clear 1: PipelineConfig::clear_seen_through with its defaults (window 1 x 1, margins 0.3 m / 0.02) and the HDL-64E sensor,
+//      one more line per registered scan: "clear <scan>: points_removed")
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -49,6 +51,7 @@ int main(int argc, char** argv) {
     cfg.mode_link_trans = atof(argv[15]); cfg.mode_link_rot = atof(argv[16]);
     cfg.mode_select_heaviest = std::string(argv[14]) == "heaviest";
   }
+  cfg.clear_seen_through = argc > 17 && atoi(argv[17]) != 0;
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;
@@ -90,6 +93,7 @@ int main(int argc, char** argv) {
         printf("info %d: %lld %d %.17g %.17g %.17g %.17g %.17g %.17g\n", s, (long long)in.pairs, (int)in.rank, in.eigval[0], in.eigval[1],
                in.eigval[2], in.eigval[3], in.eigval[4], in.eigval[5]);
       }
+      if (cfg.clear_seen_through && r.aligned) printf("clear %d: %lld\n", s, (long long)r.cleared);
       if (r.modes) {
         const svnicp_modes& m = *r.modes;
         printf("modes %d: %d %d %d %d", s, (int)m.n_modes, (int)m.n_reported, (int)m.nonfinite, (int)m.has_scores);

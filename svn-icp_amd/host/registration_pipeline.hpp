@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <numeric>
@@ -270,6 +271,23 @@ namespace seg_detail {
 constexpr double kPi = 3.14159265358979323846;
 inline float atan2_f32(float y, float x) { return (float)std::atan2((double)y, (double)x); }
 inline float deg_f32(float a) { return (float)((double)(a * 180.0f) / kPi); }
+// projectPointCloud's per-point part (:240, :281-325), the one statement of the projection on the host (segment_images and
+// VoxelHashMap::ClearSeenThrough): -> the point takes part; row, col, r its pixel and range
+inline bool range_project(float x, float y, float z, const svnicp_seg_params& prm, int* row, int* col, float* r) {
+  const int N = prm.n_scan, H = prm.horizon_scan;
+  if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) return false;   // removeNaNFromPointCloud (:240)
+  const float va = deg_f32(atan2_f32(z, std::sqrt(x * x + y * y)));
+  const float q = (va + prm.ang_bottom) / prm.ang_res_y;
+  if (!(q > -1.0f && q < (float)N)) return false;                            // size_t conversion as on x86-64
+  *row = (int)q;
+  const float h = deg_f32(atan2_f32(x, y));
+  double c = -std::round(((double)h - 90.0) / (double)prm.ang_res_x) + (double)(H / 2);
+  if (c >= (double)H) c -= (double)H;
+  if (!(c >= 0.0 && c < (double)H)) return false;
+  *col = (int)c;
+  *r = std::sqrt((x * x + y * y) + z * z);
+  return !(*r < prm.min_range);
+}
 }  // namespace seg_detail
 
 // the sensor ImageProjection.h compiles in (HDL-64E, :63-68) and the constants of :112-116 (= svnicp_seg_default_params(SVNICP_SEG_HDL64E))
@@ -293,19 +311,10 @@ inline SegImages segment_images(const Cloud& pts, const svnicp_seg_params& prm) 
   im.ground.assign(NP, 0);
   im.label.assign(NP, 0);
   for (size_t i = 0; i < pts.size(); ++i) {                                  // projectPointCloud (:281-325)
-    const float x = pts[i][0], y = pts[i][1], z = pts[i][2];
-    if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;   // removeNaNFromPointCloud (:240)
-    const float va = deg_f32(atan2_f32(z, std::sqrt(x * x + y * y)));
-    const float q = (va + prm.ang_bottom) / prm.ang_res_y;
-    if (!(q > -1.0f && q < (float)N)) continue;                              // size_t conversion as on x86-64
-    const int row = (int)q;
-    const float h = deg_f32(atan2_f32(x, y));
-    double c = -std::round(((double)h - 90.0) / (double)prm.ang_res_x) + (double)(H / 2);
-    if (c >= (double)H) c -= (double)H;
-    if (!(c >= 0.0 && c < (double)H)) continue;
-    const float r = std::sqrt((x * x + y * y) + z * z);
-    if (r < prm.min_range) continue;
-    const size_t p = (size_t)row * H + (size_t)c;
+    int row, col;
+    float r;
+    if (!range_project(pts[i][0], pts[i][1], pts[i][2], prm, &row, &col, &r)) continue;
+    const size_t p = (size_t)row * H + (size_t)col;
     im.owner[p] = (int32_t)i;                                                // the last point wins
     im.range[p] = r;
   }
@@ -414,6 +423,60 @@ class VoxelHashMap {
     }
     RemoveFarPointCloud(pose.t);
   }
+  // visibility-based clearing (include/svnicp_hip.h: svnicp_map_clear_seen_through, the same steps in the same float32 /
+  // float64 order as pipeline.py and csrc/voxel_map.hip): a stored point is dropped when the scan's beam in its direction
+  // returned from clearly behind it.  Throws std::invalid_argument where the C call answers SVNICP_ERR_INVALID.
+  svnicp_visibility_stats ClearSeenThrough(const Cloud& scan, const Pose3& pose, const svnicp_seg_params& sensor, const svnicp_visibility_opt& opt) {
+    const int N = sensor.n_scan, H = sensor.horizon_scan;
+    if (sensor.struct_size != (int32_t)sizeof(svnicp_seg_params) || opt.struct_size != (int32_t)sizeof(svnicp_visibility_opt) ||
+        !(N >= 1 && N <= 128 && H >= 1 && (int64_t)N * H <= (int64_t)1 << 19) ||
+        !(std::isfinite(sensor.ang_res_x) && sensor.ang_res_x > 0 && std::isfinite(sensor.ang_res_y) && sensor.ang_res_y > 0 &&
+          std::isfinite(sensor.ang_bottom) && std::isfinite(sensor.min_range)) ||
+        !(opt.window_rows >= 0 && opt.window_rows <= 4 && opt.window_cols >= 0 && opt.window_cols <= 8) ||
+        !(std::isfinite(opt.margin_abs) && opt.margin_abs >= 0 && std::isfinite(opt.margin_rel) && opt.margin_rel >= 0) ||
+        !(std::isfinite(opt.max_range) && opt.max_range > 0))
+      throw std::invalid_argument("VoxelHashMap::ClearSeenThrough: bad sensor or options");
+    svnicp_visibility_stats st{0, 0, 0, 0};
+    if (scan.empty() || map_.empty()) return st;
+    const float inf = std::numeric_limits<float>::infinity();
+    std::vector<float> img((size_t)N * H, inf);                                // the minimum-range image, +inf = empty
+    for (const auto& p : scan) {
+      int row, col;
+      float r;
+      if (!seg_detail::range_project(p[0], p[1], p[2], sensor, &row, &col, &r)) continue;
+      float& px = img[(size_t)row * H + col];
+      if (r < px) px = r;
+    }
+    for (float v : img) st.pixels_filled += v < inf ? 1 : 0;
+    for (auto it = map_.begin(); it != map_.end();) {
+      Cloud& v = it->second;
+      size_t w = 0;
+      for (size_t i = 0; i < v.size(); ++i) {
+        const double d0 = (double)v[i][0] - pose.t[0], d1 = (double)v[i][1] - pose.t[1], d2 = (double)v[i][2] - pose.t[2];
+        const float s0 = (float)((pose.R[0] * d0 + pose.R[3] * d1) + pose.R[6] * d2);   // R^T d, rounded once
+        const float s1 = (float)((pose.R[1] * d0 + pose.R[4] * d1) + pose.R[7] * d2);
+        const float s2 = (float)((pose.R[2] * d0 + pose.R[5] * d1) + pose.R[8] * d2);
+        int row, col;
+        float rm;
+        bool remove = false;
+        if (seg_detail::range_project(s0, s1, s2, sensor, &row, &col, &rm) && !(rm > opt.max_range) && img[(size_t)row * H + col] < inf) {
+          float r_min = inf;
+          for (int rr = std::max(0, row - opt.window_rows); rr <= std::min(N - 1, row + opt.window_rows); ++rr)   // rows do not wrap
+            for (int dc = -opt.window_cols; dc <= opt.window_cols; ++dc)
+              r_min = std::min(r_min, img[(size_t)rr * H + (size_t)(((col + dc) % H + H) % H)]);                  // columns wrap
+          ++st.points_tested;
+          const float margin = std::fmax(opt.margin_abs, opt.margin_rel * r_min);
+          remove = rm < r_min - margin;
+        }
+        if (remove) ++st.points_removed;
+        else v[w++] = v[i];
+      }
+      v.resize(w);
+      if (v.empty()) { it = map_.erase(it); ++st.voxels_emptied; }
+      else ++it;
+    }
+    return st;
+  }
   Cloud GetMap() const {
     Cloud out;
     for (const auto& kv : map_) out.insert(out.end(), kv.second.begin(), kv.second.end());
@@ -459,6 +522,19 @@ class DeviceVoxelMap {
   }
   void AddPointCloudDevice(const float* dev_xyz, int64_t n, const Pose3& pose) {   // float32 rows already in HBM (DevicePrep)
     chk(svnicp_map_add_cloud(m_, dev_xyz, n, SVNICP_MEM_DEVICE, pose.R.data(), pose.t.data()));
+  }
+  // visibility-based clearing (svnicp_map_clear_seen_through) with a scan on the host / already in HBM
+  svnicp_visibility_stats ClearSeenThrough(const Cloud& scan, const Pose3& pose, const svnicp_seg_params& sensor, const svnicp_visibility_opt& opt) {
+    svnicp_visibility_stats st{};
+    chk(svnicp_map_clear_seen_through(m_, scan.empty() ? nullptr : &scan[0][0], (int64_t)scan.size(), SVNICP_MEM_HOST, pose.R.data(), pose.t.data(),
+                                      &sensor, &opt, &st));
+    return st;
+  }
+  svnicp_visibility_stats ClearSeenThroughDevice(const float* dev_xyz, int64_t n, const Pose3& pose, const svnicp_seg_params& sensor,
+                                                 const svnicp_visibility_opt& opt) {
+    svnicp_visibility_stats st{};
+    chk(svnicp_map_clear_seen_through(m_, dev_xyz, n, SVNICP_MEM_DEVICE, pose.R.data(), pose.t.data(), &sensor, &opt, &st));
+    return st;
   }
   // -> number of points; the rows are at points_devptr()
   int64_t GetMap(const Pose3& pose, double max_range) { int64_t n = 0; chk(svnicp_map_query(m_, pose.t.data(), max_range, &n)); return n; }
@@ -601,6 +677,12 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   int mode_max = 8;                  // with the links: modes reported in full (1..SVNICP_MODES_MAX)
   bool mode_select_heaviest = false; // the correction is the first mode's mean instead of the global mean, and the pose, the
                                      // evaluate, the information and the map update follow it; needs the links
+  // clear_seen_through: after every successful registration the map points the cropped scan sees through at the result pose are
+  // dropped (ClearSeenThrough, sensor = seg_params) right before the map update, count in ScanResult::cleared; off: no call
+  bool clear_seen_through = false;
+  int clear_window_rows = 1, clear_window_cols = 1;         // the pixel window the minimum is taken over (0..4, 0..8)
+  double clear_margin_abs = 0.3, clear_margin_rel = 0.02;   // m, ratio of the range
+  double clear_max_range = 0.0;                             // map points farther than this from the sensor are left alone; 0 = max_range
 };
 
 struct ScanResult {
@@ -616,6 +698,7 @@ struct ScanResult {
   int64_t plane_inliers = -1;
   std::optional<svnicp_information> information;   // cfg.information != "off": H, b, eigen-structure, rank, step, cov at the result pose
   std::optional<svnicp_modes> modes;               // cfg.mode_link_*: the modes of the final particle set, heaviest first
+  int64_t cleared = -1;                            // cfg.clear_seen_through: map points the scan saw through and the map dropped
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -645,6 +728,12 @@ class RegistrationPipeline {
       throw std::invalid_argument("PipelineConfig: mode_link must be (link_trans, link_rot), both finite and >= 0");
     if (mode_link && !(cfg.mode_max >= 1 && cfg.mode_max <= SVNICP_MODES_MAX)) throw std::invalid_argument("PipelineConfig: mode_max must lie in 1..32");
     if (cfg.mode_select_heaviest && !mode_link) throw std::invalid_argument("PipelineConfig: mode_select \"heaviest\" needs mode_link (the modes are what it selects from)");
+    if (cfg.clear_seen_through) {
+      clear_opt_ = svnicp_visibility_opt{(int32_t)sizeof(svnicp_visibility_opt), cfg.clear_window_rows, cfg.clear_window_cols, (float)cfg.clear_margin_abs,
+                                         (float)cfg.clear_margin_rel, (float)(cfg.clear_max_range > 0 ? cfg.clear_max_range : cfg.max_range)};
+      if (!(std::isfinite(cfg.clear_max_range) && cfg.clear_max_range >= 0)) throw std::invalid_argument("PipelineConfig: clear_max_range must be finite and >= 0 (0 = max_range)");
+      VoxelHashMap(1.0, 1.0, 1).ClearSeenThrough(Cloud{}, Pose3{}, cfg.seg_params, clear_opt_);   // validates sensor and options (throws)
+    }
     if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
     if (cfg.gpu_map) dmap_ = std::make_unique<DeviceVoxelMap>(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points, cfg.device);
     if (cfg.gpu_map && cfg.gpu_prep) dprep_ = std::make_unique<DevicePrep>(cfg.device);
@@ -760,6 +849,11 @@ class RegistrationPipeline {
       if (cfg_.information != "off")   // what a filter or a gate may read; no policy here either
         res.information = solver_->information(cfg_.information == "plane" ? SVNICP_INFO_PLANE : SVNICP_INFO_POINT, cfg_.info_huber);
     }
+    if (cfg_.clear_seen_through) {   // no policy here either: every registered scan clears, with the densest cloud the step has
+      if (dprep_) res.cleared = dmap_->ClearSeenThroughDevice(dprep_->cropped(), dprep_->n_cropped, res.pose, cfg_.seg_params, clear_opt_).points_removed;
+      else if (dmap_) { res.cleared = dmap_->ClearSeenThrough(cropped, res.pose, cfg_.seg_params, clear_opt_).points_removed; bytes_h2d_ += cropped.size() * 12; }
+      else res.cleared = map_.ClearSeenThrough(cropped, res.pose, cfg_.seg_params, clear_opt_).points_removed;
+    }
     // … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is updated
     // with the same points the solver registered
     if (dprep_) dmap_->AddPointCloudDevice(dprep_->source_f32(), dprep_->n_source, res.pose);          // :630
@@ -793,6 +887,7 @@ class RegistrationPipeline {
   }
 
   PipelineConfig cfg_;
+  svnicp_visibility_opt clear_opt_{};
   VoxelHashMap map_;
   std::vector<Pose3> poses_;
   std::vector<double> times_;

@@ -316,9 +316,10 @@ def _c_round(v):
     return t + np.where(np.abs(v - t) >= 0.5, np.sign(v), 0.0)
 
 
-def _seg_project(points, prm: SegParams):
-    """copyPointCloud + projectPointCloud (:240, :281-325) -> owner image (int64 [N·H], -1 = empty) and the float32 ranges
-    of all points."""
+def _range_project(points, prm: SegParams):
+    """projectPointCloud's per-point part (:240, :281-325) for float32 [n,3] points -> (takes part bool [n], row int64 [n],
+    column int64 [n], range float32 [n]); row / column are 0 where the point takes no part.  The one statement of the
+    projection on the host: segment_images and VoxelHashMap.clear_seen_through both go through it."""
     p = np.asarray(points, np.float32).reshape(-1, 3)
     N, H = int(prm.n_scan), int(prm.horizon_scan)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
@@ -333,10 +334,18 @@ def _seg_project(points, prm: SegParams):
         col = np.where(col >= H, col - H, col)
         col_ok = (col >= 0) & (col < H)
         rng = np.sqrt((x * x + y * y) + z * z)
-        keep = finite & row_ok & col_ok & (rng >= _F32(prm.min_range))
+        keep = finite & row_ok & col_ok & ~(rng < _F32(prm.min_range))
+    return keep, np.where(keep, row, 0), np.where(keep, col, 0).astype(np.int64), rng
+
+
+def _seg_project(points, prm: SegParams):
+    """copyPointCloud + projectPointCloud (:240, :281-325) -> owner image (int64 [N·H], -1 = empty) and the float32 ranges
+    of all points."""
+    N, H = int(prm.n_scan), int(prm.horizon_scan)
+    keep, row, col, rng = _range_project(points, prm)
     owner = np.full(N * H, -1, np.int64)
     idx = np.flatnonzero(keep)
-    pix = row[idx] * H + np.where(col_ok, col, 0).astype(np.int64)[idx]
+    pix = row[idx] * H + col[idx]
     np.maximum.at(owner, pix, idx)                                                    # the last point in input order wins
     return owner, rng
 
@@ -452,6 +461,66 @@ def transform_f32(cloud, T) -> np.ndarray:
     return out
 
 
+VISIBILITY_STATS = ("pixels_filled", "points_tested", "points_removed", "voxels_emptied")   # struct svnicp_visibility_stats
+
+
+def check_visibility_options(sensor: SegParams, window, margin, max_range):
+    """The refusals of svnicp_map_clear_seen_through -> (window_rows, window_cols, margin_abs, margin_rel, max_range), the three
+    floats as float32."""
+    N, H = int(sensor.n_scan), int(sensor.horizon_scan)
+    if not (1 <= N <= 128 and H >= 1 and N * H <= 1 << 19):
+        raise ValueError("clear_seen_through: need 1 <= n_scan <= 128, horizon_scan >= 1 and n_scan * horizon_scan <= 2^19")
+    if not (np.isfinite(sensor.ang_res_x) and sensor.ang_res_x > 0 and np.isfinite(sensor.ang_res_y) and sensor.ang_res_y > 0
+            and np.isfinite(sensor.ang_bottom) and np.isfinite(sensor.min_range)):
+        raise ValueError("clear_seen_through: ang_res_x / ang_res_y must be finite and positive, ang_bottom / min_range finite")
+    if len(tuple(window)) != 2 or len(tuple(margin)) != 2:
+        raise ValueError("clear_seen_through: window is (rows, cols), margin is (abs, rel)")
+    wr, wc = int(window[0]), int(window[1])
+    if wr != window[0] or wc != window[1] or not (0 <= wr <= 4 and 0 <= wc <= 8):
+        raise ValueError("clear_seen_through: window rows must be 0..4 and window cols 0..8")
+    with np.errstate(over="ignore"):
+        ma, mr, rmax = _F32(margin[0]), _F32(margin[1]), _F32(max_range)
+    if not (np.isfinite(ma) and ma >= 0 and np.isfinite(mr) and mr >= 0):
+        raise ValueError("clear_seen_through: margins must be finite and >= 0")
+    if not (np.isfinite(rmax) and rmax > 0):
+        raise ValueError("clear_seen_through: max_range must be finite and > 0")
+    return wr, wc, ma, mr, rmax
+
+
+def visibility_image(scan, sensor: SegParams) -> np.ndarray:
+    """The minimum-range image of a scan: float32 [n_scan, horizon_scan], +inf = empty; a pixel keeps the smallest range of the
+    points projectPointCloud puts into it (the conservative choice for a rule that deletes; order-independent)."""
+    N, H = int(sensor.n_scan), int(sensor.horizon_scan)
+    keep, row, col, rng = _range_project(scan, sensor)
+    img = np.full(N * H, np.inf, np.float32)
+    np.minimum.at(img, (row * H + col)[keep], rng[keep])
+    return img.reshape(N, H)
+
+
+def visibility_test(map_points, pose, img, sensor: SegParams, wr: int, wc: int, margin_abs, margin_rel, max_range):
+    """The per-point rule of clear_seen_through for float32 map points [m,3] -> (reached the comparison bool [m], removed bool
+    [m])."""
+    N, H = img.shape
+    T = np.asarray(pose, float)
+    R, t = T[:3, :3], T[:3, 3]
+    d = np.asarray(map_points, np.float32).astype(np.float64) - t[None, :]
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = np.stack([((R[0, c] * d[:, 0] + R[1, c] * d[:, 1]) + R[2, c] * d[:, 2]).astype(np.float32) for c in range(3)], 1)   # Rᵀd
+        ok, row, col, rm = _range_project(s, sensor)
+        tested = ok & ~(rm > _F32(max_range)) & (img[row, col] < np.inf)
+        r_min = np.full(rm.shape[0], np.inf, np.float32)
+        for dr in range(-wr, wr + 1):
+            rr = row + dr
+            inside = (rr >= 0) & (rr < N)                                             # rows do not wrap
+            rr = np.clip(rr, 0, N - 1)
+            for dc in range(-wc, wc + 1):
+                v = np.where(inside, img[rr, (col + dc) % H], _F32(np.inf))           # columns wrap
+                r_min = np.minimum(r_min, v)
+        r_min = np.where(tested, r_min, _F32(0))
+        remove = tested & (rm < r_min - np.maximum(_F32(margin_abs), _F32(margin_rel) * r_min))
+    return tested, remove
+
+
 class DeviceVoxelHashMap:
     """The same map resident in HBM (svnicp_map_* of the C ABI, csrc/voxel_map.hip): ``add_pointcloud`` uploads only the new
     points, ``get_map`` leaves the selected points in device memory as float64 rows and returns (device pointer, count) for
@@ -468,6 +537,7 @@ class DeviceVoxelHashMap:
         if rc != 0:
             raise binding.SvnIcpError(f"svnicp_map_create failed ({rc}): {self._L.svnicp_map_last_error(None).decode()}")
         self.bytes_uploaded = 0
+        self._max_range = float(max_range)
 
     def _chk(self, rc, what):
         if rc != 0:
@@ -526,6 +596,34 @@ class DeviceVoxelHashMap:
         dp = C.POINTER(C.c_double)
         self._chk(self._L.svnicp_map_add_cloud(self._h, C.c_void_p(int(devptr)), int(n), 1, R.ctypes.data_as(dp), t.ctypes.data_as(dp)),
                   "svnicp_map_add_cloud")
+
+    def clear_seen_through(self, scan, pose, sensor: SegParams, window=(1, 1), margin=(0.3, 0.02), max_range: float | None = None) -> dict:
+        """Drop the stored points the scan (sensor frame, at ``pose``) sees through (svnicp_map_clear_seen_through; the rule is
+        VoxelHashMap.clear_seen_through's) -> the call's statistics.  ``max_range`` None = the map's own."""
+        pts = np.ascontiguousarray(np.asarray(scan, np.float32)[:, :3])
+        self.bytes_uploaded += pts.nbytes
+        return self._clear_seen_through(pts.ctypes.data_as(self._C.c_void_p), pts.shape[0], 0, pose, sensor, window, margin, max_range)
+
+    def clear_seen_through_device(self, devptr: int, n: int, pose, sensor: SegParams, window=(1, 1), margin=(0.3, 0.02),
+                                  max_range: float | None = None) -> dict:
+        """clear_seen_through for float32 rows that already live in HBM (DevicePreprocessor.cropped_ptr)."""
+        return self._clear_seen_through(self._C.c_void_p(int(devptr)), int(n), 1, pose, sensor, window, margin, max_range)
+
+    def _clear_seen_through(self, ptr, n, mem, pose, sensor, window, margin, max_range):
+        from . import binding
+        C = self._C
+        T = np.asarray(pose, float)
+        R = np.ascontiguousarray(T[:3, :3]).reshape(9)
+        t = np.ascontiguousarray(T[:3, 3])
+        dp = C.POINTER(C.c_double)
+        prm = seg_params_struct(sensor)
+        mr = self._max_range if max_range is None else max_range
+        opt = binding.VisibilityOptStruct(C.sizeof(binding.VisibilityOptStruct), int(window[0]), int(window[1]), float(margin[0]),
+                                          float(margin[1]), float(mr))
+        st = binding.VisibilityStatsStruct()
+        self._chk(self._L.svnicp_map_clear_seen_through(self._h, ptr, n, mem, R.ctypes.data_as(dp), t.ctypes.data_as(dp), C.byref(prm),
+                                                        C.byref(opt), C.byref(st)), "svnicp_map_clear_seen_through")
+        return {k: int(getattr(st, k)) for k in VISIBILITY_STATS}
 
     def get_map(self, pose=None, max_range: float | None = None):
         """-> (device pointer of float64 [M][3], M)"""
@@ -850,6 +948,39 @@ class VoxelHashMap:
         for k in far:
             del self._vox[k]
 
+    def clear_seen_through(self, scan, pose, sensor: SegParams, window=(1, 1), margin=(0.3, 0.02), max_range: float | None = None) -> dict:
+        """Visibility-based clearing (include/svnicp_hip.h: svnicp_map_clear_seen_through): a stored point is
+        deleted when the scan's beam in its direction returned from clearly behind it.  ``scan`` float32 [n,3] in the sensor
+        frame, ``pose`` 4x4 map <- sensor, ``sensor`` the range-image geometry, ``window`` (rows, cols) the pixel window the
+        minimum is taken over, ``margin`` (abs m, rel), ``max_range`` None = the map's own.  Stored point p: d = double(p) − t,
+        s = float(Rᵀd) summed left to right, projected like a scan point; kept when it does not project, r_m > max_range or its
+        own pixel is empty; else removed iff r_m < r_min − max(margin_abs, margin_rel·r_min) in float32.  Survivors keep their
+        order, so the next survivor becomes the voxel's first point; an emptied voxel disappears.  -> statistics."""
+        opt = check_visibility_options(sensor, window, margin, self.max_range if max_range is None else max_range)
+        stats = dict.fromkeys(VISIBILITY_STATS, 0)
+        pts = np.asarray(scan, np.float32).reshape(-1, 3)
+        if pts.shape[0] == 0 or not self._vox:
+            return stats
+        img = visibility_image(pts, sensor)
+        stats["pixels_filled"] = int(np.count_nonzero(img < np.inf))
+        keys = list(self._vox)
+        sizes = np.array([len(self._vox[k]) for k in keys])
+        P = np.concatenate([np.asarray(self._vox[k], np.float32).reshape(-1, 3) for k in keys], 0)
+        tested, remove = visibility_test(P, pose, img, sensor, *opt)
+        stats["points_tested"] = int(np.count_nonzero(tested))
+        stats["points_removed"] = int(np.count_nonzero(remove))
+        ends = np.cumsum(sizes)
+        hit = np.add.reduceat(remove.astype(np.int64), ends - sizes)
+        for v in np.flatnonzero(hit).tolist():
+            a, b = int(ends[v] - sizes[v]), int(ends[v])
+            left = [q for q, r in zip(self._vox[keys[v]], remove[a:b]) if not r]
+            if left:
+                self._vox[keys[v]] = left
+            else:
+                del self._vox[keys[v]]
+                stats["voxels_emptied"] += 1
+        return stats
+
     def get_map(self, pose=None, max_range: float | None = None) -> np.ndarray:
         if not self._vox:
             return np.zeros((0, 3))
@@ -907,8 +1038,17 @@ class PipelineConfig:
     mode_link: tuple | None = None  # (link_trans m, link_rot rad): after every registration the particles are grouped into modes (svnicp_particle_modes) in ScanResult.modes; None = off, no call is made
     mode_max: int = 8              # with mode_link: modes reported in full (1..32)
     mode_select: str = "mean"      # "heaviest": the correction is the first mode's mean instead of the global mean, and the pose, the evaluate, the information and the map update follow it; needs mode_link
+    clear_seen_through: tuple | None = None   # (window_rows, window_cols, margin_abs m, margin_rel): after every successful registration the map points the cropped scan sees through at the result pose are dropped (clear_seen_through, sensor = seg_params) right before the map update, count in ScanResult.cleared; None = off, no call is made
+    clear_max_range: float = 0.0   # with clear_seen_through: map points farther than this from the sensor are left alone; 0 = max_range
 
     def __post_init__(self):
+        if self.clear_seen_through is not None:
+            if len(tuple(self.clear_seen_through)) != 4:
+                raise ValueError("PipelineConfig: clear_seen_through must be (window_rows, window_cols, margin_abs, margin_rel)")
+            if not (np.isfinite(self.clear_max_range) and self.clear_max_range >= 0):
+                raise ValueError("PipelineConfig: clear_max_range must be finite and >= 0 (0 = max_range)")
+            w0, w1, m0, m1 = self.clear_seen_through
+            check_visibility_options(self.seg_params, (w0, w1), (m0, m1), self.clear_max_range or self.max_range)
         if self.mode_select not in ("mean", "heaviest"):
             raise ValueError('PipelineConfig: mode_select must be "mean" or "heaviest"')
         if self.mode_link is not None:
@@ -954,6 +1094,7 @@ class ScanResult:
     plane_inliers: int | None = None
     information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
     modes: object | None = None              # cfg.mode_link: solver.ParticleModes of the final particle set, heaviest first
+    cleared: int | None = None               # cfg.clear_seen_through: map points the scan saw through and the map dropped
 
 
 class RegistrationPipeline:
@@ -1071,6 +1212,15 @@ class RegistrationPipeline:
                 res.plane_rmse, res.plane_inliers = ev.plane_rmse, ev.plane_inliers
             if c.information != "off":   # what a filter or a gate may read; no policy here either
                 res.information = s.information(c.information, c.info_huber)
+        if c.clear_seen_through is not None:   # no policy here either: every registered scan clears, with the densest cloud the step has
+            w0, w1, m0, m1 = c.clear_seen_through
+            args = (pose, c.seg_params, (w0, w1), (m0, m1), c.clear_max_range or c.max_range)
+            if dev:
+                res.cleared = self.map.clear_seen_through_device(self._prep.cropped_ptr, self._prep.n_cropped, *args)["points_removed"]
+            else:
+                res.cleared = self.map.clear_seen_through(cropped, *args)["points_removed"]
+                if c.gpu_map:
+                    self.bytes_h2d += cropped.shape[0] * 12
         # … and at :630 *voxelized_cloud_toMap holds the 1.5-voxel sampling (the second in-place filter, :560): the map is
         # updated with the same points the solver registered
         if dev:
