@@ -556,6 +556,46 @@ void *svnicp_map_normals_devptr(svnicp_map *map);      /* double [count][3], row
                                                           stream-ordered: synchronise the context (svnicp_align does) before the
                                                           next query / add_cloud / clear, which invalidate the rows (NULL then) */
 int svnicp_map_download_normals(svnicp_map *map, double *out_xyz, int64_t cap_points, int64_t *n_out);   /* test tap */
+/* ---- score candidate poses against the map (an extension: the reference starts every registration at the constant-velocity
+ * prediction and has no way to look for a better start) ------------------------------------------
+ * svnicp_map_score_poses(map, src_xyz, n, src_mem_kind, posesCx12, C, poses_mem_kind, max_corr_dist, outCx4): how well do the
+ * n rows of a scan fit the map at each of C poses, straight from the hash table -- no target cloud, no candidate table.
+ *   poses        posesCx12 holds 12 doubles per pose, R row-major then t, map <- sensor: the layout of svnicp_score_particles'
+ *                posesPx12.  Host or device memory (poses_mem_kind); src_xyz is n x 3 float32 in the sensor frame, host or
+ *                device (src_mem_kind).
+ *   transformed  exactly svnicp_map_add_cloud's: c[d] = (float)(((R[3d]*(double)p0 + R[3d+1]*(double)p1) + R[3d+2]*(double)p2)
+ *   point        + t[d]), formed in float64 from the widened float32 row, left to right, rounded ONCE to float32.
+ *   voxel        truncf(c[d] / (float)voxel_size) per axis, valid in [-2^20, 2^20); otherwise the row is not located -- also for
+ *                NaN and inf, hence for every row of a pose with a non-finite entry.  A non-finite pose is never an error: its
+ *                record is {0, 0, 0, thr2}.
+ *   candidates   all points the map stores in the 3 x 3 x 3 block of voxels around that voxel.  Voxel indices outside +-2^20 do
+ *                not exist; per-voxel counts are clamped to [0, max_points]; the table is only read: probing is bounded, goes on
+ *                past a removed voxel's slot and stops at an empty one.
+ *   distance     d2 = ((dx*dx) + dy*dy) + dz*dz in float64, dx = (double)stored - (double)c; dmin2 the minimum over the
+ *                candidates.
+ *   classes      a row is located iff its voxel is valid and its block holds at least one stored point; an inlier iff located
+ *                and dmin2 < thr2, thr2 = max_corr_dist * max_corr_dist computed once in float64, the comparison strict.
+ *   sums         sum_d2 runs over the inliers; cost = (sum_d2 + (n - inliers) * thr2) / n, the mean truncated squared distance
+ *                of svnicp_score_particles, so costs of the two calls read alike.
+ *   gate         max_corr_dist must be finite, > 0 and <= voxel_size, otherwise SVNICP_ERR_INVALID.  Up to that size the nearest
+ *                point of the block is the nearest point of the whole map -- except for a stored point whose float32 quotient
+ *                coordinate / voxel_size rounded across a voxel boundary, which sits one voxel further than its coordinates say.
+ *                The contract itself is the block; that is why the result is exact.
+ *   out          outCx4 (host, may be NULL: read svnicp_map_scores_devptr), per pose {located, inliers, sum_d2, cost}; the
+ *                counts are exact integers held in doubles.
+ *   determinism  no atomics: each workgroup owns a fixed range of 256 rows of one pose and the partial records are added in an
+ *                order that depends on n alone.  The record of a pose has the same bits whether it is scored alone or in a
+ *                batch of any C, with rows and poses on the host or on the device, and the same bits on every call.
+ *   limits       0 <= n <= 2^31-1, 1 <= C <= 2^20.  n == 0 gives {0, 0, 0, thr2} for every pose.  An empty map is not an error:
+ *                nothing is located.
+ *   side         none on the map: svnicp_map_size and svnicp_map_table_info are unchanged, the rows of an earlier
+ *   effects      svnicp_map_query and its normals stay valid (the call has its own buffers, svnicp_map_query_normals is still
+ *                accepted), and a following svnicp_map_add_cloud leaves the map bit for bit that of a map that never scored.
+ *   completion   returns with the map's stream synchronised and outCx4 filled. */
+#define SVNICP_MAP_SCORE_FIELDS 4   /* per pose: {located, inliers, sum_d2, cost}; counts are exact integers held in doubles */
+int svnicp_map_score_poses(svnicp_map *map, const float *src_xyz, int64_t n, int src_mem_kind, const double *posesCx12, int64_t C,
+                           int poses_mem_kind, double max_corr_dist, double *outCx4 /* host */);
+void *svnicp_map_scores_devptr(svnicp_map *map);   /* double [C][4] of the last scoring, NULL before one */
 
 /* ---- test-only taps (parity tests; not part of the reference interface) -------------------- */
 int svnicp_get_candidates(svnicp_ctx *ctx, int32_t *outBK);          /* sourceKNN_idx_  SVGDICP.cpp:214 */

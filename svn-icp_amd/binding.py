@@ -146,6 +146,9 @@ def load_library():
     L.svnicp_map_download_normals.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64)]
     L.svnicp_map_clear_seen_through.argtypes = [vp, vp, C.c_int64, C.c_int, dp, dp, C.POINTER(SegParamsStruct),
                                                 C.POINTER(VisibilityOptStruct), C.POINTER(VisibilityStatsStruct)]
+    L.svnicp_map_score_poses.argtypes = [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_double, dp]
+    L.svnicp_map_scores_devptr.argtypes = [vp]
+    L.svnicp_map_scores_devptr.restype = vp
     L.svnicp_prep_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.svnicp_prep_destroy.argtypes = [vp]
     L.svnicp_prep_destroy.restype = None

@@ -34,21 +34,19 @@
 #include "../../include/svnicp_hip.h"
 #include "device_buffer.hpp"
 #include "kernels.hpp"
+#include "map_score.hpp"
 #include "plane_normal_device.hpp"
 #include "range_project_device.hpp"
+#include "voxel_table_device.hpp"
 
 namespace {
 
-constexpr unsigned long long kEmpty = ~0ull;
-constexpr unsigned long long kTomb = ~0ull - 1ull;
-constexpr int kOff = 1 << 20;  // voxel indices in [-2^20, 2^20)
-
-__device__ __forceinline__ unsigned long long hash_key(unsigned long long k) {  // splitmix64 finaliser
-  k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27; k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return k;
-}
+// the table's key packing, hash and read-only lookup: voxel_table_device.hpp
+using svnicp::kEmpty;
+using svnicp::kTomb;
+using svnicp::kOff;
+using svnicp::hash_key;
+using svnicp::pack_key;
 
 struct MapPose { double R[9]; double t[3]; };
 
@@ -76,8 +74,7 @@ __global__ __launch_bounds__(256) void k_map_locate(const float* __restrict__ in
     v[d] = ok ? (long long)f : 0;
   }
   if (!ok) { slot_of[i] = 0xffffffffu; atomicAdd(&stats[3], 1); return; }   // outside the index range or NaN: counted, not stored
-  const unsigned long long key = ((unsigned long long)(v[0] + kOff) << 42) | ((unsigned long long)(v[1] + kOff) << 21) |
-                                 (unsigned long long)(v[2] + kOff);
+  const unsigned long long key = pack_key(v[0], v[1], v[2]);
   unsigned long long h = hash_key(key) & (unsigned long long)(cap - 1);
   for (int64_t probe = 0; probe < cap; ++probe) {   // bounded: a full table ends the loop and is reported
     unsigned long long cur = keys[h];
@@ -338,16 +335,9 @@ __global__ __launch_bounds__(64) void k_map_normals(const unsigned long long* __
     int c = 0;
     if (lane == 13) {   // the voxel itself: its slot is the query's
       slot = sslot[j]; c = counts[slot];
-    } else if (v0 >= -kOff && v0 < kOff && v1 >= -kOff && v1 < kOff && v2 >= -kOff && v2 < kOff) {   // outside: no such voxel
-      const unsigned long long nk = ((unsigned long long)(v0 + kOff) << 42) | ((unsigned long long)(v1 + kOff) << 21) |
-                                    (unsigned long long)(v2 + kOff);
-      unsigned long long h = hash_key(nk) & (unsigned long long)(cap - 1);
-      for (int64_t probe = 0; probe < cap; ++probe) {   // bounded; the table is only read
-        const unsigned long long cur = keys[h];
-        if (cur == nk) { slot = (unsigned int)h; c = counts[h]; break; }
-        if (cur == kEmpty) break;
-        h = (h + 1) & (unsigned long long)(cap - 1);
-      }
+    } else if (svnicp::voxel_in_range(v0, v1, v2)) {   // outside: no such voxel
+      const int64_t h = svnicp::find_slot(keys, cap, pack_key(v0, v1, v2));   // bounded; the table is only read
+      if (h >= 0) { slot = (unsigned int)h; c = counts[h]; }
     }
     s_slot[lane] = slot;
     s_cnt[lane] = c < 0 ? 0 : (c > max_points ? max_points : c);
@@ -539,6 +529,11 @@ struct svnicp_map {
   GrowBuf<unsigned char> tmp;
   GrowBuf<unsigned int> vis_img;           // svnicp_map_clear_seen_through: the minimum-range image (float bit patterns)
   GrowBuf<unsigned long long> vis_stats;   // ... and its four statistics
+  // svnicp_map_score_poses: its own rows, poses, chunk records and results (the query's buffers are not touched)
+  GrowBuf<float> sc_in;
+  GrowBuf<double> sc_poses, sc_psum, sc_out;
+  GrowBuf<unsigned int> sc_pcnt;
+  int64_t sc_C = 0;      // poses of the last scoring (0 before one)
   int64_t last_M = 0;
   // svnicp_map_query_normals: the last query's selection (sel_key2 / sel_off / sel_cnt over last_live entries) still describes
   // the table — set by svnicp_map_query, dropped by svnicp_map_add_cloud, svnicp_map_clear_seen_through and svnicp_map_clear
@@ -861,6 +856,45 @@ int svnicp_map_download_normals(svnicp_map* m, double* out_xyz, int64_t cap_poin
   }
   return SVNICP_OK;
 }
+
+int svnicp_map_score_poses(svnicp_map* m, const float* src_xyz, int64_t n, int src_mem_kind, const double* posesCx12, int64_t C,
+                           int poses_mem_kind, double max_corr_dist, double* outCx4) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (n < 0 || n > 0x7fffffffLL || (n > 0 && !src_xyz))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_score_poses: need 0 <= n <= 2^31-1 and rows for n > 0");
+  if (!posesCx12 || C < 1 || C > ((int64_t)1 << 20))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_score_poses: need poses and 1 <= C <= 2^20");
+  if (!(std::isfinite(max_corr_dist) && max_corr_dist > 0.0 && max_corr_dist <= m->voxel))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_score_poses: max_corr_dist must be finite, > 0 and <= voxel_size (the 3x3x3 block "
+                                       "holds the nearest point only up to that gate)");
+  HIPCHK(m, hipSetDevice(m->device));
+  const double thr2 = max_corr_dist * max_corr_dist;
+  const float* din = src_xyz;
+  if (n > 0 && src_mem_kind != SVNICP_MEM_DEVICE) {
+    HIPCHK(m, m->sc_in.ensure((size_t)n * 3));
+    HIPCHK(m, hipMemcpyAsync(m->sc_in.p, src_xyz, (size_t)n * 12, hipMemcpyHostToDevice, m->stream));
+    din = m->sc_in.p;
+  }
+  const double* dposes = posesCx12;
+  if (poses_mem_kind != SVNICP_MEM_DEVICE) {
+    HIPCHK(m, m->sc_poses.ensure((size_t)C * 12));
+    HIPCHK(m, hipMemcpyAsync(m->sc_poses.p, posesCx12, (size_t)C * 96, hipMemcpyHostToDevice, m->stream));
+    dposes = m->sc_poses.p;
+  }
+  const int64_t chunks = svnicp::map_score_chunks(n);
+  const size_t recs = (size_t)(C < svnicp::kScorePoseBatch ? C : svnicp::kScorePoseBatch) * (size_t)chunks;
+  m->sc_C = 0;
+  HIPCHK(m, m->sc_out.ensure((size_t)C * SVNICP_MAP_SCORE_FIELDS));
+  HIPCHK(m, m->sc_pcnt.ensure(2 * recs)); HIPCHK(m, m->sc_psum.ensure(recs));
+  const svnicp::MapTableView T{m->keys.p, m->counts.p, m->pts.p, m->cap, m->max_points, (float)m->voxel};
+  HIPCHK(m, svnicp::launch_map_score(T, din, n, dposes, C, thr2, m->sc_pcnt.p, m->sc_psum.p, m->sc_out.p, m->stream));
+  if (outCx4) HIPCHK(m, hipMemcpyAsync(outCx4, m->sc_out.p, (size_t)C * SVNICP_MAP_SCORE_FIELDS * 8, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));   // complete when the call returns: the caller's rows and poses are free again
+  m->sc_C = C;
+  return SVNICP_OK;
+}
+
+void* svnicp_map_scores_devptr(svnicp_map* m) { return m && m->sc_C > 0 ? (void*)m->sc_out.p : nullptr; }
 
 void* svnicp_map_points_devptr(svnicp_map* m) { return m ? (void*)m->out.p : nullptr; }
 

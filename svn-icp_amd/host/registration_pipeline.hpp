@@ -30,6 +30,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "svnicp_hip_shim.hpp"
@@ -477,6 +478,59 @@ class VoxelHashMap {
     }
     return st;
   }
+  // how well the scan `rows` (sensor frame) fits the map at each of C poses (poses12: [C][12], R row-major then t, map <- sensor)
+  // -> [C][4] {located, inliers, sum_d2, cost}: include/svnicp_hip.h's svnicp_map_score_poses restated, the float32 / float64
+  // steps and the order of the sums (rows ascending, from 0.0) those of pipeline.py's VoxelHashMap.score_poses.  Throws
+  // std::invalid_argument where the C call answers SVNICP_ERR_INVALID.
+  std::vector<double> ScorePoses(const Cloud& rows, const std::vector<double>& poses12, double gate) const {
+    const size_t C = poses12.size() / 12;
+    if (poses12.size() % 12 != 0 || C < 1 || C > ((size_t)1 << 20)) throw std::invalid_argument("VoxelHashMap::ScorePoses: need 1 <= C <= 2^20 poses of 12 doubles");
+    if (!(std::isfinite(gate) && gate > 0 && gate <= voxel_size_))
+      throw std::invalid_argument("VoxelHashMap::ScorePoses: the gate must be finite, > 0 and <= voxel_size");
+    const double thr2 = gate * gate;
+    const float vs = (float)voxel_size_;
+    const int64_t lim = (int64_t)1 << 20, n = (int64_t)rows.size();
+    std::vector<double> out(4 * C, 0.0);
+    for (size_t ci = 0; ci < C; ++ci) {
+      const double* R = &poses12[12 * ci];
+      const double* t = R + 9;
+      int64_t located = 0, inliers = 0;
+      double sum = 0.0;
+      for (const auto& p : rows) {
+        float c[3];
+        int64_t v[3];
+        bool ok = true;
+        for (int d = 0; d < 3; ++d) {
+          c[d] = (float)(((R[3 * d] * (double)p[0] + R[3 * d + 1] * (double)p[1]) + R[3 * d + 2] * (double)p[2]) + t[d]);
+          const float f = std::trunc(c[d] / vs);
+          ok = ok && f >= (float)-lim && f < (float)lim;   // also false for NaN and inf
+          v[d] = ok ? (int64_t)f : 0;
+        }
+        if (!ok) continue;
+        bool have = false;
+        double best = 0.0;
+        for (int j = 0; j < 27; ++j) {
+          const Key w{v[0] + (j / 9 - 1), v[1] + ((j / 3) % 3 - 1), v[2] + (j % 3 - 1)};
+          if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || w[2] < -lim || w[2] >= lim) continue;   // no such voxel
+          const auto it = map_.find(w);
+          if (it == map_.end()) continue;
+          const size_t cnt = std::min(it->second.size(), (size_t)max_points_);
+          for (size_t k = 0; k < cnt; ++k) {
+            const auto& q = it->second[k];
+            const double dx = (double)q[0] - (double)c[0], dy = (double)q[1] - (double)c[1], dz = (double)q[2] - (double)c[2];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (!have || d2 < best) { best = d2; have = true; }
+          }
+        }
+        if (!have) continue;
+        ++located;
+        if (best < thr2) { ++inliers; sum += best; }
+      }
+      out[4 * ci] = (double)located; out[4 * ci + 1] = (double)inliers; out[4 * ci + 2] = sum;
+      out[4 * ci + 3] = n > 0 ? (sum + (double)(n - inliers) * thr2) / (double)n : thr2;
+    }
+    return out;
+  }
   Cloud GetMap() const {
     Cloud out;
     for (const auto& kv : map_) out.insert(out.end(), kv.second.begin(), kv.second.end());
@@ -551,6 +605,14 @@ class DeviceVoxelMap {
   // -> rows with a normal; the rows ([count][3], 0 = no normal) are at normals_devptr()
   int64_t QueryNormals(int normal_k) { int64_t n = 0; chk(svnicp_map_query_normals(m_, normal_k, &n)); return n; }
   const double* normals_devptr() { return static_cast<const double*>(svnicp_map_normals_devptr(m_)); }
+  // how well a scan fits the map at each of C poses (svnicp_map_score_poses; VoxelHashMap::ScorePoses is the host restatement)
+  // -> [C][4] {located, inliers, sum_d2, cost}; rows on the host / already in HBM (DevicePrep::source_f32)
+  std::vector<double> ScorePoses(const Cloud& rows, const std::vector<double>& poses12, double gate) {
+    return score(rows.empty() ? nullptr : &rows[0][0], (int64_t)rows.size(), SVNICP_MEM_HOST, poses12, gate);
+  }
+  std::vector<double> ScorePosesDevice(const float* dev_xyz, int64_t n, const std::vector<double>& poses12, double gate) {
+    return score(dev_xyz, n, SVNICP_MEM_DEVICE, poses12, gate);
+  }
   std::vector<double> download_normals() {   // test tap
     int64_t n = 0;
     chk(svnicp_map_download_normals(m_, nullptr, 0, &n));
@@ -560,9 +622,74 @@ class DeviceVoxelMap {
   }
 
  private:
+  std::vector<double> score(const float* xyz, int64_t n, int mem, const std::vector<double>& poses12, double gate) {
+    const int64_t C = (int64_t)(poses12.size() / 12);
+    std::vector<double> out((size_t)SVNICP_MAP_SCORE_FIELDS * (size_t)std::max<int64_t>(C, 0));
+    chk(svnicp_map_score_poses(m_, xyz, n, mem, poses12.data(), C, SVNICP_MEM_HOST, gate, out.data()));
+    return out;
+  }
   void chk(int rc) { if (rc != 0) throw std::runtime_error(svnicp_map_last_error(m_)); }
   svnicp_map* m_ = nullptr;
 };
+
+// ------------------------------------------------------------------------------------------------ search grid and seed
+// Candidates are CORRECTIONS in the solver's parametrisation [x, y, z, rx, ry, rz]: node x gives the pose
+// guess * correction_to_pose(x), which is how a particle's total pose is composed, so the best nodes can be handed to the solver
+// as particles unchanged.  The same helpers, with the same order of the nodes, are in pipeline.py.
+constexpr double kGridSlack = 1e-9;   // extent / step may miss an integer by a rounding: 10 deg / 2.5 deg is 4
+
+// Per axis the offsets are k * step, k = -m..m, m = floor(extent / step); extent 0 fixes the axis.  Lexicographic order, x
+// slowest; *zero_index is the node of the zero correction.  Throws std::invalid_argument for a negative or non-finite extent, a
+// step <= 0 on an axis with an extent, and more than 2^20 nodes.
+inline std::vector<std::array<double, 6>> correction_grid(const std::array<double, 6>& extent, const std::array<double, 6>& step, size_t* zero_index = nullptr) {
+  int64_t m[6];
+  size_t count = 1, zero = 0;
+  for (int d = 0; d < 6; ++d) {
+    if (!(std::isfinite(extent[d]) && extent[d] >= 0)) throw std::invalid_argument("correction_grid: extents must be finite and >= 0");
+    m[d] = 0;
+    if (extent[d] != 0.0) {
+      if (!(std::isfinite(step[d]) && step[d] > 0)) throw std::invalid_argument("correction_grid: an axis with a non-zero extent needs a finite step > 0");
+      m[d] = (int64_t)std::floor(extent[d] / step[d] + kGridSlack);
+    }
+    if (m[d] > ((int64_t)1 << 19)) throw std::invalid_argument("correction_grid: more than 2^20 nodes");
+    count *= (size_t)(2 * m[d] + 1);
+    if (count > ((size_t)1 << 20)) throw std::invalid_argument("correction_grid: more than 2^20 nodes");
+    zero = zero * (size_t)(2 * m[d] + 1) + (size_t)m[d];
+  }
+  std::vector<std::array<double, 6>> nodes(count);
+  for (size_t i = 0; i < count; ++i) {
+    size_t r = i;
+    for (int d = 5; d >= 0; --d) {
+      const int64_t w = 2 * m[d] + 1, k = (int64_t)(r % (size_t)w) - m[d];
+      r /= (size_t)w;
+      nodes[i][d] = (double)k * (m[d] ? step[d] : 0.0);
+    }
+  }
+  if (zero_index) *zero_index = zero;
+  return nodes;
+}
+
+// guess * correction_to_pose(x) per node -> [C][12], R row-major then t (svnicp_map_score_poses' layout)
+inline std::vector<double> correction_poses(const Pose3& guess, const std::vector<std::array<double, 6>>& nodes) {
+  std::vector<double> out(12 * nodes.size());
+  for (size_t i = 0; i < nodes.size(); ++i) {
+    const Pose3 T = guess * correction_to_pose(nodes[i]);
+    std::copy(T.R.begin(), T.R.end(), out.begin() + 12 * i);
+    std::copy(T.t.begin(), T.t.end(), out.begin() + 12 * i + 9);
+  }
+  return out;
+}
+
+// the indices of the P best nodes of a scoring ([C][4] records), ordered by (cost, index): ties in cost go to the lower index
+inline std::vector<size_t> seed_from_scores(const std::vector<double>& scores, size_t P) {
+  const size_t C = scores.size() / 4;
+  if (P < 1 || P > C) throw std::invalid_argument("seed_from_scores: need 1 <= P <= number of nodes");
+  std::vector<size_t> order(C);
+  std::iota(order.begin(), order.end(), (size_t)0);
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return scores[4 * a + 3] < scores[4 * b + 3]; });
+  order.resize(P);
+  return order;
+}
 
 // crop_pointcloud + the two uniform samplings on the device (svnicp_prep_*, csrc/scan_prep.hip): the raw scan is uploaded
 // once; the cropped cloud, the map cloud (float32) and the source cloud (float64 rows) stay in HBM
@@ -683,6 +810,12 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   int clear_window_rows = 1, clear_window_cols = 1;         // the pixel window the minimum is taken over (0..4, 0..8)
   double clear_margin_abs = 0.3, clear_margin_rel = 0.02;   // m, ratio of the range
   double clear_max_range = 0.0;                             // map points farther than this from the sensor are left alone; 0 = max_range
+  // seed_grid = (extent6, step6) of correction_grid: before every registration the scan's rows are scored against the map at the
+  // grid's nodes around the prediction (ScorePoses), result in ScanResult::seed; empty (the default) = off, no call is made
+  std::optional<std::pair<std::array<double, 6>, std::array<double, 6>>> seed_grid;
+  double seed_gate = 0.0;           // with seed_grid: the inlier gate of that scoring, at most map_voxel_size; 0 = map_voxel_size
+  std::string seed_mode = "best";   // "best": the initial mean becomes prediction * correction_to_pose(best node), the particles are
+                                    // drawn as ever; "top": the mean stays the prediction, the particles are the particle_count best nodes
 };
 
 struct ScanResult {
@@ -699,6 +832,14 @@ struct ScanResult {
   std::optional<svnicp_information> information;   // cfg.information != "off": H, b, eigen-structure, rank, step, cov at the result pose
   std::optional<svnicp_modes> modes;               // cfg.mode_link_*: the modes of the final particle set, heaviest first
   int64_t cleared = -1;                            // cfg.clear_seen_through: map points the scan saw through and the map dropped
+  struct Seed {
+    size_t index = 0;                      // the best node
+    double cost = 0, cost_zero = 0;        // its cost; the cost of the zero correction (the prediction)
+    std::array<double, 6> correction{};    // the correction applied to the initial mean ("top": zeros)
+    Pose3 prediction;                      // the constant-velocity prediction the grid is centred on
+    std::vector<size_t> nodes;             // "top": the nodes handed over as particles, best first
+  };
+  std::optional<Seed> seed;                        // cfg.seed_grid
 };
 
 // what the pipeline handed to the solver for one scan (test tap: the oracle is run on exactly these)
@@ -728,6 +869,14 @@ class RegistrationPipeline {
       throw std::invalid_argument("PipelineConfig: mode_link must be (link_trans, link_rot), both finite and >= 0");
     if (mode_link && !(cfg.mode_max >= 1 && cfg.mode_max <= SVNICP_MODES_MAX)) throw std::invalid_argument("PipelineConfig: mode_max must lie in 1..32");
     if (cfg.mode_select_heaviest && !mode_link) throw std::invalid_argument("PipelineConfig: mode_select \"heaviest\" needs mode_link (the modes are what it selects from)");
+    if (cfg.seed_mode != "best" && cfg.seed_mode != "top") throw std::invalid_argument("PipelineConfig: seed_mode must be \"best\" or \"top\"");
+    if (!(std::isfinite(cfg.seed_gate) && cfg.seed_gate >= 0 && cfg.seed_gate <= cfg.map_voxel_size))
+      throw std::invalid_argument("PipelineConfig: seed_gate must be finite, >= 0 (0 = map_voxel_size) and at most map_voxel_size");
+    if (cfg.seed_grid) {
+      seed_nodes_ = correction_grid(cfg.seed_grid->first, cfg.seed_grid->second, &seed_zero_);   // throws for a bad grid
+      if (cfg.seed_mode == "top" && seed_nodes_.size() < (size_t)cfg.particle_count)
+        throw std::invalid_argument("PipelineConfig: seed_mode \"top\" needs at least particle_count nodes in seed_grid");
+    }
     if (cfg.clear_seen_through) {
       clear_opt_ = svnicp_visibility_opt{(int32_t)sizeof(svnicp_visibility_opt), cfg.clear_window_rows, cfg.clear_window_cols, (float)cfg.clear_margin_abs,
                                          (float)cfg.clear_margin_rel, (float)(cfg.clear_max_range > 0 ? cfg.clear_max_range : cfg.max_range)};
@@ -786,7 +935,7 @@ class RegistrationPipeline {
       to_map = downsample_uniform(cropped, 0.5 * cfg_.voxel_size);                                     // :559
       source = downsample_uniform(to_map, 1.5 * cfg_.voxel_size);                                      // :560
     }
-    const Pose3 guess = pose_prediction(poses_, times_, stamp);                                        // :563-564
+    Pose3 guess = pose_prediction(poses_, times_, stamp);                                              // :563-564
     std::vector<double> init = sample_particles();                                                     // :573
     res.initial_guess = guess;
     if (dmap_ ? dmap_->Empty() : map_.Empty()) {                                                       // :585-593
@@ -802,6 +951,29 @@ class RegistrationPipeline {
     std::vector<double> src64;
     if (!dprep_) src64 = widen(source);                                                                // ICPUtils.cpp:27-43
     if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{cfg_.weight_dist > 0, cfg_.weight_dist, cfg_.weight_temperature}, cfg_.device);
+    if (cfg_.seed_grid) {   // no policy here: every scan is searched, and the best node is taken as it comes
+      const std::vector<double> poses12 = correction_poses(guess, seed_nodes_);
+      const double gate = cfg_.seed_gate > 0 ? cfg_.seed_gate : cfg_.map_voxel_size;
+      std::vector<double> scores;
+      if (dprep_) scores = dmap_->ScorePosesDevice(dprep_->source_f32(), dprep_->n_source, poses12, gate);   // not uploaded again
+      else if (dmap_) { scores = dmap_->ScorePoses(source, poses12, gate); bytes_h2d_ += source.size() * 12; }
+      else scores = map_.ScorePoses(source, poses12, gate);
+      const bool top = cfg_.seed_mode == "top";
+      const std::vector<size_t> order = seed_from_scores(scores, top ? (size_t)cfg_.particle_count : 1);
+      ScanResult::Seed sd;
+      sd.index = order[0]; sd.cost = scores[4 * order[0] + 3]; sd.cost_zero = scores[4 * seed_zero_ + 3]; sd.prediction = guess;
+      if (top) {
+        sd.nodes = order;
+        const int P = cfg_.particle_count;
+        for (int d = 0; d < 6; ++d)
+          for (int p = 0; p < P; ++p) init[(size_t)d * P + p] = seed_nodes_[order[p]][d];
+      } else {
+        sd.correction = seed_nodes_[order[0]];
+        guess = guess * correction_to_pose(sd.correction);
+        res.initial_guess = guess;
+      }
+      res.seed = sd;
+    }
     std::vector<double> tgt64;
     if (dmap_) {
       int64_t M = dmap_->GetMap(guess, scan_max_range_ + 10.0);                                        // :577-578
@@ -888,6 +1060,8 @@ class RegistrationPipeline {
 
   PipelineConfig cfg_;
   svnicp_visibility_opt clear_opt_{};
+  std::vector<std::array<double, 6>> seed_nodes_;   // cfg.seed_grid: the grid's nodes and the index of the zero correction
+  size_t seed_zero_ = 0;
   VoxelHashMap map_;
   std::vector<Pose3> poses_;
   std::vector<double> times_;

@@ -521,6 +521,89 @@ def visibility_test(map_points, pose, img, sensor: SegParams, wr: int, wc: int, 
     return tested, remove
 
 
+# ----------------------------------------------------------------------------- candidate poses scored against the map
+SCORE_FIELDS = ("located", "inliers", "sum_d2", "cost")   # SVNICP_MAP_SCORE_FIELDS of include/svnicp_hip.h
+SCORE_MAX_POSES = 1 << 20
+_VOX_OFF = 1 << 20                                        # voxel indices in [-2^20, 2^20)
+_GRID_SLACK = 1e-9                                        # correction_grid: extent / step may miss an integer by a rounding
+
+
+def pose_rows(poses) -> np.ndarray:
+    """Poses as svnicp_map_score_poses takes them: [C, 12] float64, R row-major then t.  Accepts [C, 12] or [C, 4, 4]."""
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = np.concatenate([p[:, :3, :3].reshape(-1, 9), p[:, :3, 3]], axis=1)
+    p = np.ascontiguousarray(p.reshape(-1, 12))
+    if not 1 <= p.shape[0] <= SCORE_MAX_POSES:
+        raise ValueError("score_poses: need 1 <= C <= 2^20 poses")
+    return p
+
+
+def check_score_gate(gate, voxel_size) -> float:
+    """The gate refusal of svnicp_map_score_poses -> thr2."""
+    gate = float(gate)
+    if not (np.isfinite(gate) and 0.0 < gate <= float(voxel_size)):
+        raise ValueError("score_poses: the gate must be finite, > 0 and <= voxel_size (the 3x3x3 block holds the nearest point only "
+                         "up to that gate)")
+    return gate * gate
+
+
+def correction_grid(extent6, step6):
+    """The nodes of a search grid as corrections in the solver's parametrisation [x, y, z, rx, ry, rz] -> ([C, 6], index of the
+    zero correction).  Per axis the offsets are k·step, k = -m..m, m = floor(extent / step) (a quotient within 1e-9 below an
+    integer counts as that integer: 10° / 2.5° is 4); extent 0 fixes the axis.  Lexicographic order, x slowest."""
+    ext, stp = np.asarray(extent6, np.float64).reshape(-1), np.asarray(step6, np.float64).reshape(-1)
+    if ext.shape != (6,) or stp.shape != (6,):
+        raise ValueError("correction_grid: extent and step hold six entries [x, y, z, rx, ry, rz]")
+    if not (np.isfinite(ext).all() and (ext >= 0).all()):
+        raise ValueError("correction_grid: extents must be finite and >= 0")
+    m = []
+    for e, s in zip(ext.tolist(), stp.tolist()):
+        if e == 0.0:
+            m.append(0)
+            continue
+        if not (np.isfinite(s) and s > 0):
+            raise ValueError("correction_grid: an axis with a non-zero extent needs a finite step > 0")
+        m.append(int(math.floor(e / s + _GRID_SLACK)))
+    count = 1
+    for k in m:
+        count *= 2 * k + 1
+    if count > SCORE_MAX_POSES:
+        raise ValueError(f"correction_grid: {count} nodes, more than 2^20")
+    axes = [np.arange(-k, k + 1, dtype=np.float64) * (s if k else 0.0) for k, s in zip(m, stp.tolist())]
+    nodes = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 6)
+    zero = 0
+    for k in m:
+        zero = zero * (2 * k + 1) + k
+    return nodes, zero
+
+
+def correction_poses(guess, corrections) -> np.ndarray:
+    """guess @ correction_to_pose(x) for every correction x -> [C, 12] (pose_rows' layout): how a particle's total pose is
+    composed, so a scored node can be handed to the solver as a particle unchanged."""
+    G = np.asarray(guess, float)
+    X = np.asarray(corrections, float).reshape(-1, 6)
+    out = np.empty((X.shape[0], 12))
+    for i, x in enumerate(X):
+        T = G @ correction_to_pose(x)
+        out[i, :9] = T[:3, :3].reshape(9)
+        out[i, 9:] = T[:3, 3]
+    return out
+
+
+def seed_from_scores(scores, corrections, P: int):
+    """-> (best correction [6], the P best corrections [P, 6], their node indices [P]), ordered by (cost, index): ties in cost go
+    to the lower index."""
+    sc = np.asarray(scores, np.float64).reshape(-1, len(SCORE_FIELDS))
+    X = np.asarray(corrections, np.float64).reshape(-1, 6)
+    if sc.shape[0] != X.shape[0]:
+        raise ValueError("seed_from_scores: one score record per correction")
+    if not 1 <= int(P) <= X.shape[0]:
+        raise ValueError("seed_from_scores: need 1 <= P <= number of corrections")
+    order = np.lexsort((np.arange(sc.shape[0]), sc[:, 3]))[:int(P)]
+    return X[order[0]].copy(), X[order].copy(), order
+
+
 class DeviceVoxelHashMap:
     """The same map resident in HBM (svnicp_map_* of the C ABI, csrc/voxel_map.hip): ``add_pointcloud`` uploads only the new
     points, ``get_map`` leaves the selected points in device memory as float64 rows and returns (device pointer, count) for
@@ -644,6 +727,38 @@ class DeviceVoxelHashMap:
         n = C.c_int64(0)
         self._chk(self._L.svnicp_map_query_normals(self._h, int(normal_k), C.byref(n)), "svnicp_map_query_normals")
         return int(self._L.svnicp_map_normals_devptr(self._h) or 0), int(n.value)
+
+    def score_poses(self, cloud, poses, gate: float) -> np.ndarray:
+        """How well the scan ``cloud`` (float32 [n,3], sensor frame) fits the map at each of ``poses`` ([C,12], [C,4,4] or a CUDA
+        float64 tensor [C,12]; map <- sensor) -> [C, 4] {located, inliers, sum_d2, cost} (svnicp_map_score_poses; the host
+        restatement is VoxelHashMap.score_poses).  ``gate`` is the inlier distance, at most the voxel size."""
+        pts = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 3))
+        self.bytes_uploaded += pts.nbytes
+        return self._score_poses(pts.ctypes.data_as(self._C.c_void_p) if pts.shape[0] else None, pts.shape[0], 0, poses, gate)
+
+    def score_poses_device(self, devptr: int, n: int, poses, gate: float) -> np.ndarray:
+        """score_poses for float32 rows that already live in HBM (DevicePreprocessor.source_f32_ptr)."""
+        return self._score_poses(self._C.c_void_p(int(devptr)), int(n), 1, poses, gate)
+
+    def _score_poses(self, ptr, n, mem, poses, gate):
+        C = self._C
+        if _is_cuda_tensor(poses):
+            import torch
+            t = poses.detach().to(torch.float64).reshape(-1, 12).contiguous()
+            torch.cuda.current_stream(t.device).synchronize()
+            pptr, nposes, pmem = C.c_void_p(t.data_ptr()), int(t.shape[0]), 1
+        else:
+            t = pose_rows(poses)
+            pptr, nposes, pmem = t.ctypes.data_as(C.c_void_p), t.shape[0], 0
+        out = np.zeros((max(nposes, 0), len(SCORE_FIELDS)))
+        self._chk(self._L.svnicp_map_score_poses(self._h, ptr, n, mem, pptr, nposes, pmem, float(gate),
+                                                 out.ctypes.data_as(C.POINTER(C.c_double))), "svnicp_map_score_poses")
+        return out
+
+    @property
+    def scores_ptr(self) -> int:
+        """Device pointer of the last scoring's float64 [C][4] records (0 before one)."""
+        return int(self._L.svnicp_map_scores_devptr(self._h) or 0)
 
     def download_normals(self) -> np.ndarray:
         """The rows of the last get_map_normals as a host array (test tap)."""
@@ -981,6 +1096,81 @@ class VoxelHashMap:
                 stats["voxels_emptied"] += 1
         return stats
 
+    def _score_table(self):
+        """The map as score_poses searches it: (ascending packed keys of the voxels inside the index range, first point of each
+        in ``pts``, points per voxel clamped to max_points, the points float64 [sum, 3])."""
+        keys = sorted(k for k in self._vox if all(-_VOX_OFF <= v < _VOX_OFF for v in k))
+        if not keys:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 3))
+        K = np.array(keys, np.int64).reshape(-1, 3) + _VOX_OFF
+        packed = (K[:, 0] << 42) | (K[:, 1] << 21) | K[:, 2]           # ascending, as the tuples are
+        cnt = np.array([min(len(self._vox[k]), self.max_points) for k in keys], np.int64)
+        pts = np.concatenate([np.asarray(self._vox[k][:self.max_points], np.float32).reshape(-1, 3) for k in keys], 0).astype(np.float64)
+        return packed, np.cumsum(cnt) - cnt, cnt, pts
+
+    def score_poses(self, cloud, poses, gate: float) -> np.ndarray:
+        """The numpy restatement of svnicp_map_score_poses (include/svnicp_hip.h) -> [C, 4] {located, inliers,
+        sum_d2, cost}.  Row p at pose (R, t): c = float32(((R0·x + R1·y) + R2·z) + t) in float64 of the widened float32 row;
+        voxel = trunc(c / float32(voxel_size)), valid in [-2^20, 2^20); candidates = the points of the 3x3x3 block of voxels;
+        d2 = ((dx·dx) + dy·dy) + dz·dz in float64; located iff the block holds a point, inlier iff located and min d2 < gate²
+        (strict); sum_d2 over the inliers, added in row order; cost = (sum_d2 + (n − inliers)·gate²) / n; n == 0: the cost is
+        gate².  Searched through sorted keys (searchsorted), one pass per pose and neighbour offset."""
+        thr2 = check_score_gate(gate, self.voxel_size)
+        P = pose_rows(poses)
+        f = np.asarray(cloud, np.float32).reshape(-1, 3)
+        n = f.shape[0]
+        out = np.zeros((P.shape[0], len(SCORE_FIELDS)))
+        out[:, 3] = thr2
+        if n == 0:
+            return out
+        packed, start, cnt, pts = self._score_table()
+        x, y, z = (f[:, d].astype(np.float64) for d in range(3))
+        vs = np.float32(self.voxel_size)
+        offs = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
+        batch = max(1, 65536 // n)                                       # poses handled at once: rows of the batch are flattened
+        for c0 in range(0, P.shape[0], batch):
+            Pb = P[c0:c0 + batch]
+            g = Pb.shape[0]
+            with np.errstate(all="ignore"):
+                c = np.stack([(((Pb[:, 3 * d, None] * x + Pb[:, 3 * d + 1, None] * y) + Pb[:, 3 * d + 2, None] * z)
+                               + Pb[:, 9 + d, None]).astype(np.float32) for d in range(3)], 2).reshape(g * n, 3)
+                q = np.trunc(c / vs)
+                ok = np.all((q >= np.float32(-_VOX_OFF)) & (q < np.float32(_VOX_OFF)), axis=1)      # False for NaN and inf
+            if packed.size == 0 or not ok.any():
+                continue
+            rows_ok = np.flatnonzero(ok)                                 # flat index = pose in the batch * n + row
+            v = q[rows_ok].astype(np.int64) + _VOX_OFF
+            key0 = (v[:, 0] << 42) | (v[:, 1] << 21) | v[:, 2]
+            by_key = np.argsort(key0)                                    # neighbouring queries: the bisections share their path
+            rows_ok, v, key0 = rows_ok[by_key], v[by_key], key0[by_key]
+            inside = [{-1: v[:, d] > 0, 0: True, 1: v[:, d] < 2 * _VOX_OFF - 1} for d in range(3)]   # outside: no such voxel
+            rr, vv = [], []
+            for o in offs:
+                key = key0 + ((o[0] << 42) + (o[1] << 21) + o[2])
+                pos = np.minimum(np.searchsorted(packed, key), packed.size - 1)
+                hit = (packed[pos] == key) & inside[0][o[0]] & inside[1][o[1]] & inside[2][o[2]]
+                rr.append(rows_ok[hit]); vv.append(pos[hit])
+            rr, vv = np.concatenate(rr), np.concatenate(vv)
+            if rr.size == 0:
+                continue
+            order = np.argsort(rr, kind="stable")
+            rr, vv = rr[order], vv[order]
+            cn = cnt[vv]
+            seg = np.cumsum(cn) - cn
+            idx = np.repeat(start[vv] - seg, cn) + np.arange(int(cn.sum()))
+            rep = np.repeat(rr, cn)
+            d = pts[idx] - c[rep].astype(np.float64)
+            d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            first = np.flatnonzero(np.r_[True, rep[1:] != rep[:-1]])
+            dmin = np.minimum.reduceat(d2, first)                                                    # per located row, flat rows ascending
+            cut = np.searchsorted(rep[first], np.arange(g + 1) * n)                                  # the located rows of each pose
+            for k in range(g):
+                dk = dmin[cut[k]:cut[k + 1]]
+                inl = dk[dk < thr2]
+                sm = float(np.add.accumulate(inl)[-1]) if inl.size else 0.0                          # sequential, in row order
+                out[c0 + k] = (dk.size, inl.size, sm, (sm + (n - inl.size) * thr2) / n)
+        return out
+
     def get_map(self, pose=None, max_range: float | None = None) -> np.ndarray:
         if not self._vox:
             return np.zeros((0, 3))
@@ -1040,8 +1230,25 @@ class PipelineConfig:
     mode_select: str = "mean"      # "heaviest": the correction is the first mode's mean instead of the global mean, and the pose, the evaluate, the information and the map update follow it; needs mode_link
     clear_seen_through: tuple | None = None   # (window_rows, window_cols, margin_abs m, margin_rel): after every successful registration the map points the cropped scan sees through at the result pose are dropped (clear_seen_through, sensor = seg_params) right before the map update, count in ScanResult.cleared; None = off, no call is made
     clear_max_range: float = 0.0   # with clear_seen_through: map points farther than this from the sensor are left alone; 0 = max_range
+    seed_grid: tuple | None = None  # (extent6, step6) of correction_grid: before every registration the scan's rows are scored against the map at the grid's nodes around the prediction (score_poses), result in ScanResult.seed; None = off, no call is made
+    seed_gate: float = 0.0         # with seed_grid: the inlier gate of that scoring, at most map_voxel_size; 0 = map_voxel_size
+    seed_mode: str = "best"        # "best": the registration's initial mean becomes prediction · correction_to_pose(best node), the particles are drawn as ever; "top": the mean stays the prediction and the particles are the particle_count best nodes
+
+    def seed_nodes(self):
+        """-> (corrections [C, 6], index of the zero correction) of seed_grid."""
+        return correction_grid(*self.seed_grid)
 
     def __post_init__(self):
+        if self.seed_mode not in ("best", "top"):
+            raise ValueError('PipelineConfig: seed_mode must be "best" or "top"')
+        if not (np.isfinite(self.seed_gate) and 0 <= self.seed_gate <= self.map_voxel_size):
+            raise ValueError("PipelineConfig: seed_gate must be finite, >= 0 (0 = map_voxel_size) and at most map_voxel_size")
+        if self.seed_grid is not None:
+            if len(tuple(self.seed_grid)) != 2:
+                raise ValueError("PipelineConfig: seed_grid must be (extent6, step6)")
+            nodes, _ = self.seed_nodes()                       # refuses steps <= 0 with an extent and more than 2^20 nodes
+            if self.seed_mode == "top" and nodes.shape[0] < self.particle_count:
+                raise ValueError('PipelineConfig: seed_mode "top" needs at least particle_count nodes in seed_grid')
         if self.clear_seen_through is not None:
             if len(tuple(self.clear_seen_through)) != 4:
                 raise ValueError("PipelineConfig: clear_seen_through must be (window_rows, window_cols, margin_abs, margin_rel)")
@@ -1095,6 +1302,7 @@ class ScanResult:
     information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
     modes: object | None = None              # cfg.mode_link: solver.ParticleModes of the final particle set, heaviest first
     cleared: int | None = None               # cfg.clear_seen_through: map points the scan saw through and the map dropped
+    seed: dict | None = None                 # cfg.seed_grid: {"index": best node, "cost": its cost, "cost_zero": the cost of the zero correction (the prediction), "correction": the correction applied to the initial mean ("top": zeros; with "best" initial_guess is prediction · correction_to_pose(correction)), "prediction": the constant-velocity prediction the grid is centred on, "nodes": the nodes handed over as particles ("top" only)}
 
 
 class RegistrationPipeline:
@@ -1113,6 +1321,29 @@ class RegistrationPipeline:
         self._rng = np.random.default_rng(self.cfg.seed)
         self._solver: SVNICP | None = None
         self._prep: DevicePreprocessor | None = None
+        self._seed_nodes = self.cfg.seed_nodes() if self.cfg.seed_grid is not None else None
+
+    def _seed(self, guess, source, dev):
+        """cfg.seed_grid: the scan's rows scored at the grid's nodes around the prediction -> (initial mean, particles or None,
+        ScanResult.seed).  No policy here: every scan is searched, and the best node is taken as it comes."""
+        c = self.cfg
+        nodes, zero = self._seed_nodes
+        poses = correction_poses(guess, nodes)
+        gate = c.seed_gate or c.map_voxel_size
+        if dev:
+            scores = self.map.score_poses_device(self._prep.source_f32_ptr, self._prep.n_source, poses, gate)   # not uploaded again
+        else:
+            scores = self.map.score_poses(source, poses, gate)
+            if c.gpu_map:
+                self.bytes_h2d += source.shape[0] * 12
+        top = c.seed_mode == "top"
+        best, first, order = seed_from_scores(scores, nodes, c.particle_count if top else 1)
+        seed = {"index": int(order[0]), "cost": float(scores[order[0], 3]), "cost_zero": float(scores[zero, 3]),
+                "correction": np.zeros(6) if top else best, "prediction": np.array(guess, float)}
+        if top:
+            seed["nodes"] = order.copy()
+            return guess, np.ascontiguousarray(first.T), seed
+        return guess @ correction_to_pose(best), None, seed
 
     def _particles(self) -> np.ndarray:
         return initialize_particles(self.cfg.particle_count, PRIOR_UB, PRIOR_LB, self._rng)   # set_initPose, :661-667
@@ -1168,6 +1399,11 @@ class RegistrationPipeline:
         if self._solver is None:
             self._solver = SVNICP(c.solver, init, ParticleWeightOpt(c.weight_dist > 0, c.weight_dist, c.weight_temperature), device=self.device)
         s = self._solver
+        seed = None
+        if c.seed_grid is not None:
+            guess, seeded, seed = self._seed(guess, None if dev else source, dev)
+            if seeded is not None:
+                init = seeded
         with_normal = None
         if c.gpu_map:
             ptr, M = self.map.get_map(guess, self.scan_max_range + 10.0)                                        # :577-578
@@ -1193,7 +1429,7 @@ class RegistrationPipeline:
         state = s.stein_align()                                                                                 # :602
         if state != SteinICPState.ALIGN_SUCCESS:                                                                # :602-604
             return ScanResult(stamp, guess, guess, preprocessing_s=t1 - t0, align_s=time.perf_counter() - t1, state=int(state),
-                              with_normal=with_normal)
+                              with_normal=with_normal, seed=seed)
         corr = s.get_transformation()                                                                           # :605
         pose = guess @ correction_to_pose(corr)                                                                 # updater_, :37-46
         modes = None
@@ -1205,6 +1441,7 @@ class RegistrationPipeline:
         res = ScanResult(stamp, pose, guess, corr, s.get_distribution(), s.get_cov_matrix(), s.get_particles().reshape(-1),
                          s.get_particle_weight(), t1 - t0, 0.0, int(state), with_normal)
         res.modes = modes
+        res.seed = seed
         if c.eval_dist > 0:   # the number a caller may gate the map update on (no policy here)
             ev = s.evaluate(c.eval_dist, pose)
             res.fitness, res.inlier_rmse = ev.fitness, ev.inlier_rmse
