@@ -214,7 +214,9 @@ int svnicp_set_residual(svnicp_ctx *ctx, int residual, double huber_delta, int n
 /* optional: normals of the current target, double [M][3], host or device (copied).  Must follow the svnicp_set_target /
  * svnicp_set_clouds it belongs to, with the same M; rows are normalised on upload (n / |n| in float64: a row that is already
  * unit comes back from svnicp_get_target_normals within 2 ulp, not necessarily bit for bit), a zero or non-finite row means "no
- * normal here" and stays zero; a later svnicp_set_target drops them.  SVNICP_MEM_HOST: copied when the call returns.
+ * normal here" and stays zero, and so does a finite row whose squared norm overflows or underflows to 0 in float64 (entries
+ * of 1e160, of 1e-170, subnormal entries: the norm is taken as sqrt(x x + y y + z z), unscaled; tests/test_plane_alone_gpu.py
+ * pins it); a later svnicp_set_target drops them.  SVNICP_MEM_HOST: copied when the call returns.
  * SVNICP_MEM_DEVICE: the device-to-device copy is QUEUED on the context's stream, as svnicp_set_target's is: the rows must stay
  * unchanged until a call that synchronises that stream (svnicp_align, svnicp_synchronize) has returned. */
 int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, int mem_kind);
@@ -600,6 +602,16 @@ void *svnicp_map_scores_devptr(svnicp_map *map);   /* double [C][4] of the last 
 /* ---- test-only taps (parity tests; not part of the reference interface) -------------------- */
 int svnicp_get_candidates(svnicp_ctx *ctx, int32_t *outBK);          /* sourceKNN_idx_  SVGDICP.cpp:214 */
 int svnicp_get_candidate_dist2(svnicp_ctx *ctx, double *outBK);
+/* plane mode, valid after svnicp_align_begin (NULL otherwise): the record one svnicp_iter_accumulate leaves, before any
+ * Stein step reads it (tests/test_plane_alone_gpu.py) */
+void *svnicp_plane_record_devptr(svnicp_ctx *ctx); /* double [P][42]: H (36, mirrored, + 1e-6 on the diagonal) | b (6) */
+void *svnicp_plane_stats_devptr(svnicp_ctx *ctx);  /* double [P][2]: {accepted pairs, sum w r^2} */
+/* (both are allocated max(P, Ppad) rows long, Ppad from svnicp_get_stage_b_grid: the rows from P on belong to the padded
+ * particles of the stage-B grid and are never written) */
+/* stage B's launch grid of the registration svnicp_align_begin began: {grid_x, grid_y, pts_per_block, Ppad} — the accumulate
+ * kernel runs grid_x x grid_y workgroups of pts_per_block source points each, and the finalize / reduce kernel adds grid_x
+ * records per particle.  SVNICP_ERR_INVALID before svnicp_align_begin. */
+int svnicp_get_stage_b_grid(svnicp_ctx *ctx, int out4[4]);
 /* valid when params.record_trace != 0; any pointer may be NULL.
  * corr: [I][P][B] int32 (-1 where not run), H [I][P][36], b [I][P][6], newton [I][P][6],
  * phi [I][P][6], h [I] */

@@ -211,6 +211,10 @@ def load_library():
     L.svnicp_sums_devptr.restype = vp
     L.svnicp_total_pose_devptr.argtypes = [vp]
     L.svnicp_total_pose_devptr.restype = vp
+    for name in ("svnicp_plane_record_devptr", "svnicp_plane_stats_devptr"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = vp
+    L.svnicp_get_stage_b_grid.argtypes = [vp, C.POINTER(C.c_int)]
     L.svnicp_set_minibatch.argtypes = [vp, C.c_int, C.c_uint64]
     L.svnicp_set_minibatch_indices.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.svnicp_get_minibatch_indices.argtypes = [vp, ip]

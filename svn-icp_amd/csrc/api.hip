@@ -99,7 +99,7 @@ struct PlaneState {
   DevBuf<double> nsup;        // upload staging of supplied normals
   DevBuf<int32_t> nbr;        // [rows of one pass block][normal_k] neighbour indices
   DevBuf<double> nbr_d2;
-  DevBuf<double> partial, Hb, stats;   // [grid_x][Ppad][kPlaneSums], [P][42], [P][2]
+  DevBuf<double> partial, Hb, stats;   // [grid_x][Ppad][kPlaneSums], [P][42], [P][2] (the last two allocated max(P, Ppad) rows long)
 };
 
 // svnicp_evaluate (csrc/evaluate.hip): its own buffers, nothing of the registration's
@@ -648,8 +648,10 @@ static int print_update_phases(svnicp_ctx* c, bool persistent) {
 // as the query cloud, identity pose, K = normal_k) in blocks of the rows its scratch is sized for.
 static int prepare_plane(svnicp_ctx* c) {
   HIPCHK(c, c->pl.partial.ensure((size_t)c->sb.plan.grid_x * c->sb.plan.Ppad * kPlaneSums));
-  HIPCHK(c, c->pl.Hb.ensure((size_t)c->P * 42));
-  HIPCHK(c, c->pl.stats.ensure((size_t)c->P * 2));
+  // (room for the padded particles of the stage-B grid, which no kernel writes: the kernel-by-kernel tests watch those rows)
+  const size_t rec_rows = (size_t)std::max(c->P, c->sb.plan.Ppad);
+  HIPCHK(c, c->pl.Hb.ensure(rec_rows * 42));
+  HIPCHK(c, c->pl.stats.ensure(rec_rows * 2));
   HIPCHK(c, hipMemsetAsync(c->pl.stats.p, 0, (size_t)c->P * 2 * sizeof(double), c->stream));
   const int kn = c->pl.normal_k;
   if (!normal_pass_due(c)) return SVNICP_OK;
@@ -934,6 +936,16 @@ int svnicp_stopped(svnicp_ctx* c) {
 void* svnicp_candidates_devptr(svnicp_ctx* c) { return c ? (void*)c->sa.cand_idx.p : nullptr; }
 void* svnicp_sums_devptr(svnicp_ctx* c) { return c ? (void*)c->sb.sums.p : nullptr; }
 void* svnicp_total_pose_devptr(svnicp_ctx* c) { return c ? (void*)c->st.Rtot.p : nullptr; }   // AccumArgs::Rtot, [P][12]
+// plane mode's record and statistics of the begun registration (prepare_plane sized them), and stage B's grid: test-only taps
+void* svnicp_plane_record_devptr(svnicp_ctx* c) { return (c && c->run.began && c->pl.on) ? (void*)c->pl.Hb.p : nullptr; }
+void* svnicp_plane_stats_devptr(svnicp_ctx* c) { return (c && c->run.began && c->pl.on) ? (void*)c->pl.stats.p : nullptr; }
+int svnicp_get_stage_b_grid(svnicp_ctx* c, int out4[4]) {
+  CTX_CHECK(c);
+  if (!out4) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_stage_b_grid: null argument");
+  if (!c->run.began) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_stage_b_grid: call svnicp_align_begin first");
+  out4[0] = c->sb.plan.grid_x; out4[1] = c->sb.plan.grid_y; out4[2] = c->sb.plan.pts_per_block; out4[3] = c->sb.plan.Ppad;
+  return SVNICP_OK;
+}
 
 // follow_stop: the caller is going to wait for the result anyway (svnicp_align) — with early stop on, the host then enqueues
 // the iterations in chunks and waits for the stop flag of the chunk before the previous one before it goes on: after the

@@ -247,7 +247,6 @@ hipError_t launch_reduce_partials(const double* partial, int nblk, int Ppad, int
 size_t update_uctl_doubles(int P);
 // ---------------- point-to-plane residual (plane_icp.hip) ----------------
 constexpr int kPlaneSums = 29;             // per (workgroup, particle): H upper triangle (21) | b (6) | accepted pairs | Σ w·r²
-constexpr double kPlaneMinRatio = 0.01;    // a normal is valid iff λ1 >= kPlaneMinRatio · λ2 (collinear neighbourhoods have none)
 struct PlaneArgs {
   const double* src;    // [B][3]
   const double* rec;    // [M][6] target xyz | unit normal (0 = no normal here)

@@ -60,7 +60,8 @@ __global__ __launch_bounds__(256) void k_target_normals(const double* __restrict
   o[0] = x0; o[1] = x1; o[2] = x2; o[3] = n0; o[4] = n1; o[5] = n2;
 }
 
-// supplied normals: normalised; a zero or non-finite row (or a non-finite point) means "no normal here"
+// supplied normals: normalised; a zero or non-finite row (or a non-finite point) means "no normal here", and so does a finite
+// row whose squared norm overflows or underflows to 0 in f64 (1e160, 1e-170, subnormals): the norm is not scaled
 __global__ __launch_bounds__(256) void k_pack_normals(const double* __restrict__ tgt, const double* __restrict__ nrm, int64_t M,
                                                       double* __restrict__ rec) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -2,16 +2,26 @@
 // number of sweeps, normal = unit eigenvector of the smallest eigenvalue, and the validity rule.  Stated once for
 // k_target_normals (plane_icp.hip: neighbours from stage A) and k_map_normals (voxel_map.hip: neighbours from the 27-voxel
 // block of the map); the two kernels differ only in where the neighbours come from and in the order of their sums.
+//
+// The header stands alone and also compiles for the host (tests/plane_normal_driver.cpp runs normal_from_scatter under the
+// address and undefined-behaviour sanitizers): device functions under hipcc, plain inline functions elsewhere.
 #pragma once
-#include "kernels.hpp"
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define SVNICP_NORMAL_FN __device__ __forceinline__
+#else
+#define SVNICP_NORMAL_FN inline
+#endif
 
 namespace svnicp {
 
+constexpr double kPlaneMinRatio = 0.01;   // a normal is valid iff λ1 >= kPlaneMinRatio · λ2 (collinear neighbourhoods have none)
 constexpr int kJacobiSweeps = 8;   // cyclic Jacobi on a symmetric 3x3 converges quadratically: 4-5 sweeps reach f64 round-off
 
 // one Jacobi rotation of the (P, Q) plane; R is the remaining index.  A = [a00 a11 a22 a01 a02 a12], V row-major.
 template <int P, int Q, int R>
-__device__ __forceinline__ void jacobi_rot(double* d, double& apq, double& apr, double& aqr, double* V) {
+SVNICP_NORMAL_FN void jacobi_rot(double* d, double& apq, double& apr, double& aqr, double* V) {
   if (apq == 0.0) return;
   const double theta = (d[Q] - d[P]) / (2.0 * apq);
   const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // |theta| huge: t = 0
@@ -22,7 +32,9 @@ __device__ __forceinline__ void jacobi_rot(double* d, double& apq, double& apr, 
   const double rp = apr, rq = aqr;
   apr = c * rp - s * rq;
   aqr = s * rp + c * rq;
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
   for (int i = 0; i < 3; ++i) {
     const double vp = V[3 * i + P], vq = V[3 * i + Q];
     V[3 * i + P] = c * vp - s * vq;
@@ -32,8 +44,8 @@ __device__ __forceinline__ void jacobi_rot(double* d, double& apq, double& apr, 
 
 // scatter matrix Σ (d − mean)(d − mean)ᵀ = [d0 d1 d2 | a01 a02 a12] -> unit normal n; returns false (n = 0) when there is none.
 // finite: every neighbour offset was finite (a non-finite matrix is not rotated).
-__device__ __forceinline__ bool normal_from_scatter(double d0, double d1, double d2, double a01, double a02, double a12, bool finite,
-                                                    double& n0, double& n1, double& n2) {
+SVNICP_NORMAL_FN bool normal_from_scatter(double d0, double d1, double d2, double a01, double a02, double a12, bool finite,
+                                         double& n0, double& n1, double& n2) {
   double d[3] = {d0, d1, d2};
   double V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   if (finite) {

@@ -15,7 +15,7 @@ The device sums in another order and diagonalises by Jacobi sweeps: results agre
 """
 import numpy as np
 
-MIN_RATIO = 0.01      # kPlaneMinRatio (csrc/kernels.hpp)
+MIN_RATIO = 0.01      # kPlaneMinRatio (csrc/plane_normal_device.hpp)
 INDEX_LIMIT = 1 << 20
 
 

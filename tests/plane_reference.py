@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-MIN_RATIO = 0.01      # a normal is valid iff lambda1 >= MIN_RATIO * lambda2 (kPlaneMinRatio, csrc/kernels.hpp)
+MIN_RATIO = 0.01      # a normal is valid iff lambda1 >= MIN_RATIO * lambda2 (kPlaneMinRatio, csrc/plane_normal_device.hpp)
 DAMPING = 1e-6        # SVNICP.cpp:153, kept in plane mode
 
 
