@@ -5,9 +5,10 @@
 //   k_evaluate_pairs      per row: gather the nearest target (or its xyz | normal record), recompute d2, classify, write the
 //                         index and d2; per workgroup ONE record {evaluated, inliers, plane inliers, sum d2, sum r2}
 //   k_evaluate_finalize   one workgroup adds the records in a fixed order and forms the ratios and roots
-// No atomics: workgroup w owns rows [256 w, 256 w + 256), so every addition happens in an order that depends on B alone and
-// the same context state gives the same bits on every call.
+// No atomics: workgroup w owns rows [256 w, 256 w + 256) and folds its record by fold_record (lane_fold_device.hpp), so every
+// addition happens in an order that depends on B alone and the same context state gives the same bits on every call.
 #include "kernels.hpp"
+#include "lane_fold_device.hpp"
 
 namespace svnicp {
 namespace {
@@ -24,19 +25,8 @@ __global__ __launch_bounds__(NT) void k_evaluate_transform(const double* __restr
   q[3 * b + 2] = (s0 * T.R[6] + s1 * T.R[7] + s2 * T.R[8]) + T.t[2];
 }
 
-// v summed over the workgroup, in thread 0: xor butterfly inside each wave, then waves 0..3 in order
-__device__ __forceinline__ double block_sum(double v, double* red /* [4] */) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-  const int w = threadIdx.x / kWave;
-  __syncthreads();   // the previous quantity's red[] has been read
-  if ((threadIdx.x & (kWave - 1)) == 0) red[w] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(NT) void k_evaluate_pairs(EvalArgs a) {
-  __shared__ double red[4];
+  __shared__ double lds[4 * kEvalRecord];
   const int64_t b = (int64_t)blockIdx.x * NT + threadIdx.x;
   double ev = 0.0, in = 0.0, pin = 0.0, sd = 0.0, sr = 0.0;   // the counts are exact in float64 (B < 2^31)
   if (b < a.B) {
@@ -62,25 +52,21 @@ __global__ __launch_bounds__(NT) void k_evaluate_pairs(EvalArgs a) {
       sr = pl ? r * r : 0.0;
     }
   }
-  const double t_ev = block_sum(ev, red), t_in = block_sum(in, red), t_pin = block_sum(pin, red);
-  const double t_sd = block_sum(sd, red), t_sr = block_sum(sr, red);
-  if (threadIdx.x == 0) {
-    double* o = a.partial + (size_t)blockIdx.x * kEvalRecord;
-    o[0] = t_ev; o[1] = t_in; o[2] = t_pin; o[3] = t_sd; o[4] = t_sr;
-  }
+  double v[kEvalRecord] = {ev, in, pin, sd, sr};
+  fold_record<kEvalRecord>(v, lds, a.partial + (size_t)blockIdx.x * kEvalRecord);
 }
 
 // out[kEvalResult] = {evaluated, inliers, plane inliers, sum d2, sum r2, fitness, inlier rmse, plane rmse}.  Thread t adds
-// the records t, t + 256, ... in ascending order; the 256 partial sums are folded as in k_evaluate_pairs.
+// the records t, t + 256, ... in ascending order; the 256 partial records are folded as in k_evaluate_pairs.
 __global__ __launch_bounds__(NT) void k_evaluate_finalize(const double* __restrict__ partial, int64_t nblk, int64_t rows, double* __restrict__ out) {
-  __shared__ double red[4];
+  __shared__ double lds[4 * kEvalRecord];
+  __shared__ double tot[kEvalRecord];
   double acc[kEvalRecord] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int64_t w = threadIdx.x; w < nblk; w += NT)
 #pragma unroll
     for (int i = 0; i < kEvalRecord; ++i) acc[i] += partial[(size_t)w * kEvalRecord + i];
-  double tot[kEvalRecord];
-#pragma unroll
-  for (int i = 0; i < kEvalRecord; ++i) tot[i] = block_sum(acc[i], red);
+  fold_record<kEvalRecord>(acc, lds, tot);
+  __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < kEvalRecord; ++i) out[i] = tot[i];

@@ -4,9 +4,10 @@
 //   k_information_pairs<form>     per row the terms of the form's sums, per workgroup ONE record
 //   k_information_finalize<form>  one workgroup adds the records in a fixed order and expands them to H[36] | b[6] | pairs,
 //                                 sum w, sum w r^2
-// No atomics: workgroup w owns rows [256 w, 256 w + 256) (evaluate's layout), every value is folded by the same xor butterfly
-// and the four wave totals are added in wave order, so the order of every addition depends on B alone.
+// No atomics: workgroup w owns rows [256 w, 256 w + 256) (evaluate's layout), every record is folded by fold_record
+// (lane_fold_device.hpp), so the order of every addition depends on B alone.
 #include "kernels.hpp"
+#include "lane_fold_device.hpp"
 
 namespace svnicp {
 namespace {
@@ -15,27 +16,6 @@ constexpr int NT = 256;
 static_assert(NT == 4 * kWave, "the record is folded across four waves");
 
 template <int FORM> struct Rec { static constexpr int n = FORM == 0 ? kInfoPointRecord : kInfoPlaneRecord; };
-
-// v[N] summed over the workgroup into out[N]: each value by an xor butterfly inside its wave, then ONE pass through LDS —
-// lane 0 of every wave stores its N totals, the first N threads add the four waves in order.  One barrier here; the caller
-// places another before lds is written again.
-template <int N>
-__device__ __forceinline__ void fold_record(double (&v)[N], double* lds /* [4][N] */, double* out /* [N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) v[i] += __shfl_xor(v[i], off, kWave);
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[w * N + i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    const int i = threadIdx.x;
-    out[i] = ((lds[i] + lds[N + i]) + lds[2 * N + i]) + lds[3 * N + i];
-  }
-}
 
 // Point record (18): pairs, sum w, sum w d2 | sum w s (3) | sum w s s^T upper triangle 00 01 02 11 12 22 | sum w c (3) |
 //                    sum w (s x c) (3), c = R^T e

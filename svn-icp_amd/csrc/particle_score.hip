@@ -1,16 +1,17 @@
 // particle_score.hip — svnicp_score_particles / svnicp_set_particle_weighting (include/svnicp_hip.h "score and weight the
 // particles"): every particle's total pose scored through the candidate table of the registration, by the
 // nearest-of-K rule the iterations use.  Three kernels:
-//   k_particle_score           lanes along the particles (the PW / WP geometry of plane_body), source rows in LDS tiles: the
+//   k_particle_score           lanes along the particles (ParticleLanes, lane_fold_device.hpp), source rows in LDS tiles: the
 //                              K candidate rows of a tile are gathered once, cooperatively (indices coalesced, the target
 //                              rows or xyz | normal records behind them), and every particle lane reads them as broadcasts.
-//                              Five float64 accumulators per lane; wave shuffle, then LDS: one record per (workgroup, particle)
-//   k_particle_score_finalize  the records added in k_reduce_partials' fixed order, [P][6] with the cost
+//                              Five float64 accumulators per lane; fold_particle_record: one record per (workgroup, particle)
+//   k_particle_score_finalize  the records added in reduce_block_records' fixed order, [P][6] with the cost
 //   k_particle_weights         one workgroup: cost_min, exp, Z in particle order, the weights
 // No atomics, no stop flag (a registration that stopped early is scored at the poses it stopped at).  Workgroup x owns rows
 // [64 x, 64 x + 64); inside it row b belongs to slot b mod STEP of the workgroup whatever the tile height, so every
 // addition happens in an order that depends on B and P alone.
 #include "kernels.hpp"
+#include "lane_fold_device.hpp"
 
 namespace svnicp {
 namespace {
@@ -23,27 +24,17 @@ constexpr int kTileBytesMax = 64 * 1024;   // one source row's candidates at mos
 template <int PW, int WP>
 __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
   extern __shared__ __align__(16) double lds[];
-  constexpr int BW = kWave / PW;     // source rows a wave works on at a time
-  constexpr int WB = 4 / WP;         // waves along the rows
-  constexpr int STEP = WB * BW;      // row slots of the workgroup
+  using Lanes = ParticleLanes<PW, WP>;
+  constexpr int BW = Lanes::BW, STEP = Lanes::STEP;
   static_assert(kScoreRowsPerBlock % STEP == 0, "a workgroup's rows are whole trips of its slots");
   const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wp = wave % WP, wb = wave / WP;
-  const int pl = lane % PW, bs = lane / PW;
-  const int pidx = (int)blockIdx.y * (WP * PW) + wp * PW + pl;
+  const Lanes L((int)blockIdx.y);
+  const int pidx = L.pidx;
   const bool pvalid = pidx < a.P;
-  const int slot = wb * BW + bs;
+  const int slot = L.wb * BW + L.bs;
 
   double Rt[9], tt[3];
-  {
-    const double* rp = a.Rtot + 12 * (size_t)(pvalid ? pidx : 0);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rt[i] = rp[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tt[i] = rp[9 + i];
-  }
+  load_pose(a.Rtot + 12 * (size_t)(pvalid ? pidx : 0), Rt, tt);
   const bool normals = a.rec != nullptr;
   const int W = normals ? 6 : 3;
   const int K = a.K;
@@ -112,64 +103,21 @@ __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
   }
 
   double acc[kScoreRecord] = {ev, in, pin, sd, sr};
-#pragma unroll
-  for (int off = PW; off < kWave; off <<= 1) {
-#pragma unroll
-    for (int i = 0; i < kScoreRecord; ++i) acc[i] += __shfl_xor(acc[i], off, kWave);
-  }
-  if constexpr (WB > 1) {
-    __syncthreads();   // the last tile has been read: its LDS now carries the waves' records
-    if (wb > 0 && bs == 0) {
-      double* rd = lds + ((size_t)(wb - 1) * (WP * PW) + wp * PW + pl) * kScoreRecord;
-#pragma unroll
-      for (int i = 0; i < kScoreRecord; ++i) rd[i] = acc[i];
-    }
-    __syncthreads();
-    if (wb == 0 && bs == 0) {
-      for (int o = 0; o < WB - 1; ++o) {
-        const double* rd = lds + ((size_t)o * (WP * PW) + wp * PW + pl) * kScoreRecord;
-#pragma unroll
-        for (int i = 0; i < kScoreRecord; ++i) acc[i] += rd[i];
-      }
-    }
-  }
-  if (wb == 0 && bs == 0) {
-    double* out = a.partial + ((size_t)blockIdx.x * a.Ppad + pidx) * kScoreRecord;
-#pragma unroll
-    for (int i = 0; i < kScoreRecord; ++i) out[i] = acc[i];
-  }
+  if constexpr (Lanes::WB > 1) __syncthreads();   // the last tile has been read: its LDS now carries the waves' records
+  fold_particle_record(L, acc, lds, a.partial, (size_t)blockIdx.x * a.Ppad);
 }
 
-// scores[p] = {evaluated, inliers, plane inliers, sum d2, sum r2, cost} from the workgroups' records.  A workgroup is 16
-// entries x 16 block lanes like k_reduce_partials, its entries the five sums of three particles: block lane l adds blocks
-// l, l + 16, ... in ascending order, then the 16 lanes are folded in order.  cost = (sum_d2 + (B - inliers) * thr2) / B.
+// scores[p] = {evaluated, inliers, plane inliers, sum d2, sum r2, cost} from the workgroups' records, added by
+// reduce_block_records (lane_fold_device.hpp); a workgroup's 16 entries are the five sums of three particles (one entry
+// idle).  cost = (sum_d2 + (B - inliers) * thr2) / B.
 __global__ __launch_bounds__(NT) void k_particle_score_finalize(const double* __restrict__ partial, int nblk, int Ppad, int P, double rows,
                                                                  double thr2, double* __restrict__ scores) {
-  __shared__ double red[16][17];
   __shared__ double tot[16];
   const int el = threadIdx.x & 15, bl = threadIdx.x >> 4;
   const int p = (int)blockIdx.x * 3 + el / kScoreRecord, f = el % kScoreRecord;
   const bool valid = el < 3 * kScoreRecord && p < P;
-  double a = 0.0;
-  if (valid) {
-    const size_t stride = (size_t)Ppad * kScoreRecord;
-    const double* src = partial + (size_t)p * kScoreRecord + f;
-    int blk = bl;
-    for (; blk + 7 * 16 < nblk; blk += 8 * 16) {
-      double v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(blk + 16 * i) * stride];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a += v[i];
-    }
-    for (; blk < nblk; blk += 16) a += src[(size_t)blk * stride];
-  }
-  red[bl][el] = a;
-  __syncthreads();
+  const double s = reduce_block_records(partial + (size_t)p * kScoreRecord + f, (size_t)Ppad * kScoreRecord, nblk, valid);
   if (bl == 0) {
-    double s = red[0][el];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) s += red[i][el];
     tot[el] = s;
     if (valid) scores[(size_t)p * kScoreFields + f] = s;
   }
@@ -242,15 +190,7 @@ hipError_t launch_particle_score(ScoreArgs a, double* scores, hipStream_t st) {
   a.Ppad = sh.Ppad;
   a.TH = score_tile_rows(a.P, a.K, a.rec != nullptr);
   if (a.TH < 1) return hipErrorInvalidValue;   // refused, never overflowed
-  hipError_t e;
-  switch (sh.PW) {
-    case 16: e = launch_s<16, 1>(a, sh.grid_y, st); break;
-    case 32: e = launch_s<32, 1>(a, sh.grid_y, st); break;
-    default:
-      if (sh.WP == 1) e = launch_s<64, 1>(a, sh.grid_y, st);
-      else if (sh.WP == 2) e = launch_s<64, 2>(a, sh.grid_y, st);
-      else e = launch_s<64, 4>(a, sh.grid_y, st);
-  }
+  const hipError_t e = dispatch_lanes(sh.PW, sh.WP, [&](auto l) { return launch_s<l.PW, l.WP>(a, sh.grid_y, st); });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_particle_score_finalize, dim3((a.P + 2) / 3), dim3(NT), 0, st, a.partial, (int)score_blocks(a.B), a.Ppad, a.P,
                      (double)a.B, a.thr2, scores);

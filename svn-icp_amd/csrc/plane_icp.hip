@@ -11,6 +11,7 @@
 //   k_plane_finalize    adds the workgroups' records in a fixed order, mirrors H, adds the 1e-6 damping: [P][42] = H | b,
 //                       which the Stein-step kernels read in place of finalize_Hb's output (UpdateArgs::plane_Hb).
 #include "kernels.hpp"
+#include "lane_fold_device.hpp"
 #include "plane_normal_device.hpp"
 #include "stein_common.hpp"
 
@@ -78,39 +79,27 @@ __global__ __launch_bounds__(256) void k_pack_normals(const double* __restrict__
 // ---------------------------------------------------------------------------------------------
 // accumulation from the search kernel's winner indices
 // ---------------------------------------------------------------------------------------------
-// Same geometry as accumulate_body (stein_split_device.hpp): lane <-> particle (PW particles x 64/PW points per wave, WP
-// particle waves x 4/WP point waves per workgroup), U points per wave and loop trip so that the index -> record gathers go
-// out as batches, wave shuffle, then LDS, one record per workgroup.  Ts and d² are the search kernel's unfused expressions:
-// the winner was certified for exactly that Ts and the gate compares exactly that d².
+// Lane <-> particle by ParticleLanes (lane_fold_device.hpp), U points per wave and loop trip so that the index -> record
+// gathers go out as batches, then fold_particle_record: one record per (workgroup, particle).  Ts and d² are the search
+// kernel's unfused expressions: the winner was certified for exactly that Ts and the gate compares exactly that d².
 template <int PW, int WP, bool TRACE>
 __device__ __forceinline__ void plane_body(const PlaneArgs& a, int bx, int by, double* lds) {
   if (a.ctl[0]) return;
-  constexpr int BW = kWave / PW;
-  constexpr int WB = 4 / WP;
   constexpr int U = 2;   // 29 accumulators + the pose: two 48-byte records in flight per lane keep the kernel at three waves per SIMD
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wp = wave % WP, wb = wave / WP;
-  const int pl = lane % PW, bs = lane / PW;
-  const int pidx = by * (WP * PW) + wp * PW + pl;
+  using Lanes = ParticleLanes<PW, WP>;
+  constexpr int BW = Lanes::BW, STEP = Lanes::STEP;
+  const Lanes L(by);
+  const int wb = L.wb, bs = L.bs, pidx = L.pidx;
   const int p = a.p_lo + pidx;
   const bool pvalid = p < a.p_hi;
 
   double Rt[9], tt[3];
-  {
-    const double* rp = a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rt[i] = rp[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tt[i] = rp[9 + i];
-  }
+  load_pose(a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo), Rt, tt);
   double acc[kPlaneSums];
 #pragma unroll
   for (int i = 0; i < kPlaneSums; ++i) acc[i] = 0.0;
   const int64_t blk_lo = (int64_t)bx * a.pts_per_block;
   const int64_t blk_hi = (blk_lo + a.pts_per_block < a.B) ? blk_lo + a.pts_per_block : a.B;
-  constexpr int STEP = WB * BW;
   const SVNICP_CONST_AS double* csrc = (const SVNICP_CONST_AS double*)a.src;   // wave-uniform rows become s_load
   const SVNICP_CONST_AS double* crec = (const SVNICP_CONST_AS double*)a.rec;
   const int32_t* kip = a.kidx + pidx;
@@ -187,32 +176,7 @@ __device__ __forceinline__ void plane_body(const PlaneArgs& a, int bx, int by, d
     }
   }
 
-#pragma unroll
-  for (int off = PW; off < kWave; off <<= 1) {
-#pragma unroll
-    for (int i = 0; i < kPlaneSums; ++i) acc[i] += __shfl_xor(acc[i], off, kWave);
-  }
-  if constexpr (WB > 1) {
-    double* red = lds;
-    if (wb > 0 && bs == 0) {
-      double* r = red + ((size_t)(wb - 1) * (WP * PW) + wp * PW + pl) * kPlaneSums;
-#pragma unroll
-      for (int i = 0; i < kPlaneSums; ++i) r[i] = acc[i];
-    }
-    __syncthreads();
-    if (wb == 0 && bs == 0) {
-      for (int o = 0; o < WB - 1; ++o) {
-        const double* r = red + ((size_t)o * (WP * PW) + wp * PW + pl) * kPlaneSums;
-#pragma unroll
-        for (int i = 0; i < kPlaneSums; ++i) acc[i] += r[i];
-      }
-    }
-  }
-  if (wb == 0 && bs == 0) {
-    double* out = a.partial + ((size_t)bx * a.Ppad + pidx) * kPlaneSums;
-#pragma unroll
-    for (int i = 0; i < kPlaneSums; ++i) out[i] = acc[i];
-  }
+  fold_particle_record(L, acc, lds, a.partial, (size_t)bx * a.Ppad);
 }
 
 template <int PW, int WP, bool TRACE>
@@ -222,35 +186,15 @@ __global__ __launch_bounds__(NT, 3) void k_plane_accumulate(PlaneArgs a) {
 }
 
 // Hb[p] = H (36, mirrored, + 1e-6 on the diagonal) | b (6), stats[p] = {accepted pairs, Σ w·r²} from the workgroups'
-// records.  Workgroup = 16 entries x 16 block lanes like k_reduce_partials: block lane l adds blocks l, l + 16, … in
-// ascending order, then the 16 lanes are folded in order — one fixed order of additions, whatever the launch geometry.
+// records, added by reduce_block_records (lane_fold_device.hpp): one fixed order of additions, whatever the launch geometry.
 __global__ __launch_bounds__(256) void k_plane_finalize(const double* __restrict__ partial, int nblk, int Ppad, int p_lo, int n_particles,
                                                         double* __restrict__ Hb, double* __restrict__ stats, const int* __restrict__ ctl) {
   if (ctl[0]) return;
-  __shared__ double red[16][17];
   const int el = threadIdx.x & 15, bl = threadIdx.x >> 4;
   const int entry = blockIdx.x * 16 + el;  // index into [n_particles][kPlaneSums]
   const int n_entries = n_particles * kPlaneSums;
-  double a = 0.0;
-  if (entry < n_entries) {
-    const size_t stride = (size_t)Ppad * kPlaneSums;
-    const double* src = partial + entry;
-    int blk = bl;
-    for (; blk + 7 * 16 < nblk; blk += 8 * 16) {
-      double v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(blk + 16 * i) * stride];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a += v[i];
-    }
-    for (; blk < nblk; blk += 16) a += src[(size_t)blk * stride];
-  }
-  red[bl][el] = a;
-  __syncthreads();
+  const double s = reduce_block_records(partial + entry, (size_t)Ppad * kPlaneSums, nblk, entry < n_entries);
   if (bl == 0 && entry < n_entries) {
-    double s = red[0][el];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) s += red[i][el];
     const int p = p_lo + entry / kPlaneSums, e = entry % kPlaneSums;
     double* o = Hb + (size_t)p * 42;
     if (e < 21) {
@@ -296,14 +240,7 @@ hipError_t launch_pack_normals(const double* tgt, const double* nrm, int64_t M, 
 hipError_t launch_plane_accumulate(const AccumPlan& plan, PlaneArgs a, hipStream_t st) {
   if (plan.f32 != 3) return hipErrorInvalidValue;   // the kernel consumes the search kernel's winner index
   a.Ppad = plan.Ppad; a.pts_per_block = plan.pts_per_block;
-  switch (plan.PW) {
-    case 16: return launch_p<16, 1>(plan, a, st);
-    case 32: return launch_p<32, 1>(plan, a, st);
-    default:
-      if (plan.WP == 1) return launch_p<64, 1>(plan, a, st);
-      if (plan.WP == 2) return launch_p<64, 2>(plan, a, st);
-      return launch_p<64, 4>(plan, a, st);
-  }
+  return dispatch_lanes(plan.PW, plan.WP, [&](auto l) { return launch_p<l.PW, l.WP>(plan, a, st); });
 }
 
 hipError_t launch_plane_finalize(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* Hb, double* stats,

@@ -179,6 +179,22 @@ inline AccumPlan stage_b_shape(int variant, int nshard, int K) {
   pl.RS = (3 * K) | 1;
   return pl;
 }
+// a run-time (PW, WP) of stage_b_shape's split layout as a compile-time tag: f(Lanes<PW, WP>{}) for the five geometries the
+// lane <-> particle kernels are instantiated for, e.g.
+//   dispatch_lanes(plan.PW, plan.WP, [&](auto l) { return launch<l.PW, l.WP>(plan, a, st); });
+// (the stage-B kernels of stein_iter.hip also run PW = 8, shards of at most eight particles: they ask for it first)
+template <int PW_, int WP_> struct Lanes { static constexpr int PW = PW_, WP = WP_; };
+template <class F>
+auto dispatch_lanes(int PW, int WP, F&& f) {
+  switch (PW) {
+    case 16: return f(Lanes<16, 1>{});
+    case 32: return f(Lanes<32, 1>{});
+    default:
+      if (WP == 1) return f(Lanes<64, 1>{});
+      if (WP == 2) return f(Lanes<64, 2>{});
+      return f(Lanes<64, 4>{});
+  }
+}
 // small registration (few pairs, one context holds everything, 2 <= P <= 128): the accumulate kernel runs at most
 // kSmallChainBlocks workgroups (plan_accumulate clamps its grid), so the update kernels add their records themselves
 inline bool small_registration(const AccumPlan& shape, const RegistrationFacts& f, const Tuning& t, int64_t Bi) {

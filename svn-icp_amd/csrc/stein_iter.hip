@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "kernels.hpp"
+#include "lane_fold_device.hpp"
 #include "stein_common.hpp"
 #include "stein_step_device.hpp"
 
@@ -184,25 +185,17 @@ __global__ __launch_bounds__(NT) void k_icp_single(AccumArgs a, UpdateArgs u) {
 template <int PW, int WP>
 __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a) {
   if (a.ctl[0]) return;  // early stop already signalled (SVNICP.cpp:95-101)
-  constexpr int BW = kWave / PW;  // source points per wave pass
-  constexpr int WB = 4 / WP;      // waves along the source-point axis
+  using Lanes = ParticleLanes<PW, WP>;   // lane_fold_device.hpp
+  constexpr int BW = Lanes::BW, WB = Lanes::WB;
   extern __shared__ __align__(16) double lds[];
   const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid >> 6;
-  const int wp = wave % WP, wb = wave / WP;
-  const int pl = lane % PW, bs = lane / PW;
-  const int pidx = blockIdx.y * (WP * PW) + wp * PW + pl;  // index inside the shard (padded)
-  const int p = a.p_lo + pidx;
+  const Lanes lanes((int)blockIdx.y);
+  const int wb = lanes.wb, bs = lanes.bs;
+  const int p = a.p_lo + lanes.pidx;
   const bool pvalid = p < a.p_hi;
 
   double Rt[9], tt[3];
-  {
-    const double* rp = a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rt[i] = rp[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tt[i] = rp[9 + i];
-  }
+  load_pose(a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo), Rt, tt);
   double acc[kNSums];
 #pragma unroll
   for (int i = 0; i < kNSums; ++i) acc[i] = 0.0;
@@ -265,33 +258,8 @@ __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a) {
   }
 
   // ---- fixed-order reduction: lane groups → waves → one partial row per particle ----
-#pragma unroll
-  for (int off = PW; off < kWave; off <<= 1) {
-#pragma unroll
-    for (int i = 0; i < kNSums; ++i) acc[i] += __shfl_xor(acc[i], off, kWave);
-  }
-  if constexpr (WB > 1) {
-    __syncthreads();  // tile memory is free now
-    double* red = lds;  // [(WB-1)][WP*PW][kNSums]
-    if (wb > 0 && bs == 0) {
-      double* r = red + ((size_t)(wb - 1) * (WP * PW) + wp * PW + pl) * kNSums;
-#pragma unroll
-      for (int i = 0; i < kNSums; ++i) r[i] = acc[i];
-    }
-    __syncthreads();
-    if (wb == 0 && bs == 0) {
-      for (int o = 0; o < WB - 1; ++o) {
-        const double* r = red + ((size_t)o * (WP * PW) + wp * PW + pl) * kNSums;
-#pragma unroll
-        for (int i = 0; i < kNSums; ++i) acc[i] += r[i];
-      }
-    }
-  }
-  if (wb == 0 && bs == 0) {
-    double* out = a.partial + ((size_t)blockIdx.x * a.Ppad + pidx) * kNSums;
-#pragma unroll
-    for (int i = 0; i < kNSums; ++i) out[i] = acc[i];
-  }
+  if constexpr (WB > 1) __syncthreads();  // tile memory is free now
+  fold_particle_record(lanes, acc, lds, a.partial, (size_t)blockIdx.x * a.Ppad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -319,25 +287,18 @@ __global__ __launch_bounds__(NT) void k_stein_accumulate(AccumArgs a) {
 template <int PW, int WP>
 __global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a) {
   if (a.ctl[0]) return;
-  constexpr int BW = kWave / PW;
-  constexpr int WB = 4 / WP;
+  using Lanes = ParticleLanes<PW, WP>;   // lane_fold_device.hpp
+  constexpr int BW = Lanes::BW, WB = Lanes::WB;
   extern __shared__ __align__(16) double lds[];
   const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid >> 6;
-  const int wp = wave % WP, wb = wave / WP;
-  const int pl = lane % PW, bs = lane / PW;
-  const int pidx = blockIdx.y * (WP * PW) + wp * PW + pl;
-  const int p = a.p_lo + pidx;
+  const int lane = tid & (kWave - 1);
+  const Lanes lanes((int)blockIdx.y);
+  const int wb = lanes.wb, bs = lanes.bs;
+  const int p = a.p_lo + lanes.pidx;
   const bool pvalid = p < a.p_hi;
 
   double Rt[9], tt[3];
-  {
-    const double* rp = a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rt[i] = rp[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tt[i] = rp[9 + i];
-  }
+  load_pose(a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo), Rt, tt);
   double acc[kNSums];
 #pragma unroll
   for (int i = 0; i < kNSums; ++i) acc[i] = 0.0;
@@ -453,33 +414,8 @@ __global__ __launch_bounds__(NT, 4) void k_stein_accumulate_f32(AccumArgs a) {
     if (have && pend.pt >= 0) accumulate_point(pend, spts, a.max_dist, a.svgd, acc);  // drain before the tile is replaced
   }
 
-#pragma unroll
-  for (int off = PW; off < kWave; off <<= 1) {
-#pragma unroll
-    for (int i = 0; i < kNSums; ++i) acc[i] += __shfl_xor(acc[i], off, kWave);
-  }
-  if constexpr (WB > 1) {
-    __syncthreads();
-    double* red = lds;
-    if (wb > 0 && bs == 0) {
-      double* r = red + ((size_t)(wb - 1) * (WP * PW) + wp * PW + pl) * kNSums;
-#pragma unroll
-      for (int i = 0; i < kNSums; ++i) r[i] = acc[i];
-    }
-    __syncthreads();
-    if (wb == 0 && bs == 0) {
-      for (int o = 0; o < WB - 1; ++o) {
-        const double* r = red + ((size_t)o * (WP * PW) + wp * PW + pl) * kNSums;
-#pragma unroll
-        for (int i = 0; i < kNSums; ++i) acc[i] += r[i];
-      }
-    }
-  }
-  if (wb == 0 && bs == 0) {
-    double* out = a.partial + ((size_t)blockIdx.x * a.Ppad + pidx) * kNSums;
-#pragma unroll
-    for (int i = 0; i < kNSums; ++i) out[i] = acc[i];
-  }
+  if constexpr (WB > 1) __syncthreads();  // the last tile has been read: its LDS now carries the waves' records
+  fold_particle_record(lanes, acc, lds, a.partial, (size_t)blockIdx.x * a.Ppad);
 }
 
 // candidate table: f64 absolute coordinates (target_batch = index_select(target, sourceKNN_idx),
@@ -535,12 +471,8 @@ static int occ_t(const AccumPlan& pl) {
   return n > 8 ? 8 : n;
 }
 static int occupancy_blocks(const AccumPlan& pl) {
-  switch (pl.PW) {
-    case 8: return occ_t<8, 1>(pl);
-    case 16: return occ_t<16, 1>(pl);
-    case 32: return occ_t<32, 1>(pl);
-    default: return pl.WP == 1 ? occ_t<64, 1>(pl) : pl.WP == 2 ? occ_t<64, 2>(pl) : occ_t<64, 4>(pl);
-  }
+  if (pl.PW == 8) return occ_t<8, 1>(pl);
+  return dispatch_lanes(pl.PW, pl.WP, [&](auto l) { return occ_t<l.PW, l.WP>(pl); });
 }
 
 AccumPlan plan_accumulate(AccumPlan pl, int64_t B, int num_cus, const Tuning& tune) {
@@ -623,15 +555,8 @@ hipError_t launch_accumulate(const AccumPlan& plan, AccumArgs a, const UpdateArg
     hipLaunchKernelGGL(k_icp_single, dim3(single_particle_grid(a.B)), dim3(NT), 0, st, a, *single);
     return hipGetLastError();
   }
-  switch (plan.PW) {
-    case 8: return launch_t<8, 1>(plan, a, st);
-    case 16: return launch_t<16, 1>(plan, a, st);
-    case 32: return launch_t<32, 1>(plan, a, st);
-    default:
-      if (plan.WP == 1) return launch_t<64, 1>(plan, a, st);
-      if (plan.WP == 2) return launch_t<64, 2>(plan, a, st);
-      return launch_t<64, 4>(plan, a, st);
-  }
+  if (plan.PW == 8) return launch_t<8, 1>(plan, a, st);
+  return dispatch_lanes(plan.PW, plan.WP, [&](auto l) { return launch_t<l.PW, l.WP>(plan, a, st); });
 }
 
 hipError_t launch_build_table2(const int32_t* idx, int64_t B, int K, const double* tgt, int64_t M, double* table,

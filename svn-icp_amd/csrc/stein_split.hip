@@ -142,14 +142,7 @@ void occ_split(int K, size_t smem, int* search, int* accum) {
 
 // resident workgroups per CU of the two kernels (grids are sized to one resident round)
 void split_occupancy_blocks(int PW, int WP, int K, size_t smem, int* search, int* accum) {
-  switch (PW) {
-    case 16: return occ_split<16, 1>(K, smem, search, accum);
-    case 32: return occ_split<32, 1>(K, smem, search, accum);
-    default:
-      if (WP == 1) return occ_split<64, 1>(K, smem, search, accum);
-      if (WP == 2) return occ_split<64, 2>(K, smem, search, accum);
-      return occ_split<64, 4>(K, smem, search, accum);
-  }
+  return dispatch_lanes(PW, WP, [&](auto l) { return occ_split<l.PW, l.WP>(K, smem, search, accum); });
 }
 
 hipError_t launch_build_table3(const int32_t* idx, int64_t B, int K, const double* tgt, int64_t M, double* table,
@@ -172,14 +165,7 @@ hipError_t launch_build_table3_list(const int32_t* idx, const int32_t* list, con
 hipError_t launch_search_split(const AccumPlan& plan, AccumArgs a, hipStream_t st) {
   a.Ppad = plan.Ppad; a.pts_per_block = plan.pts_per_block; a.spts_per_block = plan.spts_per_block;
   if (!search_offsets_fit(a.Ppad, a.K)) return hipErrorInvalidValue;   // search_limits.hpp
-  switch (plan.PW) {
-    case 16: return launch_srb<16, 1>(plan, a, st);
-    case 32: return launch_srb<32, 1>(plan, a, st);
-    default:
-      if (plan.WP == 1) return launch_srb<64, 1>(plan, a, st);
-      if (plan.WP == 2) return launch_srb<64, 2>(plan, a, st);
-      return launch_srb<64, 4>(plan, a, st);
-  }
+  return dispatch_lanes(plan.PW, plan.WP, [&](auto l) { return launch_srb<l.PW, l.WP>(plan, a, st); });
 }
 
 __global__ __launch_bounds__(256) void k_transform_cloud(const double* __restrict__ src, int64_t B, const double* __restrict__ pose12,
@@ -200,14 +186,7 @@ hipError_t launch_transform_cloud(const double* src, int64_t B, const double* po
 }
 
 hipError_t launch_accumulate_split(const AccumPlan& plan, const AccumArgs& a, hipStream_t st) {
-  switch (plan.PW) {
-    case 16: return launch_w<16, 1>(plan, a, st);
-    case 32: return launch_w<32, 1>(plan, a, st);
-    default:
-      if (plan.WP == 1) return launch_w<64, 1>(plan, a, st);
-      if (plan.WP == 2) return launch_w<64, 2>(plan, a, st);
-      return launch_w<64, 4>(plan, a, st);
-  }
+  return dispatch_lanes(plan.PW, plan.WP, [&](auto l) { return launch_w<l.PW, l.WP>(plan, a, st); });
 }
 
 }  // namespace svnicp

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include "kernels.hpp"
 #include "stein_common.hpp"
+#include "lane_fold_device.hpp"
 #include "search_limits.hpp"
 
 namespace svnicp {
@@ -603,36 +604,25 @@ __global__ __launch_bounds__(NT, (PW == 16 || WP == 4) ? 3 : SVNICP_SEARCH_WAVES
 template <int PW, int WP, bool PLAIN, bool SVGD = false>
 __device__ __forceinline__ void accumulate_body(const AccumArgs& a, int bx, int by, double* lds) {   // lds: the launch's dynamic LDS
   if (a.ctl[0]) return;
-  constexpr int BW = kWave / PW;
-  constexpr int WB = 4 / WP;
 #ifndef SVNICP_ACCUM_U
 #define SVNICP_ACCUM_U 4
 #endif
   constexpr int U = SVNICP_ACCUM_U;   // points per wave and loop trip: their dependent loads go out as batches (2, 6, 8 measured: no better)
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wp = wave % WP, wb = wave / WP;
-  const int pl = lane % PW, bs = lane / PW;
-  const int pidx = by * (WP * PW) + wp * PW + pl;
+  using Lanes = ParticleLanes<PW, WP>;   // lane_fold_device.hpp
+  constexpr int BW = Lanes::BW, STEP = Lanes::STEP;
+  const Lanes L(by);
+  const int wb = L.wb, bs = L.bs, pidx = L.pidx;
   const int p = a.p_lo + pidx;
   const bool pvalid = p < a.p_hi;
 
   double Rt[9], tt[3];
-  {
-    const double* rp = a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rt[i] = rp[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tt[i] = rp[9 + i];
-  }
+  load_pose(a.Rtot + 12 * (size_t)(pvalid ? p : a.p_lo), Rt, tt);
   double acc[kNSums];
 #pragma unroll
   for (int i = 0; i < kNSums; ++i) acc[i] = 0.0;
   const int K = a.K;
   const int64_t blk_lo = (int64_t)bx * a.pts_per_block;
   const int64_t blk_hi = (blk_lo + a.pts_per_block < a.B) ? blk_lo + a.pts_per_block : a.B;
-  constexpr int STEP = WB * BW;
   const SVNICP_CONST_AS double* csrc = (const SVNICP_CONST_AS double*)a.src;       // wave-uniform rows become s_load
   const SVNICP_CONST_AS int32_t* ccand = (const SVNICP_CONST_AS int32_t*)a.cand;
   const SVNICP_CONST_AS double* ctgt = (const SVNICP_CONST_AS double*)a.tgt;
@@ -754,22 +744,25 @@ __device__ __forceinline__ void accumulate_body(const AccumArgs& a, int bx, int 
     }
   }
 
+  // fold_particle_record (lane_fold_device.hpp) written out: the same additions in the same order.  Through the helper
+  // the compiler allocates one or two VGPRs more in the WP = 1 instantiations, and <64, 1, true, false> stands at 127 of
+  // the 128 that four waves per SIMD allow (tests/test_search_isa_budget.py).  A change to either site is a change to both.
+  constexpr int WB = Lanes::WB, NP = Lanes::NP;
 #pragma unroll
   for (int off = PW; off < kWave; off <<= 1) {
 #pragma unroll
     for (int i = 0; i < kNSums; ++i) acc[i] += __shfl_xor(acc[i], off, kWave);
   }
   if constexpr (WB > 1) {
-    double* red = lds;
     if (wb > 0 && bs == 0) {
-      double* r = red + ((size_t)(wb - 1) * (WP * PW) + wp * PW + pl) * kNSums;
+      double* r = lds + ((size_t)(wb - 1) * NP + L.wp * PW + L.pl) * kNSums;
 #pragma unroll
       for (int i = 0; i < kNSums; ++i) r[i] = acc[i];
     }
     __syncthreads();
     if (wb == 0 && bs == 0) {
       for (int o = 0; o < WB - 1; ++o) {
-        const double* r = red + ((size_t)o * (WP * PW) + wp * PW + pl) * kNSums;
+        const double* r = lds + ((size_t)o * NP + L.wp * PW + L.pl) * kNSums;
 #pragma unroll
         for (int i = 0; i < kNSums; ++i) acc[i] += r[i];
       }

@@ -3,7 +3,10 @@ the preconditions of what tests/test_particle_score_gpu.py compares exactly."""
 import numpy as np
 
 B_, M_ = 300, 3000
-PS = (1, 4, 9, 64, 130)
+# every geometry of ParticleLanes: 1, 4, 9 -> 16 lanes; 25 -> 32; 64 -> 64 x 1 wave; 100 -> 64 x 2; 130 -> 64 x 4
+# (appended, never inserted: cloud_of and iterations_of go by the position in PS).  25, not 24: in SVGD mode at K = 1 one
+# of 24 particles (and of 18, 19, 21, 30, 31) ends without an inlier at the narrow gate, which the GPU test's cases exclude.
+PS = (1, 4, 9, 64, 130, 25, 100)
 KS = (1, 16, 128, 150)        # 150: the fused float32 stage B and the seeded scan
 GATES = (0.3, 1.0)
 CLOUDS = ("random", "sheets")

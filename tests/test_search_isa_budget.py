@@ -6,7 +6,8 @@ this test cross-compiles stein_split.hip for gfx950 with the Makefile's flags in
 group loop of that instantiation (the innermost loop whose body holds the step's 24 MFMAs) and bounds the vector
 instructions issued by one trip of it.  Blocks of loops nested inside it (the exact pass a full queue falls back to)
 are not counted.  The budgets are the counts the code has now, so a change that adds work to the step fails here
-first.
+first.  The same assembly also holds the plain accumulate kernels, which stand one or two registers below the four-wave
+limit: their kernel descriptors are read for that limit.
 """
 import collections
 import os
@@ -24,7 +25,8 @@ SYM = "_ZN6svnicp12_GLOBAL__N_119k_stein_search_bf16ILi64ELi2ELi6ELb1EEEvNS_9Acc
 VECTOR_BUDGET = 372   # v_*, ds_*, global_* per group step (396 before the plane layout of the tile rows, the 32-bit offsets,
                       # the tile-index tags, the mask-free B split and the branch-free decision)
 MOV_BUDGET = 13       # v_mov_b32 (25 before)
-VGPR_BUDGET = 128     # four waves per SIMD
+VGPR_BUDGET = 128     # four waves per SIMD: 512 VGPRs / 4
+ACCUM_SYM = "_ZN6svnicp12_GLOBAL__N_120k_stein_accumulate_wILi64ELi%dELb1ELb%dEEEvNS_9AccumArgsE"   # <64, WP, true, SVGD>
 
 
 def _makefile_flags():
@@ -69,15 +71,21 @@ def group_loop(asm, sym=SYM):
         st = body[n].strip()
         if st and not st.startswith((";", ".")) and cur <= depth[i]:
             cnt[st.split()[0]] += 1
+    return cnt, kernel_descriptor(asm, sym)
+
+
+def kernel_descriptor(asm, sym):
+    """next_free_vgpr and group_segment_fixed_size of kernel `sym`, from its .amdhsa_kernel block in `asm`."""
+    lines = asm.splitlines()
     meta = {}
-    k = next(n for n in range(s, len(lines)) if lines[n].split() == [".amdhsa_kernel", sym])
+    k = next(n for n in range(len(lines)) if lines[n].split() == [".amdhsa_kernel", sym])
     for l in lines[k:]:
         m = re.match(r"\s+\.amdhsa_(next_free_vgpr|group_segment_fixed_size)\s+(\d+)", l)
         if m:
             meta[m.group(1)] = int(m.group(2))
         if ".end_amdhsa_kernel" in l:
             break
-    return cnt, meta
+    return meta
 
 
 @pytest.fixture(scope="module")
@@ -103,3 +111,12 @@ def test_search_kernel_keeps_four_waves_per_simd(search_asm):
     _, meta = group_loop(search_asm)
     assert meta["next_free_vgpr"] <= VGPR_BUDGET
     assert 4 * meta["group_segment_fixed_size"] <= 160 * 1024   # four workgroups per CU in LDS
+
+
+@pytest.mark.parametrize("svgd", [False, True])
+@pytest.mark.parametrize("WP", [1, 2, 4])
+def test_accumulate_kernel_keeps_four_waves_per_simd(search_asm, WP, svgd):
+    """The plain accumulate kernels of 64-particle waves sit at the occupancy cliff (127, 127, 126 VGPRs in SVN mode, 120 in
+    SVGD mode): one register more than 128 and a SIMD holds three waves of them, not four."""
+    meta = kernel_descriptor(search_asm, ACCUM_SYM % (WP, int(svgd)))
+    assert meta["next_free_vgpr"] <= VGPR_BUDGET, meta
