@@ -598,6 +598,57 @@ int svnicp_map_download_normals(svnicp_map *map, double *out_xyz, int64_t cap_po
 int svnicp_map_score_poses(svnicp_map *map, const float *src_xyz, int64_t n, int src_mem_kind, const double *posesCx12, int64_t C,
                            int poses_mem_kind, double max_corr_dist, double *outCx4 /* host */);
 void *svnicp_map_scores_devptr(svnicp_map *map);   /* double [C][4] of the last scoring, NULL before one */
+/* ---- coarse-to-fine pose search against the map -------------------------------------------------
+ * svnicp_map_search_poses(map, src_xyz, n, src_mem_kind, guess_R, guess_t, opt, out): levels of scored nodes around `guess`, each
+ * level three times finer than the one before, only the `keep` best nodes of a level expanded.  Nodes are made, scored and
+ * ranked on the device in one enqueue: no host synchronisation and no host-to-device copy between levels.
+ *   lattice      every node is an integer vector k[6] on the finest lattice.  fine[a] = step[a] / (double)3^(levels-1), one
+ *                division (0 on an axis whose step is not finite and > 0); the correction of a node is x[a] = (double)k[a] *
+ *                fine[a], one multiplication, in the solver's parametrisation [x, y, z, rx, ry, rz].  m[a] = floor(extent[a] /
+ *                step[a] + 1e-9), 0 for extent 0; axis a is active iff m[a] >= 1; A is the number of active axes.
+ *   level 0      the nodes k[a] = j * 3^(levels-1), j = -m[a]..m[a], in lexicographic order with x slowest: prod(2m+1) nodes.
+ *                With levels == 1 this is the flat grid of k * step, bit for bit.
+ *   level l+1    for each kept node of level l in rank order and each offset o in {-1, 0, 1}^A (lexicographic over the active
+ *                axes, x slowest) the child k_parent + o * 3^(levels-2-l), at index rank * 3^A + offset index:
+ *                kept_l * 3^A nodes, kept_l = min(keep, count_l).  Children of distinct parents never coincide; children may
+ *                leave +-extent by less than half a level-0 step.
+ *   pose         guess * correction_to_pose(x), the total pose of a particle: R = G_R * Exp(x[3:6]) (Rodrigues), t[d] =
+ *                ((G_R[3d]*x0 + G_R[3d+1]*x1) + G_R[3d+2]*x2) + G_t[d]; float64, unfused.
+ *   record       per node {located, inliers, sum_d2, cost} with the bits svnicp_map_score_poses gives for that pose scored alone.
+ *   rank         ascending (cost, k lexicographic with x first); costs compare as doubles and are never NaN.  At level 0
+ *                lexicographic order is index order.
+ *   limits       1 <= levels <= 8, 1 <= keep <= 1024, every level's count <= 2^20, m[a] * 3^(levels-1) + (3^(levels-1) - 1) / 2
+ *                < 2^20 per axis, extents finite and >= 0, a finite step > 0 on an axis with an extent, max_corr_dist under the
+ *                gate rule of svnicp_map_score_poses, a finite guess, 0 <= n <= 2^31-1, no NULL among guess, opt and out:
+ *                otherwise SVNICP_ERR_INVALID and nothing is enqueued.  n == 0 and an empty map are not errors: all costs tie at
+ *                the squared gate and the lexicographically smallest nodes are kept.
+ *   out          levels, active_axes, nodes_scored (all levels), level_count / level_kept per level, fine_step, and of the best
+ *                node of the last level its lattice vector, correction, pose (R row-major, then t) and record; zero_record is
+ *                the level-0 record of the zero correction, i.e. of `guess` itself.
+ *   determinism  the same bits on every call, and with rows on the host or on the device.
+ *   side         none on the map, on svnicp_map_scores_devptr or on an earlier svnicp_map_query's rows and normals: the search
+ *   effects      has its own buffers, which hold every level until the next search.  A following svnicp_map_add_cloud leaves
+ *                the map bit for bit that of a map that never searched.
+ *   completion   returns with the map's stream synchronised. */
+#define SVNICP_MAP_SEARCH_MAX_LEVELS 8
+#define SVNICP_MAP_SEARCH_MAX_KEEP 1024
+typedef struct svnicp_map_search_opt { double extent[6], step[6]; int levels, keep; double max_corr_dist; } svnicp_map_search_opt;
+typedef struct svnicp_map_search {
+  int levels, active_axes; int64_t nodes_scored; int64_t level_count[8]; int32_t level_kept[8];
+  double fine_step[6]; int32_t best_lattice[6]; double best_correction[6], best_pose[12], best_record[4], zero_record[4];
+} svnicp_map_search;
+int svnicp_map_search_poses(svnicp_map *map, const float *src_xyz, int64_t n, int src_mem_kind,
+                            const double guess_R_rowmajor[9], const double guess_t[3],
+                            const svnicp_map_search_opt *opt, svnicp_map_search *out);
+/* the kept nodes of the last level of the last search in rank order, at most cap of them (host arrays; any output may be NULL;
+ * *n_out = how many there are, whatever cap is).  No device work.  SVNICP_ERR_INVALID before a search, or for cap < 0. */
+int svnicp_map_search_top(svnicp_map *map, int cap, int32_t *latticeNx6, double *correctionsNx6, double *posesNx12,
+                          double *recordsNx4, int *n_out);
+/* test tap: level `level` of the last search -- the first min(cap, count) nodes' lattice vectors, poses and records and the
+ * level's kept list (indices into the level, rank order, level_kept entries: size kept_indices for 1024); any output may be NULL.
+ * SVNICP_ERR_INVALID before a search, for a level outside [0, levels) or cap < 0. */
+int svnicp_map_search_level(svnicp_map *map, int level, int64_t cap, int32_t *latticeCx6, double *posesCx12, double *recordsCx4,
+                            int32_t *kept_indices, int64_t *count_out, int *kept_out);
 
 /* ---- test-only taps (parity tests; not part of the reference interface) -------------------- */
 int svnicp_get_candidates(svnicp_ctx *ctx, int32_t *outBK);          /* sourceKNN_idx_  SVGDICP.cpp:214 */

@@ -80,6 +80,23 @@ class ModesStruct(C.Structure):
                 ("R", C.c_double * (9 * MODES_MAX)), ("t", C.c_double * (3 * MODES_MAX))]
 
 
+MAP_SEARCH_MAX_LEVELS, MAP_SEARCH_MAX_KEEP = 8, 1024   # SVNICP_MAP_SEARCH_MAX_LEVELS, SVNICP_MAP_SEARCH_MAX_KEEP
+
+
+class MapSearchOptStruct(C.Structure):
+    """struct svnicp_map_search_opt (include/svnicp_hip.h)."""
+    _fields_ = [("extent", C.c_double * 6), ("step", C.c_double * 6), ("levels", C.c_int), ("keep", C.c_int),
+                ("max_corr_dist", C.c_double)]
+
+
+class MapSearchStruct(C.Structure):
+    """struct svnicp_map_search (include/svnicp_hip.h)."""
+    _fields_ = [("levels", C.c_int), ("active_axes", C.c_int), ("nodes_scored", C.c_int64),
+                ("level_count", C.c_int64 * MAP_SEARCH_MAX_LEVELS), ("level_kept", C.c_int32 * MAP_SEARCH_MAX_LEVELS),
+                ("fine_step", C.c_double * 6), ("best_lattice", C.c_int32 * 6), ("best_correction", C.c_double * 6),
+                ("best_pose", C.c_double * 12), ("best_record", C.c_double * 4), ("zero_record", C.c_double * 4)]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -149,6 +166,9 @@ def load_library():
     L.svnicp_map_score_poses.argtypes = [vp, vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_double, dp]
     L.svnicp_map_scores_devptr.argtypes = [vp]
     L.svnicp_map_scores_devptr.restype = vp
+    L.svnicp_map_search_poses.argtypes = [vp, vp, C.c_int64, C.c_int, dp, dp, C.POINTER(MapSearchOptStruct), C.POINTER(MapSearchStruct)]
+    L.svnicp_map_search_top.argtypes = [vp, C.c_int, ip, dp, dp, dp, C.POINTER(C.c_int)]
+    L.svnicp_map_search_level.argtypes = [vp, C.c_int, C.c_int64, ip, dp, dp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.svnicp_prep_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.svnicp_prep_destroy.argtypes = [vp]
     L.svnicp_prep_destroy.restype = None

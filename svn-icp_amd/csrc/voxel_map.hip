@@ -35,6 +35,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "map_score.hpp"
+#include "map_search.hpp"
 #include "plane_normal_device.hpp"
 #include "range_project_device.hpp"
 #include "voxel_table_device.hpp"
@@ -534,6 +535,15 @@ struct svnicp_map {
   GrowBuf<double> sc_poses, sc_psum, sc_out;
   GrowBuf<unsigned int> sc_pcnt;
   int64_t sc_C = 0;      // poses of the last scoring (0 before one)
+  // svnicp_map_search_poses: its own rows, the lattice vectors, poses and records of EVERY level (the tap reads them), the kept
+  // lists (kSearchMaxKeep indices per level), its own chunk records, and the staging block the host reads with one copy
+  GrowBuf<float> se_in;
+  GrowBuf<int32_t> se_lat, se_kept;
+  GrowBuf<double> se_poses, se_rec, se_psum, se_stage;
+  GrowBuf<unsigned int> se_pcnt;
+  std::vector<double> se_host;       // the staging block of the last search, as map_search.hpp lays it out
+  svnicp::MapSearchPlan se_plan{};   // the last search's lattice (se_done says whether there is one)
+  bool se_done = false;
   int64_t last_M = 0;
   // svnicp_map_query_normals: the last query's selection (sel_key2 / sel_off / sel_cnt over last_live entries) still describes
   // the table — set by svnicp_map_query, dropped by svnicp_map_add_cloud, svnicp_map_clear_seen_through and svnicp_map_clear
@@ -895,6 +905,118 @@ int svnicp_map_score_poses(svnicp_map* m, const float* src_xyz, int64_t n, int s
 }
 
 void* svnicp_map_scores_devptr(svnicp_map* m) { return m && m->sc_C > 0 ? (void*)m->sc_out.p : nullptr; }
+
+int svnicp_map_search_poses(svnicp_map* m, const float* src_xyz, int64_t n, int src_mem_kind, const double* guess_R, const double* guess_t,
+                            const svnicp_map_search_opt* opt, svnicp_map_search* out) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (!guess_R || !guess_t || !opt || !out)
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_poses: guess_R, guess_t, opt and out must not be NULL");
+  if (n < 0 || n > 0x7fffffffLL || (n > 0 && !src_xyz))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_poses: need 0 <= n <= 2^31-1 and rows for n > 0");
+  if (!(std::isfinite(opt->max_corr_dist) && opt->max_corr_dist > 0.0 && opt->max_corr_dist <= m->voxel))
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_poses: max_corr_dist must be finite, > 0 and <= voxel_size (the 3x3x3 block "
+                                       "holds the nearest point only up to that gate)");
+  svnicp::MapSearchPlan P{};
+  if (const char* why = svnicp::plan_map_search(opt->extent, opt->step, opt->levels, opt->keep, P))
+    return fail(m, SVNICP_ERR_INVALID, std::string("svnicp_map_search_poses: ") + why);
+  for (int j = 0; j < 12; ++j) {
+    P.grid.G[j] = j < 9 ? guess_R[j] : guess_t[j - 9];
+    if (!std::isfinite(P.grid.G[j])) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_poses: the guess must be finite");
+  }
+  HIPCHK(m, hipSetDevice(m->device));
+  m->se_done = false;
+  const double thr2 = opt->max_corr_dist * opt->max_corr_dist;
+  const float* din = src_xyz;
+  if (n > 0 && src_mem_kind != SVNICP_MEM_DEVICE) {
+    HIPCHK(m, m->se_in.ensure((size_t)n * 3));
+    HIPCHK(m, hipMemcpyAsync(m->se_in.p, src_xyz, (size_t)n * 12, hipMemcpyHostToDevice, m->stream));
+    din = m->se_in.p;
+  }
+  // every buffer at its final size before the first launch: growing one would drop the levels it already holds
+  const int64_t chunks = svnicp::map_score_chunks(n);
+  const size_t recs = (size_t)(P.max_count < svnicp::kScorePoseBatch ? P.max_count : svnicp::kScorePoseBatch) * (size_t)chunks;
+  const int n_top = P.kept[P.levels - 1];
+  const size_t stage_bytes = svnicp::map_search_stage_bytes(n_top);
+  HIPCHK(m, m->se_lat.ensure((size_t)P.total * 6));
+  HIPCHK(m, m->se_poses.ensure((size_t)P.total * 12));
+  HIPCHK(m, m->se_rec.ensure((size_t)P.total * SVNICP_MAP_SCORE_FIELDS));
+  HIPCHK(m, m->se_kept.ensure((size_t)svnicp::kSearchMaxLevels * svnicp::kSearchMaxKeep));
+  HIPCHK(m, m->se_pcnt.ensure(2 * recs)); HIPCHK(m, m->se_psum.ensure(recs));
+  HIPCHK(m, m->se_stage.ensure(stage_bytes / 8));
+  HIPCHK(m, hipMemsetAsync(m->se_kept.p, 0, (size_t)svnicp::kSearchMaxLevels * svnicp::kSearchMaxKeep * 4, m->stream));
+  const svnicp::MapTableView T{m->keys.p, m->counts.p, m->pts.p, m->cap, m->max_points, (float)m->voxel};
+  for (int l = 0; l < P.levels; ++l) {   // per level: nodes, score (one or two launches per 32768 poses), rank
+    int32_t* lat = m->se_lat.p + 6 * P.first[l];
+    double* poses = m->se_poses.p + 12 * P.first[l];
+    double* rec = m->se_rec.p + SVNICP_MAP_SCORE_FIELDS * P.first[l];
+    int32_t* kept = m->se_kept.p + (size_t)l * svnicp::kSearchMaxKeep;
+    HIPCHK(m, svnicp::launch_map_search_nodes(P.grid, l, P.levels, P.count[l], l ? m->se_lat.p + 6 * P.first[l - 1] : nullptr,
+                                              l ? kept - svnicp::kSearchMaxKeep : nullptr, lat, poses, m->stream));
+    HIPCHK(m, svnicp::launch_map_score(T, din, n, poses, P.count[l], thr2, m->se_pcnt.p, m->se_psum.p, rec, m->stream));
+    HIPCHK(m, svnicp::launch_map_search_rank(rec, lat, P.count[l], P.kept[l], kept, m->stream));
+  }
+  const int last = P.levels - 1;
+  HIPCHK(m, svnicp::launch_map_search_gather(P.grid, m->se_lat.p + 6 * P.first[last], m->se_poses.p + 12 * P.first[last],
+                                             m->se_rec.p + SVNICP_MAP_SCORE_FIELDS * P.first[last],
+                                             m->se_kept.p + (size_t)last * svnicp::kSearchMaxKeep, n_top,
+                                             m->se_rec.p + SVNICP_MAP_SCORE_FIELDS * P.zero_index, m->se_stage.p, m->stream));
+  m->se_host.resize(stage_bytes / 8);
+  HIPCHK(m, hipMemcpyAsync(m->se_host.data(), m->se_stage.p, stage_bytes, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));   // complete when the call returns: the caller's rows are free again
+  m->se_plan = P;
+  m->se_done = true;
+  std::memset(out, 0, sizeof *out);
+  out->levels = P.levels; out->active_axes = P.active_axes; out->nodes_scored = P.total;
+  for (int l = 0; l < P.levels; ++l) { out->level_count[l] = P.count[l]; out->level_kept[l] = P.kept[l]; }
+  std::memcpy(out->fine_step, P.grid.fine, sizeof out->fine_step);
+  const double* h = m->se_host.data();
+  std::memcpy(out->zero_record, h, 4 * 8);
+  std::memcpy(out->best_correction, h + 4, 6 * 8);
+  std::memcpy(out->best_pose, h + 10, 12 * 8);
+  std::memcpy(out->best_record, h + 22, 4 * 8);
+  std::memcpy(out->best_lattice, h + 4 + svnicp::kSearchTopDoubles * n_top, 6 * 4);
+  return SVNICP_OK;
+}
+
+int svnicp_map_search_top(svnicp_map* m, int cap, int32_t* latticeNx6, double* correctionsNx6, double* posesNx12, double* recordsNx4,
+                          int* n_out) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (!m->se_done) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_top: no successful svnicp_map_search_poses yet");
+  if (cap < 0) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_top: cap must be >= 0");
+  const int n_top = m->se_plan.kept[m->se_plan.levels - 1];
+  if (n_out) *n_out = n_top;
+  const int k = cap < n_top ? cap : n_top;
+  const double* h = m->se_host.data() + 4;
+  const int32_t* hl = reinterpret_cast<const int32_t*>(h + svnicp::kSearchTopDoubles * n_top);
+  for (int i = 0; i < k; ++i, h += svnicp::kSearchTopDoubles) {
+    if (latticeNx6) std::memcpy(latticeNx6 + 6 * i, hl + 6 * i, 6 * 4);
+    if (correctionsNx6) std::memcpy(correctionsNx6 + 6 * i, h, 6 * 8);
+    if (posesNx12) std::memcpy(posesNx12 + 12 * i, h + 6, 12 * 8);
+    if (recordsNx4) std::memcpy(recordsNx4 + 4 * i, h + 18, 4 * 8);
+  }
+  return SVNICP_OK;
+}
+
+int svnicp_map_search_level(svnicp_map* m, int level, int64_t cap, int32_t* latticeCx6, double* posesCx12, double* recordsCx4,
+                            int32_t* kept_indices, int64_t* count_out, int* kept_out) {
+  if (!m) return SVNICP_ERR_INVALID;
+  if (!m->se_done) return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_level: no successful svnicp_map_search_poses yet");
+  const svnicp::MapSearchPlan& P = m->se_plan;
+  if (level < 0 || level >= P.levels || cap < 0)
+    return fail(m, SVNICP_ERR_INVALID, "svnicp_map_search_level: need 0 <= level < levels of the last search and cap >= 0");
+  HIPCHK(m, hipSetDevice(m->device));
+  if (count_out) *count_out = P.count[level];
+  if (kept_out) *kept_out = P.kept[level];
+  const size_t c = (size_t)(cap < P.count[level] ? cap : P.count[level]);
+  const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+  if (c && latticeCx6) HIPCHK(m, hipMemcpyAsync(latticeCx6, m->se_lat.p + 6 * P.first[level], c * 24, d2h, m->stream));
+  if (c && posesCx12) HIPCHK(m, hipMemcpyAsync(posesCx12, m->se_poses.p + 12 * P.first[level], c * 96, d2h, m->stream));
+  if (c && recordsCx4) HIPCHK(m, hipMemcpyAsync(recordsCx4, m->se_rec.p + 4 * P.first[level], c * 32, d2h, m->stream));
+  if (kept_indices)
+    HIPCHK(m, hipMemcpyAsync(kept_indices, m->se_kept.p + (size_t)level * svnicp::kSearchMaxKeep, (size_t)P.kept[level] * 4, d2h, m->stream));
+  HIPCHK(m, hipStreamSynchronize(m->stream));
+  return SVNICP_OK;
+}
 
 void* svnicp_map_points_devptr(svnicp_map* m) { return m ? (void*)m->out.p : nullptr; }
 

@@ -13,7 +13,10 @@
 //      modes mean|heaviest link_trans link_rot: PipelineConfig::mode_link_* / mode_select_heaviest, one more line per registered scan:
 //      "modes <scan>: n_modes n_reported nonfinite has_scores" and per reported mode " | label count best mass mean[0..5]" with %.17g;
 //      clear 1: PipelineConfig::clear_seen_through with its defaults (window 1 x 1, margins 0.3 m / 0.02) and the HDL-64E sensor,
-//      one more line per registered scan: "clear <scan>: points_removed")
+//      one more line per registered scan: "clear <scan>: points_removed";
+//      after those, seven more: seed_levels seed_keep seed_skip_fitness extent_xy extent_yaw step_xy step_yaw -- seed_levels > 0 turns
+//      PipelineConfig::seed_grid on with that x / y / yaw grid (1 = the flat grid, > 1 = the coarse-to-fine search), one more line per
+//      seeded scan: "seed <scan>: searched levels nodes_scored fitness_zero cost_zero cost correction[x] [y] [yaw]" with %.17g)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -52,6 +55,11 @@ int main(int argc, char** argv) {
     cfg.mode_select_heaviest = std::string(argv[14]) == "heaviest";
   }
   cfg.clear_seen_through = argc > 17 && atoi(argv[17]) != 0;
+  if (argc > 24 && atoi(argv[18]) > 0) {
+    const double exy = atof(argv[21]), eyaw = atof(argv[22]), sxy = atof(argv[23]), syaw = atof(argv[24]);
+    cfg.seed_grid = std::make_pair(std::array<double, 6>{exy, exy, 0, 0, 0, eyaw}, std::array<double, 6>{sxy, sxy, 0, 0, 0, syaw});
+    cfg.seed_levels = atoi(argv[18]); cfg.seed_keep = atoi(argv[19]); cfg.seed_skip_fitness = atof(argv[20]);
+  }
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;
@@ -94,6 +102,10 @@ int main(int argc, char** argv) {
                in.eigval[2], in.eigval[3], in.eigval[4], in.eigval[5]);
       }
       if (cfg.clear_seen_through && r.aligned) printf("clear %d: %lld\n", s, (long long)r.cleared);
+      if (r.seed)
+        printf("seed %d: %d %d %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", s, r.seed->searched ? 1 : 0, r.seed->levels,
+               (long long)r.seed->nodes_scored, r.seed->fitness_zero, r.seed->cost_zero, r.seed->cost, r.seed->correction[0],
+               r.seed->correction[1], r.seed->correction[5]);
       if (r.modes) {
         const svnicp_modes& m = *r.modes;
         printf("modes %d: %d %d %d %d", s, (int)m.n_modes, (int)m.n_reported, (int)m.nonfinite, (int)m.has_scores);

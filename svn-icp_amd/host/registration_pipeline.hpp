@@ -398,6 +398,30 @@ inline Cloud segment_scan(const Cloud& pts, const svnicp_seg_params& prm, std::v
   return out;
 }
 
+// what a coarse-to-fine pose search returns (svnicp_map_search_poses, include/svnicp_hip.h; the helpers are further down)
+using Lattice = std::vector<std::array<int32_t, 6>>;   // integer vectors on the finest lattice of a search
+struct MapSearchLevel {   // one level: its nodes, and the indices of the kept ones in rank order
+  Lattice lattice;
+  std::vector<double> poses12, records;
+  std::vector<int32_t> kept;
+};
+struct MapSearchResult {
+  int levels = 0, active_axes = 0;
+  int64_t nodes_scored = 0;
+  std::vector<int64_t> level_count;
+  std::vector<int32_t> level_kept;
+  std::array<double, 6> fine_step{}, best_correction{};
+  std::array<int32_t, 6> best_lattice{};
+  std::array<double, 12> best_pose{};
+  std::array<double, 4> best_record{}, zero_record{};
+  double cost_level0 = 0;   // the best cost of level 0
+  // the kept nodes of the last level in rank order
+  Lattice top_lattice;
+  std::vector<std::array<double, 6>> top_corrections;
+  std::vector<double> top_poses12, top_records;
+  std::vector<MapSearchLevel> level;   // every level (the host restatement only)
+};
+
 // ------------------------------------------------------------------------------------------------ local map
 // svnicp::VoxelHashMap (src/core/VoxelHashMap.cpp:22-101): voxel -> at most max_points points in insertion order; voxel index
 // = coordinates / voxel_size truncated TOWARD ZERO (Eigen cast<int>, :29); a voxel is dropped when its FIRST point is
@@ -531,6 +555,11 @@ class VoxelHashMap {
     }
     return out;
   }
+  // svnicp_map_search_poses restated from ScorePoses and the lattice helpers below (search_lattice, search_children,
+  // search_rank), the lattice and the ranks with the bits of pipeline.py's VoxelHashMap.search_poses; every level is kept.
+  // Throws std::invalid_argument where the C call answers SVNICP_ERR_INVALID.
+  MapSearchResult SearchPoses(const Cloud& rows, const Pose3& guess, const std::array<double, 6>& extent, const std::array<double, 6>& step,
+                              int levels, int keep, double gate) const;
   Cloud GetMap() const {
     Cloud out;
     for (const auto& kv : map_) out.insert(out.end(), kv.second.begin(), kv.second.end());
@@ -620,8 +649,47 @@ class DeviceVoxelMap {
     if (n) chk(svnicp_map_download_normals(m_, o.data(), n, &n));
     return o;
   }
+  // coarse-to-fine search around `guess` (svnicp_map_search_poses; VoxelHashMap::SearchPoses is the host restatement): the
+  // struct's fields, the kept nodes of the last level (svnicp_map_search_top) and level 0's best cost; rows on the host / in HBM
+  MapSearchResult SearchPoses(const Cloud& rows, const Pose3& guess, const std::array<double, 6>& extent, const std::array<double, 6>& step,
+                              int levels, int keep, double gate) {
+    return search(rows.empty() ? nullptr : &rows[0][0], (int64_t)rows.size(), SVNICP_MEM_HOST, guess, extent, step, levels, keep, gate);
+  }
+  MapSearchResult SearchPosesDevice(const float* dev_xyz, int64_t n, const Pose3& guess, const std::array<double, 6>& extent,
+                                    const std::array<double, 6>& step, int levels, int keep, double gate) {
+    return search(dev_xyz, n, SVNICP_MEM_DEVICE, guess, extent, step, levels, keep, gate);
+  }
 
  private:
+  MapSearchResult search(const float* xyz, int64_t n, int mem, const Pose3& guess, const std::array<double, 6>& extent,
+                         const std::array<double, 6>& step, int levels, int keep, double gate) {
+    svnicp_map_search_opt opt{};
+    std::copy(extent.begin(), extent.end(), opt.extent);
+    std::copy(step.begin(), step.end(), opt.step);
+    opt.levels = levels; opt.keep = keep; opt.max_corr_dist = gate;
+    svnicp_map_search s{};
+    chk(svnicp_map_search_poses(m_, xyz, n, mem, guess.R.data(), guess.t.data(), &opt, &s));
+    MapSearchResult r;
+    r.levels = s.levels; r.active_axes = s.active_axes; r.nodes_scored = s.nodes_scored;
+    r.level_count.assign(s.level_count, s.level_count + s.levels);
+    r.level_kept.assign(s.level_kept, s.level_kept + s.levels);
+    std::copy(s.fine_step, s.fine_step + 6, r.fine_step.begin());
+    std::copy(s.best_lattice, s.best_lattice + 6, r.best_lattice.begin());
+    std::copy(s.best_correction, s.best_correction + 6, r.best_correction.begin());
+    std::copy(s.best_pose, s.best_pose + 12, r.best_pose.begin());
+    std::copy(s.best_record, s.best_record + 4, r.best_record.begin());
+    std::copy(s.zero_record, s.zero_record + 4, r.zero_record.begin());
+    const int n_top = s.level_kept[s.levels - 1];
+    r.top_lattice.resize((size_t)n_top); r.top_corrections.resize((size_t)n_top);
+    r.top_poses12.resize((size_t)12 * n_top); r.top_records.resize((size_t)4 * n_top);
+    int got = 0;
+    chk(svnicp_map_search_top(m_, n_top, &r.top_lattice[0][0], &r.top_corrections[0][0], r.top_poses12.data(), r.top_records.data(), &got));
+    std::vector<double> rec0((size_t)4 * s.level_count[0]);
+    std::vector<int32_t> kept0((size_t)s.level_kept[0]);
+    chk(svnicp_map_search_level(m_, 0, s.level_count[0], nullptr, nullptr, rec0.data(), kept0.data(), nullptr, nullptr));
+    r.cost_level0 = rec0[(size_t)4 * kept0[0] + 3];
+    return r;
+  }
   std::vector<double> score(const float* xyz, int64_t n, int mem, const std::vector<double>& poses12, double gate) {
     const int64_t C = (int64_t)(poses12.size() / 12);
     std::vector<double> out((size_t)SVNICP_MAP_SCORE_FIELDS * (size_t)std::max<int64_t>(C, 0));
@@ -689,6 +757,137 @@ inline std::vector<size_t> seed_from_scores(const std::vector<double>& scores, s
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return scores[4 * a + 3] < scores[4 * b + 3]; });
   order.resize(P);
   return order;
+}
+
+// ---- the coarse-to-fine search: the lattice of svnicp_map_search_poses (include/svnicp_hip.h), as in pipeline.py -------------
+struct SearchLattice {
+  std::array<int64_t, 6> m{};     // level 0: j = -m..m per axis
+  std::array<double, 6> fine{};   // step / 3^(levels-1), 0 on an axis without a usable step
+  std::vector<int> active;        // the axes with m >= 1
+  Lattice level0;                 // j * 3^(levels-1), lexicographic, x slowest
+  size_t zero = 0;                // level 0's node of the zero correction
+  std::vector<int64_t> count;     // nodes per level
+  std::vector<int32_t> kept;      // min(keep, count)
+};
+inline int64_t pow3(int e) { int64_t p = 1; while (e-- > 0) p *= 3; return p; }
+
+// throws std::invalid_argument for what the C call refuses: levels outside 1..8, keep outside 1..1024, a bad extent or step, a
+// level over 2^20 nodes, m * 3^(levels-1) + (3^(levels-1) - 1) / 2 >= 2^20
+inline SearchLattice search_lattice(const std::array<double, 6>& extent, const std::array<double, 6>& step, int levels, int keep) {
+  if (levels < 1 || levels > SVNICP_MAP_SEARCH_MAX_LEVELS) throw std::invalid_argument("search_lattice: need 1 <= levels <= 8");
+  if (keep < 1 || keep > SVNICP_MAP_SEARCH_MAX_KEEP) throw std::invalid_argument("search_lattice: need 1 <= keep <= 1024");
+  const int64_t top = pow3(levels - 1), lim = (int64_t)1 << 20;
+  SearchLattice L;
+  int64_t c0 = 1;
+  for (int a = 0; a < 6; ++a) {
+    const double e = extent[a], s = step[a];
+    if (!(std::isfinite(e) && e >= 0)) throw std::invalid_argument("search_lattice: extents must be finite and >= 0");
+    int64_t m = 0;
+    if (e != 0.0) {
+      if (!(std::isfinite(s) && s > 0)) throw std::invalid_argument("search_lattice: an axis with a non-zero extent needs a finite step > 0");
+      const double q = std::floor(e / s + kGridSlack);
+      m = q < (double)lim ? (int64_t)q : lim;
+    }
+    if (m * top + (top - 1) / 2 >= lim) throw std::invalid_argument("search_lattice: lattice overflow");
+    L.m[a] = m;
+    L.fine[a] = (std::isfinite(s) && s > 0) ? s / (double)top : 0.0;
+    if (m >= 1) L.active.push_back(a);
+    c0 *= 2 * m + 1;
+    if (c0 > lim) throw std::invalid_argument("search_lattice: a level holds more than 2^20 nodes");
+    L.zero = L.zero * (size_t)(2 * m + 1) + (size_t)m;
+  }
+  const int64_t children = pow3((int)L.active.size());
+  for (int l = 0; l < levels; ++l) {
+    const int64_t c = l == 0 ? c0 : (int64_t)L.kept.back() * children;
+    if (c > lim) throw std::invalid_argument("search_lattice: a level holds more than 2^20 nodes");
+    L.count.push_back(c);
+    L.kept.push_back((int32_t)std::min<int64_t>(keep, c));
+  }
+  L.level0.resize((size_t)c0);
+  for (size_t i = 0; i < (size_t)c0; ++i) {
+    size_t r = i;
+    for (int a = 5; a >= 0; --a) {
+      const int64_t w = 2 * L.m[a] + 1;
+      L.level0[i][a] = (int32_t)(((int64_t)(r % (size_t)w) - L.m[a]) * top);
+      r /= (size_t)w;
+    }
+  }
+  return L;
+}
+
+// the nodes of level `level`+1 from the kept nodes of level `level` in rank order: child index = rank * 3^A + offset index
+inline Lattice search_children(const Lattice& kept_lattice, int level, int levels, const std::vector<int>& active) {
+  const int64_t scale = pow3(levels - 2 - level), children = pow3((int)active.size());
+  Lattice out;
+  out.reserve(kept_lattice.size() * (size_t)children);
+  for (const auto& parent : kept_lattice)
+    for (int64_t o = 0; o < children; ++o) {
+      std::array<int32_t, 6> k = parent;
+      int64_t r = o;
+      for (int j = (int)active.size() - 1; j >= 0; --j) { k[active[j]] += (int32_t)((r % 3 - 1) * scale); r /= 3; }
+      out.push_back(k);
+    }
+  return out;
+}
+
+// the indices of the min(keep, count) best nodes in rank order: ascending (cost, lattice vector lexicographic, x first)
+inline std::vector<int32_t> search_rank(const std::vector<double>& records, const Lattice& lattice, int keep) {
+  if (records.size() != 4 * lattice.size()) throw std::invalid_argument("search_rank: one record per lattice vector");
+  std::vector<int32_t> order(lattice.size());
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    const double ca = records[4 * (size_t)a + 3], cb = records[4 * (size_t)b + 3];
+    return ca != cb ? ca < cb : lattice[a] < lattice[b];
+  });
+  order.resize(std::min(order.size(), (size_t)keep));
+  return order;
+}
+
+// x = (double)k * fine: one multiplication per entry
+inline std::vector<std::array<double, 6>> search_corrections(const Lattice& lattice, const std::array<double, 6>& fine) {
+  std::vector<std::array<double, 6>> x(lattice.size());
+  for (size_t i = 0; i < lattice.size(); ++i)
+    for (int a = 0; a < 6; ++a) x[i][a] = (double)lattice[i][a] * fine[a];
+  return x;
+}
+
+inline MapSearchResult VoxelHashMap::SearchPoses(const Cloud& rows, const Pose3& guess, const std::array<double, 6>& extent,
+                                                 const std::array<double, 6>& step, int levels, int keep, double gate) const {
+  if (!(std::isfinite(gate) && gate > 0 && gate <= voxel_size_))
+    throw std::invalid_argument("VoxelHashMap::SearchPoses: the gate must be finite, > 0 and <= voxel_size");
+  for (int i = 0; i < 9; ++i) if (!std::isfinite(guess.R[i])) throw std::invalid_argument("VoxelHashMap::SearchPoses: the guess must be finite");
+  for (int i = 0; i < 3; ++i) if (!std::isfinite(guess.t[i])) throw std::invalid_argument("VoxelHashMap::SearchPoses: the guess must be finite");
+  const SearchLattice L = search_lattice(extent, step, levels, keep);
+  MapSearchResult r;
+  r.levels = levels; r.active_axes = (int)L.active.size();
+  r.level_count = L.count; r.level_kept = L.kept; r.fine_step = L.fine;
+  for (int l = 0; l < levels; ++l) {
+    MapSearchLevel lv;
+    if (l == 0) lv.lattice = L.level0;
+    else {
+      Lattice parents;
+      for (int32_t i : r.level.back().kept) parents.push_back(r.level.back().lattice[(size_t)i]);
+      lv.lattice = search_children(parents, l - 1, levels, L.active);
+    }
+    lv.poses12 = correction_poses(guess, search_corrections(lv.lattice, L.fine));
+    lv.records = ScorePoses(rows, lv.poses12, gate);
+    lv.kept = search_rank(lv.records, lv.lattice, keep);
+    r.nodes_scored += (int64_t)lv.lattice.size();
+    r.level.push_back(std::move(lv));
+  }
+  const MapSearchLevel& last = r.level.back();
+  for (int32_t i : last.kept) {
+    r.top_lattice.push_back(last.lattice[(size_t)i]);
+    r.top_poses12.insert(r.top_poses12.end(), last.poses12.begin() + 12 * (size_t)i, last.poses12.begin() + 12 * (size_t)i + 12);
+    r.top_records.insert(r.top_records.end(), last.records.begin() + 4 * (size_t)i, last.records.begin() + 4 * (size_t)i + 4);
+  }
+  r.top_corrections = search_corrections(r.top_lattice, L.fine);
+  r.best_lattice = r.top_lattice[0]; r.best_correction = r.top_corrections[0];
+  std::copy(r.top_poses12.begin(), r.top_poses12.begin() + 12, r.best_pose.begin());
+  std::copy(r.top_records.begin(), r.top_records.begin() + 4, r.best_record.begin());
+  std::copy(r.level[0].records.begin() + 4 * L.zero, r.level[0].records.begin() + 4 * L.zero + 4, r.zero_record.begin());
+  r.cost_level0 = r.level[0].records[4 * (size_t)r.level[0].kept[0] + 3];
+  return r;
 }
 
 // crop_pointcloud + the two uniform samplings on the device (svnicp_prep_*, csrc/scan_prep.hip): the raw scan is uploaded
@@ -816,6 +1015,11 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   double seed_gate = 0.0;           // with seed_grid: the inlier gate of that scoring, at most map_voxel_size; 0 = map_voxel_size
   std::string seed_mode = "best";   // "best": the initial mean becomes prediction * correction_to_pose(best node), the particles are
                                     // drawn as ever; "top": the mean stays the prediction, the particles are the particle_count best nodes
+  int seed_levels = 1;              // with seed_grid: > 1 = coarse-to-fine (SearchPoses): seed_grid is level 0, every further level is three
+                                    // times finer and expands the seed_keep best nodes of the one before; 1 = the flat grid
+  int seed_keep = 8;                // with seed_levels > 1: nodes of a level that are expanded ("top": at least particle_count are kept)
+  double seed_skip_fitness = 0.0;   // with seed_grid: > 0 = the prediction alone is scored first, and with inliers / rows at or above this
+                                    // no search is made and the registration starts as without seeding; 0 = every scan is searched
 };
 
 struct ScanResult {
@@ -838,6 +1042,17 @@ struct ScanResult {
     std::array<double, 6> correction{};    // the correction applied to the initial mean ("top": zeros)
     Pose3 prediction;                      // the constant-velocity prediction the grid is centred on
     std::vector<size_t> nodes;             // "top": the nodes handed over as particles, best first
+    // cfg.seed_skip_fitness > 0: was the search made, and inliers / rows of the prediction alone (-1 where it was not computed)
+    bool searched = true;
+    double fitness_zero = -1;
+    // cfg.seed_levels > 1 (index and nodes are unused then): the search's levels, the best node's lattice vector, the finest
+    // step, the nodes scored, the best cost of level 0, and with "top" the lattice vectors handed over as particles
+    int levels = 1;
+    std::array<int32_t, 6> lattice{};
+    std::array<double, 6> fine_step{};
+    int64_t nodes_scored = 0;
+    double cost_level0 = 0;
+    Lattice node_lattice;
   };
   std::optional<Seed> seed;                        // cfg.seed_grid
 };
@@ -874,8 +1089,21 @@ class RegistrationPipeline {
       throw std::invalid_argument("PipelineConfig: seed_gate must be finite, >= 0 (0 = map_voxel_size) and at most map_voxel_size");
     if (cfg.seed_grid) {
       seed_nodes_ = correction_grid(cfg.seed_grid->first, cfg.seed_grid->second, &seed_zero_);   // throws for a bad grid
-      if (cfg.seed_mode == "top" && seed_nodes_.size() < (size_t)cfg.particle_count)
+      if (cfg.seed_mode == "top" && cfg.seed_levels == 1 && seed_nodes_.size() < (size_t)cfg.particle_count)
         throw std::invalid_argument("PipelineConfig: seed_mode \"top\" needs at least particle_count nodes in seed_grid");
+    }
+    if (cfg.seed_levels < 1 || cfg.seed_levels > SVNICP_MAP_SEARCH_MAX_LEVELS) throw std::invalid_argument("PipelineConfig: seed_levels must lie in 1..8");
+    if (cfg.seed_keep < 1 || cfg.seed_keep > SVNICP_MAP_SEARCH_MAX_KEEP) throw std::invalid_argument("PipelineConfig: seed_keep must lie in 1..1024");
+    if (!(std::isfinite(cfg.seed_skip_fitness) && cfg.seed_skip_fitness >= 0 && cfg.seed_skip_fitness <= 1))
+      throw std::invalid_argument("PipelineConfig: seed_skip_fitness must lie in [0, 1] (0 = every scan is searched)");
+    if (!cfg.seed_grid && (cfg.seed_levels > 1 || cfg.seed_skip_fitness > 0))
+      throw std::invalid_argument("PipelineConfig: seed_levels > 1 and seed_skip_fitness > 0 need seed_grid (level 0 of the search)");
+    if (cfg.seed_grid && cfg.seed_levels > 1) {
+      if (cfg.seed_mode == "top" && cfg.particle_count > SVNICP_MAP_SEARCH_MAX_KEEP)
+        throw std::invalid_argument("PipelineConfig: seed_mode \"top\" with seed_levels > 1 hands over at most 1024 nodes (particle_count)");
+      const SearchLattice L = search_lattice(cfg.seed_grid->first, cfg.seed_grid->second, cfg.seed_levels, seed_search_keep());   // throws
+      if (cfg.seed_mode == "top" && L.count.back() < (int64_t)cfg.particle_count)
+        throw std::invalid_argument("PipelineConfig: seed_mode \"top\" needs at least particle_count nodes in the last level of the search");
     }
     if (cfg.clear_seen_through) {
       clear_opt_ = svnicp_visibility_opt{(int32_t)sizeof(svnicp_visibility_opt), cfg.clear_window_rows, cfg.clear_window_cols, (float)cfg.clear_margin_abs,
@@ -951,9 +1179,49 @@ class RegistrationPipeline {
     std::vector<double> src64;
     if (!dprep_) src64 = widen(source);                                                                // ICPUtils.cpp:27-43
     if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{cfg_.weight_dist > 0, cfg_.weight_dist, cfg_.weight_temperature}, cfg_.device);
-    if (cfg_.seed_grid) {   // no policy here: every scan is searched, and the best node is taken as it comes
+    bool search = (bool)cfg_.seed_grid;
+    const double gate = cfg_.seed_gate > 0 ? cfg_.seed_gate : cfg_.map_voxel_size;
+    double fitness_zero = -1;
+    if (search && cfg_.seed_skip_fitness > 0) {   // the only policy: the prediction alone first (one pose, the same call)
+      const std::vector<double> one = correction_poses(guess, {std::array<double, 6>{}});
+      std::vector<double> rec;
+      const int64_t n = dprep_ ? dprep_->n_source : (int64_t)source.size();
+      if (dprep_) rec = dmap_->ScorePosesDevice(dprep_->source_f32(), dprep_->n_source, one, gate);
+      else if (dmap_) { rec = dmap_->ScorePoses(source, one, gate); bytes_h2d_ += source.size() * 12; }
+      else rec = map_.ScorePoses(source, one, gate);
+      fitness_zero = n > 0 ? rec[1] / (double)n : 0.0;
+      if (fitness_zero >= cfg_.seed_skip_fitness) {
+        search = false;
+        ScanResult::Seed sd;
+        sd.searched = false; sd.fitness_zero = fitness_zero; sd.cost_zero = rec[3]; sd.prediction = guess;
+        res.seed = sd;
+      }
+    }
+    if (search && cfg_.seed_levels > 1) {   // coarse-to-fine: seed_grid is level 0
+      const auto& [ext, stp] = *cfg_.seed_grid;
+      const int keep = seed_search_keep();
+      const int64_t n = dprep_ ? dprep_->n_source : (int64_t)source.size();
+      MapSearchResult sr;
+      if (dprep_) sr = dmap_->SearchPosesDevice(dprep_->source_f32(), dprep_->n_source, guess, ext, stp, cfg_.seed_levels, keep, gate);
+      else if (dmap_) { sr = dmap_->SearchPoses(source, guess, ext, stp, cfg_.seed_levels, keep, gate); bytes_h2d_ += source.size() * 12; }
+      else sr = map_.SearchPoses(source, guess, ext, stp, cfg_.seed_levels, keep, gate);
+      ScanResult::Seed sd;
+      sd.cost = sr.best_record[3]; sd.cost_zero = sr.zero_record[3]; sd.cost_level0 = sr.cost_level0; sd.prediction = guess;
+      sd.levels = sr.levels; sd.lattice = sr.best_lattice; sd.fine_step = sr.fine_step; sd.nodes_scored = sr.nodes_scored;
+      sd.fitness_zero = fitness_zero >= 0 ? fitness_zero : (n > 0 ? sr.zero_record[1] / (double)n : 0.0);
+      if (cfg_.seed_mode == "top") {
+        const int P = cfg_.particle_count;
+        sd.node_lattice.assign(sr.top_lattice.begin(), sr.top_lattice.begin() + P);
+        for (int d = 0; d < 6; ++d)
+          for (int p = 0; p < P; ++p) init[(size_t)d * P + p] = sr.top_corrections[(size_t)p][d];
+      } else {
+        sd.correction = sr.best_correction;
+        guess = guess * correction_to_pose(sd.correction);
+        res.initial_guess = guess;
+      }
+      res.seed = sd;
+    } else if (search) {   // the flat grid: every node is scored, and the best node is taken as it comes
       const std::vector<double> poses12 = correction_poses(guess, seed_nodes_);
-      const double gate = cfg_.seed_gate > 0 ? cfg_.seed_gate : cfg_.map_voxel_size;
       std::vector<double> scores;
       if (dprep_) scores = dmap_->ScorePosesDevice(dprep_->source_f32(), dprep_->n_source, poses12, gate);   // not uploaded again
       else if (dmap_) { scores = dmap_->ScorePoses(source, poses12, gate); bytes_h2d_ += source.size() * 12; }
@@ -962,6 +1230,7 @@ class RegistrationPipeline {
       const std::vector<size_t> order = seed_from_scores(scores, top ? (size_t)cfg_.particle_count : 1);
       ScanResult::Seed sd;
       sd.index = order[0]; sd.cost = scores[4 * order[0] + 3]; sd.cost_zero = scores[4 * seed_zero_ + 3]; sd.prediction = guess;
+      sd.fitness_zero = fitness_zero;
       if (top) {
         sd.nodes = order;
         const int P = cfg_.particle_count;
@@ -1060,6 +1329,8 @@ class RegistrationPipeline {
 
   PipelineConfig cfg_;
   svnicp_visibility_opt clear_opt_{};
+  // the `keep` of the coarse-to-fine search: "top" needs particle_count nodes out of the last level
+  int seed_search_keep() const { return cfg_.seed_mode == "top" ? std::max(cfg_.seed_keep, cfg_.particle_count) : cfg_.seed_keep; }
   std::vector<std::array<double, 6>> seed_nodes_;   // cfg.seed_grid: the grid's nodes and the index of the zero correction
   size_t seed_zero_ = 0;
   VoxelHashMap map_;

@@ -604,6 +604,102 @@ def seed_from_scores(scores, corrections, P: int):
     return X[order[0]].copy(), X[order].copy(), order
 
 
+# ----------------------------------------------------------------------------- the coarse-to-fine search
+SEARCH_MAX_LEVELS = 8          # SVNICP_MAP_SEARCH_MAX_LEVELS
+SEARCH_MAX_KEEP = 1024         # SVNICP_MAP_SEARCH_MAX_KEEP
+_LAT_OFF = 1 << 20             # lattice entries lie in (-2^20, 2^20)
+
+
+def search_lattice(extent6, step6, levels: int):
+    """The lattice of svnicp_map_search_poses (include/svnicp_hip.h) -> (level-0 lattice int32 [C0, 6], fine step [6], m [6],
+    active axes).  Nodes are integer vectors on the finest lattice: fine = step / 3^(levels-1) (0 on an axis without a usable
+    step), m as correction_grid's, level 0 is j·3^(levels-1), j = -m..m, lexicographic with x slowest; an axis is active iff
+    m >= 1.  Refuses what the C call refuses."""
+    levels = int(levels)
+    if not 1 <= levels <= SEARCH_MAX_LEVELS:
+        raise ValueError("search_lattice: need 1 <= levels <= 8")
+    ext, stp = np.asarray(extent6, np.float64).reshape(-1), np.asarray(step6, np.float64).reshape(-1)
+    if ext.shape != (6,) or stp.shape != (6,):
+        raise ValueError("search_lattice: extent and step hold six entries [x, y, z, rx, ry, rz]")
+    if not (np.isfinite(ext).all() and (ext >= 0).all()):
+        raise ValueError("search_lattice: extents must be finite and >= 0")
+    top = 3 ** (levels - 1)
+    m, fine, count = [], [], 1
+    for e, s in zip(ext.tolist(), stp.tolist()):
+        k = 0
+        if e != 0.0:
+            if not (np.isfinite(s) and s > 0):
+                raise ValueError("search_lattice: an axis with a non-zero extent needs a finite step > 0")
+            q = e / s + _GRID_SLACK
+            k = int(math.floor(q)) if q < _LAT_OFF else _LAT_OFF
+        if k * top + (top - 1) // 2 >= _LAT_OFF:
+            raise ValueError("search_lattice: lattice overflow, m * 3^(levels-1) + (3^(levels-1) - 1) / 2 must stay below 2^20")
+        m.append(k)
+        fine.append(s / float(top) if (np.isfinite(s) and s > 0) else 0.0)
+        count *= 2 * k + 1
+        if count > SCORE_MAX_POSES:
+            raise ValueError("search_lattice: a level holds more than 2^20 nodes")
+    axes = [np.arange(-k, k + 1, dtype=np.int64) * top for k in m]
+    lat = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 6).astype(np.int32)
+    return lat, np.array(fine), m, [a for a in range(6) if m[a] >= 1]
+
+
+def search_level_counts(m, levels: int, keep: int):
+    """-> ([count per level], [kept per level]): count_0 = prod(2m+1), count_{l+1} = kept_l · 3^A, kept_l = min(keep, count_l).
+    Refuses a keep outside 1..1024 and a level over 2^20 nodes."""
+    if not 1 <= int(keep) <= SEARCH_MAX_KEEP:
+        raise ValueError("search: need 1 <= keep <= 1024")
+    children = 3 ** sum(1 for k in m if k >= 1)
+    counts, kept = [], []
+    for l in range(int(levels)):
+        c = int(np.prod([2 * k + 1 for k in m], dtype=object)) if l == 0 else kept[-1] * children
+        if c > SCORE_MAX_POSES:
+            raise ValueError("search: a level holds more than 2^20 nodes")
+        counts.append(c)
+        kept.append(min(int(keep), c))
+    return counts, kept
+
+
+def search_children(kept_lattice, level: int, levels: int, active):
+    """The nodes of level `level`+1 from the kept nodes of level `level` in rank order -> int32 [kept · 3^A, 6]: per parent the
+    offsets {-1, 0, 1}·3^(levels-2-level) over the active axes, lexicographic with x slowest; child index = rank·3^A + offset."""
+    K = np.asarray(kept_lattice, np.int64).reshape(-1, 6)
+    scale = 3 ** (int(levels) - 2 - int(level))
+    off = np.zeros((3 ** len(active), 6), np.int64)
+    if active:
+        grid = np.stack(np.meshgrid(*([np.array([-1, 0, 1])] * len(active)), indexing="ij"), -1).reshape(-1, len(active))
+        off[:, list(active)] = grid * scale
+    return (K[:, None, :] + off[None, :, :]).reshape(-1, 6).astype(np.int32)
+
+
+def search_rank(records, lattice, keep: int) -> np.ndarray:
+    """Indices of the min(keep, count) best nodes in rank order: ascending (cost, lattice vector lexicographic, x first)."""
+    sc = np.asarray(records, np.float64).reshape(-1, len(SCORE_FIELDS))
+    L = np.asarray(lattice, np.int64).reshape(-1, 6)
+    if sc.shape[0] != L.shape[0]:
+        raise ValueError("search_rank: one record per lattice vector")
+    return np.lexsort((L[:, 5], L[:, 4], L[:, 3], L[:, 2], L[:, 1], L[:, 0], sc[:, 3]))[:min(int(keep), L.shape[0])]
+
+
+def search_corrections(lattice, fine) -> np.ndarray:
+    """x = (double)k · fine: the corrections of lattice vectors, one multiplication each."""
+    return np.asarray(lattice, np.int32).reshape(-1, 6).astype(np.float64) * np.asarray(fine, np.float64).reshape(1, 6)
+
+
+def search_zero_index(m) -> int:
+    zero = 0
+    for k in m:
+        zero = zero * (2 * k + 1) + k
+    return zero
+
+
+def _check_search_guess(guess) -> np.ndarray:
+    G = np.asarray(guess, np.float64)
+    if G.shape != (4, 4) or not np.isfinite(G[:3]).all():
+        raise ValueError("search_poses: the guess must be a finite 4x4 pose")
+    return G
+
+
 class DeviceVoxelHashMap:
     """The same map resident in HBM (svnicp_map_* of the C ABI, csrc/voxel_map.hip): ``add_pointcloud`` uploads only the new
     points, ``get_map`` leaves the selected points in device memory as float64 rows and returns (device pointer, count) for
@@ -754,6 +850,66 @@ class DeviceVoxelHashMap:
         self._chk(self._L.svnicp_map_score_poses(self._h, ptr, n, mem, pptr, nposes, pmem, float(gate),
                                                  out.ctypes.data_as(C.POINTER(C.c_double))), "svnicp_map_score_poses")
         return out
+
+    def search_poses(self, cloud, guess, extent6, step6, levels: int, keep: int, gate: float) -> dict:
+        """Coarse-to-fine search around ``guess`` (svnicp_map_search_poses; the host restatement is VoxelHashMap.search_poses):
+        ``levels`` levels of scored nodes, each three times finer, the ``keep`` best of a level expanded.  -> the fields of
+        struct svnicp_map_search as a dict; ``search_top`` and ``search_level`` read the rest."""
+        pts = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 3))
+        self.bytes_uploaded += pts.nbytes
+        return self._search_poses(pts.ctypes.data_as(self._C.c_void_p) if pts.shape[0] else None, pts.shape[0], 0, guess, extent6, step6,
+                                  levels, keep, gate)
+
+    def search_poses_device(self, devptr: int, n: int, guess, extent6, step6, levels: int, keep: int, gate: float) -> dict:
+        """search_poses for float32 rows that already live in HBM (DevicePreprocessor.source_f32_ptr)."""
+        return self._search_poses(self._C.c_void_p(int(devptr)), int(n), 1, guess, extent6, step6, levels, keep, gate)
+
+    def _search_poses(self, ptr, n, mem, guess, extent6, step6, levels, keep, gate):
+        from . import binding
+        C = self._C
+        G = np.ascontiguousarray(np.asarray(guess, np.float64).reshape(4, 4))
+        R, t = np.ascontiguousarray(G[:3, :3]), np.ascontiguousarray(G[:3, 3])
+        opt = binding.MapSearchOptStruct()
+        opt.extent[:] = [float(v) for v in np.asarray(extent6, np.float64).reshape(6)]
+        opt.step[:] = [float(v) for v in np.asarray(step6, np.float64).reshape(6)]
+        opt.levels, opt.keep, opt.max_corr_dist = int(levels), int(keep), float(gate)
+        out = binding.MapSearchStruct()
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.svnicp_map_search_poses(self._h, ptr, n, mem, R.ctypes.data_as(dp), t.ctypes.data_as(dp), C.byref(opt),
+                                                  C.byref(out)), "svnicp_map_search_poses")
+        L = out.levels
+        return {"levels": L, "active_axes": out.active_axes, "nodes_scored": int(out.nodes_scored),
+                "level_count": [int(v) for v in out.level_count[:L]], "level_kept": [int(v) for v in out.level_kept[:L]],
+                "fine_step": np.array(out.fine_step[:]), "best_lattice": np.array(out.best_lattice[:], np.int32),
+                "best_correction": np.array(out.best_correction[:]), "best_pose": np.array(out.best_pose[:]),
+                "best_record": np.array(out.best_record[:]), "zero_record": np.array(out.zero_record[:])}
+
+    def search_top(self, cap: int = SEARCH_MAX_KEEP) -> dict:
+        """The kept nodes of the last search's last level in rank order, at most ``cap`` -> {"lattice" int32 [N,6], "corrections"
+        [N,6], "poses" [N,12], "records" [N,4]}."""
+        C = self._C
+        n = C.c_int(0)
+        self._chk(self._L.svnicp_map_search_top(self._h, 0, None, None, None, None, C.byref(n)), "svnicp_map_search_top")
+        N = min(int(cap), n.value)
+        lat, x, P, rec = np.zeros((N, 6), np.int32), np.zeros((N, 6)), np.zeros((N, 12)), np.zeros((N, 4))
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.svnicp_map_search_top(self._h, N, lat.ctypes.data_as(C.POINTER(C.c_int32)), x.ctypes.data_as(dp),
+                                                P.ctypes.data_as(dp), rec.ctypes.data_as(dp), C.byref(n)), "svnicp_map_search_top")
+        return {"lattice": lat, "corrections": x, "poses": P, "records": rec}
+
+    def search_level(self, level: int) -> dict:
+        """Level ``level`` of the last search (test tap) -> {"lattice" int32 [C,6], "poses" [C,12], "records" [C,4], "kept": the
+        indices of the kept nodes in rank order}."""
+        C = self._C
+        cnt, kept = C.c_int64(0), C.c_int(0)
+        self._chk(self._L.svnicp_map_search_level(self._h, int(level), 0, None, None, None, None, C.byref(cnt), C.byref(kept)),
+                  "svnicp_map_search_level")
+        N = int(cnt.value)
+        lat, P, rec, idx = np.zeros((N, 6), np.int32), np.zeros((N, 12)), np.zeros((N, 4)), np.zeros(kept.value, np.int32)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._chk(self._L.svnicp_map_search_level(self._h, int(level), N, lat.ctypes.data_as(ip), P.ctypes.data_as(dp), rec.ctypes.data_as(dp),
+                                                  idx.ctypes.data_as(ip), C.byref(cnt), C.byref(kept)), "svnicp_map_search_level")
+        return {"lattice": lat, "poses": P, "records": rec, "kept": idx}
 
     @property
     def scores_ptr(self) -> int:
@@ -1171,6 +1327,36 @@ class VoxelHashMap:
                 out[c0 + k] = (dk.size, inl.size, sm, (sm + (n - inl.size) * thr2) / n)
         return out
 
+    def search_poses(self, cloud, guess, extent6, step6, levels: int, keep: int, gate: float) -> dict:
+        """The numpy restatement of svnicp_map_search_poses (include/svnicp_hip.h), built on score_poses and the
+        lattice helpers -> the fields DeviceVoxelHashMap.search_poses returns, plus "top" (search_top's dict) and "level": per
+        level {"lattice", "corrections", "poses", "records", "kept"} (search_level's dict)."""
+        check_score_gate(gate, self.voxel_size)
+        G = _check_search_guess(guess)
+        lat, fine, m, active = search_lattice(extent6, step6, levels)
+        counts, kepts = search_level_counts(m, levels, keep)
+        rows = np.asarray(cloud, np.float32).reshape(-1, 3)
+        level = []
+        for l in range(int(levels)):
+            if l > 0:
+                prev = level[-1]
+                lat = search_children(prev["lattice"][prev["kept"]], l - 1, levels, active)
+            x = search_corrections(lat, fine)
+            poses = correction_poses(G, x)
+            rec = self.score_poses(rows, poses, gate)
+            level.append({"lattice": lat, "corrections": x, "poses": poses, "records": rec,
+                          "kept": search_rank(rec, lat, keep).astype(np.int32)})
+            assert lat.shape[0] == counts[l] and level[-1]["kept"].shape[0] == kepts[l]
+        last = level[-1]
+        order = last["kept"]
+        top = {"lattice": last["lattice"][order], "corrections": last["corrections"][order], "poses": last["poses"][order],
+               "records": last["records"][order]}
+        return {"levels": int(levels), "active_axes": len(active), "nodes_scored": int(sum(counts)), "level_count": counts,
+                "level_kept": kepts, "fine_step": fine, "best_lattice": top["lattice"][0].copy(),
+                "best_correction": top["corrections"][0].copy(), "best_pose": top["poses"][0].copy(),
+                "best_record": top["records"][0].copy(), "zero_record": level[0]["records"][search_zero_index(m)].copy(),
+                "top": top, "level": level}
+
     def get_map(self, pose=None, max_range: float | None = None) -> np.ndarray:
         if not self._vox:
             return np.zeros((0, 3))
@@ -1234,20 +1420,45 @@ class PipelineConfig:
     seed_gate: float = 0.0         # with seed_grid: the inlier gate of that scoring, at most map_voxel_size; 0 = map_voxel_size
     seed_mode: str = "best"        # "best": the registration's initial mean becomes prediction · correction_to_pose(best node), the particles are drawn as ever; "top": the mean stays the prediction and the particles are the particle_count best nodes
 
+    seed_levels: int = 1           # with seed_grid: > 1 = coarse-to-fine (search_poses): seed_grid is level 0, every further level is three times finer and expands the seed_keep best nodes of the one before; 1 = the flat grid
+    seed_keep: int = 8             # with seed_levels > 1: nodes of a level that are expanded ("top": at least particle_count are kept)
+    seed_skip_fitness: float = 0.0  # with seed_grid: > 0 = the prediction alone is scored first, and with inliers / rows at or above this no search is made and the registration starts as without seeding; 0 = every scan is searched
+
     def seed_nodes(self):
         """-> (corrections [C, 6], index of the zero correction) of seed_grid."""
         return correction_grid(*self.seed_grid)
 
+    def seed_search_keep(self) -> int:
+        """The `keep` of the coarse-to-fine search: "top" needs particle_count nodes out of the last level."""
+        return max(int(self.seed_keep), int(self.particle_count)) if self.seed_mode == "top" else int(self.seed_keep)
+
     def __post_init__(self):
         if self.seed_mode not in ("best", "top"):
             raise ValueError('PipelineConfig: seed_mode must be "best" or "top"')
+        if not (isinstance(self.seed_levels, int) and 1 <= self.seed_levels <= SEARCH_MAX_LEVELS):
+            raise ValueError("PipelineConfig: seed_levels must be an integer in 1..8")
+        if not (isinstance(self.seed_keep, int) and 1 <= self.seed_keep <= SEARCH_MAX_KEEP):
+            raise ValueError("PipelineConfig: seed_keep must be an integer in 1..1024")
+        if not (np.isfinite(self.seed_skip_fitness) and 0 <= self.seed_skip_fitness <= 1):
+            raise ValueError("PipelineConfig: seed_skip_fitness must lie in [0, 1] (0 = every scan is searched)")
+        if self.seed_grid is None and (self.seed_levels > 1 or self.seed_skip_fitness > 0):
+            raise ValueError("PipelineConfig: seed_levels > 1 and seed_skip_fitness > 0 need seed_grid (level 0 of the search)")
+        if self.seed_grid is not None and self.seed_levels > 1:
+            if len(tuple(self.seed_grid)) != 2:
+                raise ValueError("PipelineConfig: seed_grid must be (extent6, step6)")
+            if self.seed_mode == "top" and self.particle_count > SEARCH_MAX_KEEP:
+                raise ValueError('PipelineConfig: seed_mode "top" with seed_levels > 1 hands over at most 1024 nodes (particle_count)')
+            _, _, m, _ = search_lattice(*self.seed_grid, self.seed_levels)          # refuses what the search itself refuses
+            counts, _ = search_level_counts(m, self.seed_levels, self.seed_search_keep())
+            if self.seed_mode == "top" and counts[-1] < self.particle_count:
+                raise ValueError('PipelineConfig: seed_mode "top" needs at least particle_count nodes in the last level of the search')
         if not (np.isfinite(self.seed_gate) and 0 <= self.seed_gate <= self.map_voxel_size):
             raise ValueError("PipelineConfig: seed_gate must be finite, >= 0 (0 = map_voxel_size) and at most map_voxel_size")
         if self.seed_grid is not None:
             if len(tuple(self.seed_grid)) != 2:
                 raise ValueError("PipelineConfig: seed_grid must be (extent6, step6)")
             nodes, _ = self.seed_nodes()                       # refuses steps <= 0 with an extent and more than 2^20 nodes
-            if self.seed_mode == "top" and nodes.shape[0] < self.particle_count:
+            if self.seed_mode == "top" and self.seed_levels == 1 and nodes.shape[0] < self.particle_count:
                 raise ValueError('PipelineConfig: seed_mode "top" needs at least particle_count nodes in seed_grid')
         if self.clear_seen_through is not None:
             if len(tuple(self.clear_seen_through)) != 4:
@@ -1302,7 +1513,7 @@ class ScanResult:
     information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
     modes: object | None = None              # cfg.mode_link: solver.ParticleModes of the final particle set, heaviest first
     cleared: int | None = None               # cfg.clear_seen_through: map points the scan saw through and the map dropped
-    seed: dict | None = None                 # cfg.seed_grid: {"index": best node, "cost": its cost, "cost_zero": the cost of the zero correction (the prediction), "correction": the correction applied to the initial mean ("top": zeros; with "best" initial_guess is prediction · correction_to_pose(correction)), "prediction": the constant-velocity prediction the grid is centred on, "nodes": the nodes handed over as particles ("top" only)}
+    seed: dict | None = None                 # cfg.seed_grid: {"index": best node, "cost": its cost, "cost_zero": the cost of the zero correction (the prediction), "correction": the correction applied to the initial mean ("top": zeros; with "best" initial_guess is prediction · correction_to_pose(correction)), "prediction": the constant-velocity prediction the grid is centred on, "nodes": the nodes handed over as particles ("top" only)}; cfg.seed_levels > 1: "index" gives way to "lattice" (the best node's integer vector on the finest lattice, "nodes" likewise [P, 6]) and "levels", "fine_step", "nodes_scored", "cost_level0" (level 0's best cost) and "fitness_zero" (inliers / rows of the prediction) are added; cfg.seed_skip_fitness > 0: "searched" and "fitness_zero" are added, and a scan that was not searched has only those two, "cost_zero" and "prediction"
 
 
 class RegistrationPipeline:
@@ -1325,11 +1536,28 @@ class RegistrationPipeline:
 
     def _seed(self, guess, source, dev):
         """cfg.seed_grid: the scan's rows scored at the grid's nodes around the prediction -> (initial mean, particles or None,
-        ScanResult.seed).  No policy here: every scan is searched, and the best node is taken as it comes."""
+        ScanResult.seed).  The only policy is cfg.seed_skip_fitness; otherwise every scan is searched, and the best node is taken
+        as it comes.  seed_levels == 1 and seed_skip_fitness == 0 is the flat grid as ever."""
         c = self.cfg
+        gate = c.seed_gate or c.map_voxel_size
+        extra = {}
+        if c.seed_skip_fitness > 0:   # the prediction alone first: one pose, the existing call
+            one = pose_rows(np.asarray(guess, float)[None])
+            if dev:
+                rec, n = self.map.score_poses_device(self._prep.source_f32_ptr, self._prep.n_source, one, gate)[0], self._prep.n_source
+            else:
+                rec, n = self.map.score_poses(source, one, gate)[0], source.shape[0]
+                if c.gpu_map:
+                    self.bytes_h2d += source.shape[0] * 12
+            fitness = float(rec[1]) / n if n else 0.0
+            if fitness >= c.seed_skip_fitness:
+                return guess, None, {"searched": False, "fitness_zero": fitness, "cost_zero": float(rec[3]),
+                                     "prediction": np.array(guess, float)}
+            extra = {"searched": True, "fitness_zero": fitness}
+        if c.seed_levels > 1:
+            return self._seed_search(guess, source, dev, gate, extra)
         nodes, zero = self._seed_nodes
         poses = correction_poses(guess, nodes)
-        gate = c.seed_gate or c.map_voxel_size
         if dev:
             scores = self.map.score_poses_device(self._prep.source_f32_ptr, self._prep.n_source, poses, gate)   # not uploaded again
         else:
@@ -1340,10 +1568,38 @@ class RegistrationPipeline:
         best, first, order = seed_from_scores(scores, nodes, c.particle_count if top else 1)
         seed = {"index": int(order[0]), "cost": float(scores[order[0], 3]), "cost_zero": float(scores[zero, 3]),
                 "correction": np.zeros(6) if top else best, "prediction": np.array(guess, float)}
+        seed.update(extra)
         if top:
             seed["nodes"] = order.copy()
             return guess, np.ascontiguousarray(first.T), seed
         return guess @ correction_to_pose(best), None, seed
+
+    def _seed_search(self, guess, source, dev, gate, extra):
+        """cfg.seed_levels > 1: _seed through the coarse-to-fine search (search_poses), seed_grid being its level 0."""
+        c = self.cfg
+        ext, stp = c.seed_grid
+        keep = c.seed_search_keep()
+        if dev:
+            n = self._prep.n_source
+            res = self.map.search_poses_device(self._prep.source_f32_ptr, n, guess, ext, stp, c.seed_levels, keep, gate)   # not uploaded again
+        else:
+            n = source.shape[0]
+            res = self.map.search_poses(source, guess, ext, stp, c.seed_levels, keep, gate)
+            if c.gpu_map:
+                self.bytes_h2d += n * 12
+        level0 = res["level"][0] if "level" in res else self.map.search_level(0)
+        top = c.seed_mode == "top"
+        seed = {"lattice": np.array(res["best_lattice"], np.int32), "cost": float(res["best_record"][3]),
+                "cost_zero": float(res["zero_record"][3]), "cost_level0": float(level0["records"][level0["kept"][0], 3]),
+                "correction": np.zeros(6) if top else np.array(res["best_correction"], float), "prediction": np.array(guess, float),
+                "levels": int(res["levels"]), "fine_step": np.array(res["fine_step"], float), "nodes_scored": int(res["nodes_scored"]),
+                "fitness_zero": float(res["zero_record"][1]) / n if n else 0.0}
+        seed.update(extra)
+        if top:
+            first = res["top"] if "top" in res else self.map.search_top(c.particle_count)
+            seed["nodes"] = np.array(first["lattice"][:c.particle_count], np.int32)
+            return guess, np.ascontiguousarray(np.array(first["corrections"][:c.particle_count], float).T), seed
+        return guess @ correction_to_pose(seed["correction"]), None, seed
 
     def _particles(self) -> np.ndarray:
         return initialize_particles(self.cfg.particle_count, PRIOR_UB, PRIOR_LB, self._rng)   # set_initPose, :661-667
