@@ -1,23 +1,16 @@
 // map_score.hpp — host-side interface of map_score.hip (svnicp_map_score_poses; the contract is in include/svnicp_hip.h, the
-// design in DESIGN.md §4.16).  voxel_map.hip owns the map and its buffers and calls these.
+// design in DESIGN.md §4.16).  voxel_map.hip owns the map (map_state.hpp: MapScoreBufs) and calls these.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "map_table.hpp"   // MapTableView
+
 namespace svnicp {
 
 constexpr int kScoreRows = 256;          // source rows per workgroup: one per thread, whatever n and C are
 constexpr int kScorePoseBatch = 32768;   // poses per launch (the grid's y extent is limited to 65535)
-
-struct MapTableView {   // the table as the kernels read it
-  const unsigned long long* keys;
-  const int* counts;
-  const float* pts;
-  int64_t cap;
-  int max_points;
-  float voxel;
-};
 
 inline int64_t map_score_chunks(int64_t n) { return (n + kScoreRows - 1) / kScoreRows; }
 

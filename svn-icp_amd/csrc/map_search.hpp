@@ -1,5 +1,5 @@
 // map_search.hpp — host-side interface of map_search.hip (svnicp_map_search_poses; the contract is in include/svnicp_hip.h,
-// the design in DESIGN.md §4.17).  voxel_map.hip owns the map and its buffers and calls these.  The lattice of a search --
+// the design in DESIGN.md §4.17).  voxel_map.hip owns the map (map_state.hpp: MapSearchBufs) and calls these.  The lattice of a search --
 // m, the active axes, the fine step, every level's count -- is planned here, once, on the host, before the first launch.
 #pragma once
 #include <hip/hip_runtime.h>

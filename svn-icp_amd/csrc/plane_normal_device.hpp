@@ -1,6 +1,6 @@
 // plane_normal_device.hpp — from a neighbourhood's scatter matrix to its normal: cyclic Jacobi with a fixed
 // number of sweeps, normal = unit eigenvector of the smallest eigenvalue, and the validity rule.  Stated once for
-// k_target_normals (plane_icp.hip: neighbours from stage A) and k_map_normals (voxel_map.hip: neighbours from the 27-voxel
+// k_target_normals (plane_icp.hip: neighbours from stage A) and k_map_normals (map_normals.hip: neighbours from the 27-voxel
 // block of the map); the two kernels differ only in where the neighbours come from and in the order of their sums.
 //
 // The header stands alone and also compiles for the host (tests/plane_normal_driver.cpp runs normal_from_scatter under the

@@ -2,7 +2,7 @@
 //
 // projectPointCloud of LeGO-LOAM's ImageProjection (include/segmentation/ImageProjection.h:281-325) as include/svnicp_hip.h
 // writes it out: finite check, row from the elevation, column from the azimuth, range, minimum range.  k_seg_project
-// (range_segment.hip) and the visibility kernels of the voxel map (voxel_map.hip) call this one function, so a map point and a
+// (range_segment.hip) and the visibility kernels of the voxel map (map_visibility.hip) call this one function, so a map point and a
 // scan point fall into a pixel by the same arithmetic.  Every atan2f is the float64 function of the float32 operands rounded
 // once; everything else is IEEE + - * / sqrt under -ffp-contract=off.
 #pragma once

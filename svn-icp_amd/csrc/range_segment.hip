@@ -45,7 +45,7 @@ struct SegK {
   int vpn, vln;
 };
 
-using svnicp::atan2_f32;   // range_project_device.hpp: the projection and its two float helpers, shared with voxel_map.hip
+using svnicp::atan2_f32;   // range_project_device.hpp: the projection and its two float helpers, shared with map_visibility.hip
 using svnicp::deg_f32;
 
 __device__ __forceinline__ float point_range(const float* __restrict__ in, int o) {

@@ -1,7 +1,8 @@
 // voxel_table_device.hpp — the voxel map's hash table as device code sees it, stated once: the packed key of a voxel index, the
-// hash, and the bounded read-only lookup.  Used by voxel_map.hip (insert, rehash, k_map_normals) and map_score.hip.
-// Layout (voxel_map.hip's header comment): open addressing with linear probing over keys[cap], cap a power of two; a key is the
-// three voxel indices, each offset by 2^20 into 21 bits; kEmpty ends a probe sequence, kTomb (a removed voxel) does not.
+// hash, and the bounded read-only lookup.  Used by map_table.hip (insert, rehash), map_normals.hip, map_visibility.hip and
+// map_score.hip.  Layout (voxel_map.hip's header comment): open addressing with linear probing over keys[cap], cap a power of
+// two; a key is the three voxel indices, each offset by 2^20 into 21 bits; kEmpty ends a probe sequence, kTomb (a removed
+// voxel) does not.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +41,11 @@ __device__ __forceinline__ int64_t find_slot(const unsigned long long* __restric
     h = (h + 1) & (unsigned long long)(cap - 1);
   }
   return -1;
+}
+
+// wave helper of the map kernels that compact in place (select_smallest of map_normals.hip, k_vis_clear)
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {   // set bits of mask that belong to lanes below this one
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 }  // namespace svnicp

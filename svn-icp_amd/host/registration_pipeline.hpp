@@ -436,7 +436,7 @@ class VoxelHashMap {
 
   void AddPointCloud(const Cloud& cloud, const Pose3& pose) {
     // pcl::transformPointCloud with gtsam's double Matrix4 (VoxelHashMap.cpp:23-25): formed in double from the widened float32
-    // point, left to right, rounded once to float32 (the expression of voxel_map.hip and pipeline.py)
+    // point, left to right, rounded once to float32 (the expression of map_table.hip and pipeline.py)
     const float vs = (float)voxel_size_;
     for (const auto& p : cloud) {
       std::array<float, 3> q;
@@ -449,7 +449,7 @@ class VoxelHashMap {
     RemoveFarPointCloud(pose.t);
   }
   // visibility-based clearing (include/svnicp_hip.h: svnicp_map_clear_seen_through, the same steps in the same float32 /
-  // float64 order as pipeline.py and csrc/voxel_map.hip): a stored point is dropped when the scan's beam in its direction
+  // float64 order as pipeline.py and csrc/map_visibility.hip): a stored point is dropped when the scan's beam in its direction
   // returned from clearly behind it.  Throws std::invalid_argument where the C call answers SVNICP_ERR_INVALID.
   svnicp_visibility_stats ClearSeenThrough(const Cloud& scan, const Pose3& pose, const svnicp_seg_params& sensor, const svnicp_visibility_opt& opt) {
     const int N = sensor.n_scan, H = sensor.horizon_scan;

@@ -450,7 +450,7 @@ def segment_scan(points, params: SegParams | None = None):
 def transform_f32(cloud, T) -> np.ndarray:
     """pcl::transformPointCloud of float32 points with gtsam's DOUBLE Matrix4 (VoxelHashMap.cpp:23-25): every coordinate
     q = ((R0·x + R1·y) + R2·z) + t is formed in float64 from the widened float32 point and rounded once to float32 — the
-    same expression as registration_pipeline.hpp and voxel_map.hip, so all three maps hold identical points.  (Parity with
+    same expression as registration_pipeline.hpp and map_table.hip, so all three maps hold identical points.  (Parity with
     PCL itself is unpinned: PCL is not in this image.)"""
     c = np.asarray(cloud, np.float32).astype(np.float64)
     R = np.asarray(T, float)[:3, :3]

@@ -1,4 +1,4 @@
-"""Normals from the voxel map's own cells on the device (svnicp_map_query_normals, k_map_normals in csrc/voxel_map.hip,
+"""Normals from the voxel map's own cells on the device (svnicp_map_query_normals, k_map_normals in csrc/map_normals.hip,
 DESIGN.md section 4.4) against tests/map_normals_reference.py, the numpy restatement of the same definition.
 
 Comparison rule: flags equal; with_normal equal to the restatement's count; 1 - |n.n_ref| <= 1e-9 where

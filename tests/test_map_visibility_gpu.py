@@ -1,4 +1,4 @@
-"""Visibility-based clearing of the device voxel map (svnicp_map_clear_seen_through, csrc/voxel_map.hip)
+"""Visibility-based clearing of the device voxel map (svnicp_map_clear_seen_through, csrc/map_visibility.hip)
 against pipeline.VoxelHashMap.clear_seen_through, the numpy restatement of the same contract: after every call the device map
 (svnicp_map_download after a whole-map query) equals the restatement's point for point and in order, and every field of
 svnicp_visibility_stats is equal.  The crafted cases carry expectations written out by hand (tests/map_visibility_cases.py)."""

@@ -1,4 +1,4 @@
-"""The limits the voxel map states (csrc/voxel_map.hip, include/svnicp_hip.h), hit exactly: the voxel index range [-2^20, 2^20)
+"""The limits the voxel map states (csrc/map_table.hip, include/svnicp_hip.h), hit exactly: the voxel index range [-2^20, 2^20)
 at both bounds (storage, the skipped-points counter and the neighbour-range test of k_map_normals), points on voxel faces
 (truncf of a float32 division), a distance equal to the radius in the cull (>) and in the range query (<), max_points 1 and
 256 with a voxel that fills inside one run, and the degenerate calls.  Every map is compared bit for bit with

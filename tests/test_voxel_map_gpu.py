@@ -1,4 +1,4 @@
-"""The local map in HBM (csrc/voxel_map.hip, svnicp_map_* of the C ABI) against the host map it replaces:
+"""The local map in HBM (csrc/voxel_map.hip: svnicp_map_* of the C ABI; csrc/map_table.hip: the table) against the host map it replaces:
 svnicp::VoxelHashMap (VoxelHashMap.cpp:22-101) as restated in svn-icp_amd/pipeline.py.  Same voxels, same points, same
 order inside a voxel; range cull and range query pick the same voxels."""
 import importlib

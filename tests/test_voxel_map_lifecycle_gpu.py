@@ -1,5 +1,5 @@
-"""The voxel map's table over a drive (csrc/voxel_map.hip): k_map_rehash moving LIVE voxels, once at unchanged capacity because
-tombstones piled up and once into a table twice the size, then a cloud given by device pointer, svnicp_map_clear and a refill.
+"""The voxel map's table over a drive (csrc/map_table.hip, behind the entry points of csrc/voxel_map.hip): k_map_rehash moving
+LIVE voxels, once at unchanged capacity because tombstones piled up and once into a table twice the size, then a cloud given by device pointer, svnicp_map_clear and a refill.
 After every step the device map equals pipeline.VoxelHashMap bit for bit: len, the whole-map query and a range query that cuts
 the map, in ascending voxel order (_host_rows of tests/test_voxel_map_gpu.py).
 
@@ -10,7 +10,11 @@ rehash of an empty table.  Host model of this sequence (the host map and that ru
 after step 1; 3 931 live and 17 134 tombstones before step 3 (4 * 17 134 > 65 536: rebuild at 65 536 slots); step 3's cloud meets
 63 full voxels and 765 with room, re-creates 153 culled voxels and makes 13 346 new ones; 17 430 live before step 4
 ((17 430 + 30 000) * 2 > 65 536: rebuild into 131 072 slots).  On an MI355X: the same figures, table_info (65536, 2249, 1) after
-the first rebuild and (131072, 3797, 2) after the second, 1.9 s."""
+the first rebuild and (131072, 3797, 2) after the second, 1.9 s.
+
+Further down: every job of the map in turn on ONE map with all rows in host memory — query, normals, scoring, search, scoring
+again, the taps — against each job run alone on a fresh identical map, bit for bit.  The jobs upload their rows into one shared
+staging buffer and keep their results and validity flags apart (csrc/map_state.hpp); this is the test of that."""
 import importlib
 import math
 
@@ -165,3 +169,78 @@ def test_rebuilds_with_live_voxels_and_tombstones(hip):
     fresh.add_pointcloud(s["c1"], s["P1"]); dm.add_pointcloud(s["c1"], s["P1"])
     _check("step 7", dm, fresh, [10.0, 0.0, 0.0])
     assert dm.table_info()[0] == 2 * SLOTS and dm.table_info()[2] == 2
+
+
+# ---------------------------------------------------------------------------------------------
+# One map, every job in turn, all rows from host memory: the jobs share ONE staging buffer for uploaded rows
+# (stage_rows, csrc/map_state.hpp) and each keeps its own results and validity flag, so no job may disturb what another left.
+# ---------------------------------------------------------------------------------------------
+NORMALS_REFUSAL = ("svnicp_map_query_normals: no svnicp_map_query yet, or the map changed (add_cloud / clear_seen_through / clear) "
+                   "since the last one")
+
+
+def _two_scans():
+    """Two synthetic scans of 2048 points (a 10 x 10 x 2 m slab: three to four points per 0.5 m voxel) and their poses."""
+    rng = np.random.default_rng(77)
+    clouds = [(rng.uniform(-1, 1, size=(2048, 3)) * [5.0, 5.0, 1.0]).astype(np.float32) for _ in range(2)]
+    return clouds, [_yaw_pose(0.0, [0.0, 0.0, 0.0]), _yaw_pose(0.05, [0.5, 0.0, 0.0])]
+
+
+def _poses(n, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([_yaw_pose(rng.uniform(-0.05, 0.05), rng.uniform(-0.3, 0.3, size=3)) for _ in range(n)])
+
+
+def _search_bytes(top, level):
+    return b"".join(d[k].tobytes() for d, keys in ((top, ("lattice", "corrections", "poses", "records")),
+                                                   (level, ("lattice", "poses", "records", "kept"))) for k in keys)
+
+
+def test_jobs_share_the_staging_buffer_and_keep_their_own_results(hip):
+    pl = importlib.import_module(hip.__name__ + ".pipeline")
+    binding = importlib.import_module(hip.__name__ + ".binding")
+    clouds, poses = _two_scans()
+    gate = 0.4
+    search_args = (_yaw_pose(0.02, [0.1, 0.0, 0.0]), [0.6, 0, 0, 0, 0, 0], [0.3, 0, 0, 0, 0, 0], 2, 4, gate)   # x alone: m = 2
+
+    def fresh():
+        dm = pl.DeviceVoxelHashMap(0.5, 100.0, 20, device=0, capacity_voxels=1)
+        for c, T in zip(clouds, poses):
+            dm.add_pointcloud(c, T)                                           # 1.
+        return dm
+
+    # each job alone on a freshly built identical map
+    dm = fresh(); ref_score = dm.score_poses(clouds[0], _poses(9, 1), gate); dm.close()
+    dm = fresh(); dm.search_poses(clouds[0], *search_args); ref_search = _search_bytes(dm.search_top(), dm.search_level(0)); dm.close()
+    dm = fresh()
+    _, ref_M = dm.get_map(); _, ref_with = dm.get_map_normals()
+    ref_rows, ref_normals = dm.download(), dm.download_normals()
+    dm.close()
+    assert ref_M > 1000 and ref_with > 100 and ref_rows.shape == ref_normals.shape == (ref_M, 3)
+    assert len(ref_search) == 4 * (6 * 4 + 6 * 8 + 12 * 8 + 4 * 8) + 5 * (6 * 4 + 12 * 8 + 4 * 8) + 4 * 4   # 4 kept, 5 nodes at level 0
+
+    # the sequence on one map
+    dm = fresh()
+    _, M = dm.get_map()                                                       # 2.
+    _, with_normal = dm.get_map_normals()                                     # 3.
+    score = dm.score_poses(clouds[0], _poses(9, 1), gate)                     # 4.
+    res = dm.search_poses(clouds[0], *search_args)                            # 5.
+    assert res["level_count"] == [5, 12] and res["level_kept"] == [4, 4]
+    other = dm.score_poses(clouds[1], _poses(9, 2), gate)                     # 6. other rows, other poses
+    top = dm.search_top()                                                     # 7.
+    level0 = dm.search_level(0)                                               # 8.
+    rows = dm.download()                                                      # 9.
+    normals = dm.download_normals()                                           # 10.
+    assert (M, with_normal) == (ref_M, ref_with)
+    assert rows.tobytes() == ref_rows.tobytes() and normals.tobytes() == ref_normals.tobytes()
+    assert _search_bytes(top, level0) == ref_search
+    assert score.tobytes() == ref_score.tobytes() and other.tobytes() != score.tobytes()
+
+    # a further cloud: the selection and the normals are dropped, the search's results do not depend on the table
+    dm.add_pointcloud(clouds[0], _yaw_pose(0.1, [1.0, 0.0, 0.0]))
+    with pytest.raises(binding.SvnIcpError) as e:
+        dm.get_map_normals()
+    assert str(e.value).endswith(NORMALS_REFUSAL)
+    assert dm.download_normals().shape == (0, 3)
+    assert _search_bytes(dm.search_top(), dm.search_level(0)) == ref_search
+    dm.close()
