@@ -226,6 +226,28 @@ int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, i
 int svnicp_get_target_normals(svnicp_ctx *ctx, double *outMx3);
 int svnicp_get_plane_stats(svnicp_ctx *ctx, double *outPx2, int64_t *normal_passes);
 
+/* ---- Gaussian pose prior on the correction (an extension: the reference's posterior has no prior) --
+ * svnicp_set_pose_prior(ctx, mean6, info36): from the next svnicp_align_begin on, SVN mode minimises, per particle,
+ * 1/2 sum w |e|^2 + 1/2 e^T Lambda e with e = [t_p - mu_t ; Log(R_mu^T R_p)], (R_p, t_p) the particle's CORRECTION pose (not
+ * the total pose R0 R_p), mean6 = [mu_t ; mu_r] in the coordinates of svnicp_get_transformation, R_mu = Exp(mu_r), and info36
+ * = Lambda, 6x6 row-major in the order (t, r) of svnicp_get_cov_matrix.  In front of every Stein step one kernel adds
+ * J^T Lambda e to b and J^T Lambda J to H of every particle, J = blkdiag(R_p, Jr^-1(e_r)), at the pose the iteration's
+ * search used; the 1e-6 I of the data term stays, H stays exactly symmetric, and the trace taps H, b include the prior.
+ * Domain |e_r| < pi.  A particle with a non-finite pose gets a non-finite record; the others are unaffected.
+ * UNITS: Lambda is in the units of the cost, which has NO point noise in it (the data term is sum w |e|^2 in m^2).  For a
+ * metric prior covariance Sigma and a point noise sigma_pt pass Lambda = sigma_pt^2 Sigma^-1.
+ * info36 NULL: the prior is off (the default): exactly the launches of a context that never called this.
+ * SVNICP_ERR_INVALID for a non-finite entry, |Lambda_ij - Lambda_ji| > 1e-12 max|Lambda|, a negative diagonal entry, a
+ * smallest eigenvalue below -1e-12 max|Lambda|, or |mu_r| >= pi; the stored matrix is (Lambda + Lambda^T) / 2.
+ * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID while a prior is set: SVGD mode, a partial particle
+ * shard, a source-row shard and the option chain=persistent.  Allowed: mini-batch mode, the plane residual,
+ * correspondence=full, update=fused, particle weighting, any particle count.  With a prior the small chain and the fused
+ * one-particle iteration are not chosen (neither has a place for the launch between the sums and the step).
+ * svnicp_get_pose_prior: *on = a prior is set; mean6 / info36 (the symmetrised matrix) are written only then; any pointer
+ * may be NULL. */
+int svnicp_set_pose_prior(svnicp_ctx *ctx, const double mean6[6], const double info36[36]);
+int svnicp_get_pose_prior(svnicp_ctx *ctx, int *on, double mean6[6], double info36[36]);
+
 /* ---- evaluate a registration: fitness, inlier RMSE, nearest pairs (an extension: the reference returns a pose and a
  * covariance and nothing that says whether the registration worked) -------------------------------
  * svnicp_evaluate(ctx, R, t, max_corr_dist, out): one pose against the WHOLE target, on the device, blocking.
@@ -657,6 +679,9 @@ int svnicp_get_candidate_dist2(svnicp_ctx *ctx, double *outBK);
  * Stein step reads it (tests/test_plane_alone_gpu.py) */
 void *svnicp_plane_record_devptr(svnicp_ctx *ctx); /* double [P][42]: H (36, mirrored, + 1e-6 on the diagonal) | b (6) */
 void *svnicp_plane_stats_devptr(svnicp_ctx *ctx);  /* double [P][2]: {accepted pairs, sum w r^2} */
+/* the particles' correction poses as the kernels hold them, valid after svnicp_set_particles (NULL otherwise):
+ * which = 0: R double [P][9] row-major, which = 1: t double [P][3] (tests/test_pose_prior_gpu.py reads and crafts them) */
+void *svnicp_particle_pose_devptr(svnicp_ctx *ctx, int which);
 /* (both are allocated max(P, Ppad) rows long, Ppad from svnicp_get_stage_b_grid: the rows from P on belong to the padded
  * particles of the stage-B grid and are never written) */
 /* stage B's launch grid of the registration svnicp_align_begin began: {grid_x, grid_y, pts_per_block, Ppad} — the accumulate

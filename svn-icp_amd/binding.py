@@ -241,6 +241,10 @@ def load_library():
     L.svnicp_get_minibatch_candidates.argtypes = [vp, ip]
     L.svnicp_get_minibatch_rows.argtypes = [vp, C.POINTER(C.c_int64)]
     L.svnicp_set_residual.argtypes = [vp, C.c_int, C.c_double, C.c_int]
+    L.svnicp_set_pose_prior.argtypes = [vp, dp, dp]
+    L.svnicp_get_pose_prior.argtypes = [vp, C.POINTER(C.c_int), dp, dp]
+    L.svnicp_particle_pose_devptr.argtypes = [vp, C.c_int]
+    L.svnicp_particle_pose_devptr.restype = vp
     L.svnicp_set_target_normals.argtypes = [vp, vp, C.c_int64, C.c_int]
     L.svnicp_get_target_normals.argtypes = [vp, dp]
     L.svnicp_get_plane_stats.argtypes = [vp, dp, C.POINTER(C.c_int64)]

@@ -18,6 +18,7 @@
 #include "device_buffer.hpp"
 #include "information_solve.hpp"
 #include "kernels.hpp"
+#include "pose_prior.hpp"
 #include "stage_a_host.hpp"
 #include "stage_b_host.hpp"
 
@@ -143,6 +144,16 @@ struct ModesState {
   int P = 0;
 };
 
+// Gaussian pose prior on the correction (svnicp_set_pose_prior; csrc/pose_prior.hip)
+struct PriorState {
+  bool set = false;             // what the next registration runs with: mean6 / info36 as the getter returns them, `next` as the kernel takes them
+  double mean6[6] = {}, info36[36] = {};
+  PosePrior next{};
+  bool on = false;              // the registration begun last runs with `args`
+  PosePrior args{};
+  DevBuf<double> rec;           // [P][42] = H | b with the prior added: what the Stein-step kernels read through UpdateArgs::plane_Hb
+};
+
 struct Trace { DevBuf<double> H, b, N, phi, h; DevBuf<int32_t> corr; };   // record_trace
 
 struct Profiling {   // timing events
@@ -183,7 +194,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb; PlaneState pl; EvalState ev; ScoreState sc; ModesState md;
+  Sharding shard; MiniBatch mb; PlaneState pl; PriorState pr; EvalState ev; ScoreState sc; ModesState md;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -226,8 +237,8 @@ static StageAEnv stage_a_env(const svnicp_ctx* c) {
   return {c->stream, c->tune, c->num_cus, c->prm.record_trace != 0, c->cloud.tgt.p, c->B, c->M, c->pose0};
 }
 
-// what the rules of registration_plan.hpp read of the context; plane: the residual this registration runs with
-static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane) {
+// what the rules of registration_plan.hpp read of the context; plane, prior: what this registration runs with
+static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane, bool prior) {
   RegistrationFacts f;
   f.P = c->P; f.K = c->K; f.I = c->prm.iterations; f.B = c->B; f.M = c->M;
   f.svgd = c->prm.mode == SVNICP_MODE_SVGD; f.check_early_stop = c->prm.check_early_stop != 0; f.record_trace = c->prm.record_trace != 0;
@@ -236,6 +247,7 @@ static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane) {
   f.batch = c->mb.batch; f.explicit_tab = c->mb.explicit_tab; f.tab_I = c->mb.tab_I;
   f.plane = plane; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
   f.weighting = c->sc.kind;
+  f.prior = prior;
   return f;
 }
 
@@ -476,7 +488,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   c->run.have_candidates = false;
   c->sa.held = TargetLayout::None;
   // svnicp_iter_accumulate now refuses until the next svnicp_align_begin; svnicp_iter_update goes on and follows the new options
-  if (c->run.began) c->st.step = plan_step(registration_facts(c, c->pl.on), c->tune, c->sb.plan);
+  if (c->run.began) c->st.step = plan_step(registration_facts(c, c->pl.on, c->pr.on), c->tune, c->sb.plan);
   return SVNICP_OK;
 }
 
@@ -520,7 +532,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   const int I = c->prm.iterations, P = c->P;
   const int64_t B = c->B;
   const bool plane = c->pl.residual == SVNICP_RESIDUAL_PLANE;
-  const RegistrationFacts f = registration_facts(c, plane);
+  const RegistrationFacts f = registration_facts(c, plane, c->pr.set);
   if (const char* why = minibatch_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kMinibatchRefusal) + why);
   if (c->mb.batch != 0 && c->mb.explicit_tab && !c->mb.tab_h.empty() && c->mb.tab_checked_B != B) {
     for (const int32_t v : c->mb.tab_h)
@@ -532,12 +544,14 @@ int svnicp_align_begin(svnicp_ctx* c) {
   if (const char* why = weighting_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + why);
   if (f.weighting && score_tile_rows(P, c->K, true) < 1)
     return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + "knn_count is too large for one row's candidates to fit the scoring kernel's LDS tile");
+  if (const char* why = prior_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kPriorRefusal) + why);
   const RegistrationRows r = registration_rows(c->mb.batch, I, B);
   const AccumPlan shape = plan_stage_b(f, c->tune, r.Bi);
   // (the stage-A plan StageA::begin is about to make: every refusal comes before the context changes)
   const bool stage_a_k1 = StageA::plan_for(stage_a_env(c), r.Bq, c->K).can_search(1);
   if (const char* why = full_corr_refusal(f, c->tune, shape.f32, stage_a_k1)) return fail(c, SVNICP_ERR_INVALID, why);
   c->pl.on = plane;
+  c->pr.on = f.prior; c->pr.args = c->pr.next;
   c->ev.mark_stale("a registration began after the last svnicp_evaluate");   // svnicp_eval_information wants one afterwards
   c->sc.on = f.weighting != 0; c->sc.reg_refusal = scoring_refusal(f, c->tune);
   c->mb.on = r.mb; c->mb.have = false; c->mb.check = false;
@@ -556,6 +570,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
     HIPCHK(c, c->mb.cand.ensure((size_t)r.Bt * c->K));
   }
   if (const int rc = c->sb.begin(c, f, c->tune, r, shape, c->num_cus)) return rc;
+  if (c->pr.on) HIPCHK(c, c->pr.rec.ensure((size_t)P * 42));
   HIPCHK(c, c->st.history.ensure((size_t)(I > 0 ? I : 1) * 6 * P));
   c->st.hist_I = I; c->st.hist_P = P;
   if (c->prm.record_trace) {
@@ -726,8 +741,9 @@ int svnicp_build_candidate_table(svnicp_ctx* c) {
   return SVNICP_OK;
 }
 
-// argument block of the Stein-step kernels for iteration `it`
-static UpdateArgs update_args(svnicp_ctx* c, int it) {
+// argument block of the Stein-step kernels for iteration `it`; with_prior = false: as a registration without a pose prior
+// would get it — what the prior's own kernel forms its base record from
+static UpdateArgs update_args(svnicp_ctx* c, int it, bool with_prior = true) {
   UpdateArgs u{};
   u.sums = c->shard.row_world > 1 ? c->shard.rank_sums.p : c->sb.sums.p; u.n_ranks = c->shard.row_world; u.R = c->st.R.p; u.t = c->st.t.p; u.Rtot = c->st.Rtot.p; u.pose = c->pose0;
   u.P = c->P; u.iteration = it; u.iterations = c->prm.iterations;
@@ -744,6 +760,7 @@ static UpdateArgs update_args(svnicp_ctx* c, int it) {
   u.dbg = c->tune.debug ? c->dbg.upd.p : nullptr;
   u.svgd = c->prm.mode == SVNICP_MODE_SVGD ? 1 : 0;
   u.plane_Hb = c->pl.on ? c->pl.Hb.p : nullptr;
+  if (with_prior && c->pr.on) u.plane_Hb = c->pr.rec.p;   // H | b come finished from k_pose_prior, in point mode too
   return u;
 }
 // argument block of the stage-B kernels for iteration `it` (full_idx: set by the correspondence = full search)
@@ -856,6 +873,8 @@ int svnicp_iter_update(svnicp_ctx* c, int it) {
   if (const int rc = ensure_dbg_upd(c)) return rc;
   UpdateArgs u = update_args(c, it);
   HIPCHK(c, prof_begin(c, KC_UPDATE));
+  if (c->pr.on)   // the prior's record first: every launch shape below reads it in place of the sums or the plane record
+    HIPCHK(c, launch_pose_prior(update_args(c, it, false), c->pr.args, c->pr.rec.p, c->stream));
   if (c->tune.debug && it == c->prm.iterations - 1)   // phase cycles of the one-workgroup kernels so far
     if (const int rc = print_update_phases(c, false)) return rc;
   const StepChain chain = c->st.step.chain;
@@ -938,6 +957,9 @@ void* svnicp_sums_devptr(svnicp_ctx* c) { return c ? (void*)c->sb.sums.p : nullp
 void* svnicp_total_pose_devptr(svnicp_ctx* c) { return c ? (void*)c->st.Rtot.p : nullptr; }   // AccumArgs::Rtot, [P][12]
 // plane mode's record and statistics of the begun registration (prepare_plane sized them), and stage B's grid: test-only taps
 void* svnicp_plane_record_devptr(svnicp_ctx* c) { return (c && c->run.began && c->pl.on) ? (void*)c->pl.Hb.p : nullptr; }
+void* svnicp_particle_pose_devptr(svnicp_ctx* c, int which) {   // the correction poses R [P][9] (0) and t [P][3] (1)
+  return (c && c->run.particles_set && (which == 0 || which == 1)) ? (void*)(which == 0 ? c->st.R.p : c->st.t.p) : nullptr;
+}
 void* svnicp_plane_stats_devptr(svnicp_ctx* c) { return (c && c->run.began && c->pl.on) ? (void*)c->pl.stats.p : nullptr; }
 int svnicp_get_stage_b_grid(svnicp_ctx* c, int out4[4]) {
   CTX_CHECK(c);
@@ -961,7 +983,7 @@ static int align_enqueue(svnicp_ctx* c, bool follow_stop) {
   if ((rc = svnicp_stage_candidates(c, 0, c->B))) return rc;
   if ((rc = svnicp_build_candidate_table(c))) return rc;
   c->st.small_launched = false;
-  const DrivePlan drive = plan_drive(registration_facts(c, c->pl.on), c->tune, c->sb.plan, c->st.step, follow_stop);
+  const DrivePlan drive = plan_drive(registration_facts(c, c->pl.on, c->pr.on), c->tune, c->sb.plan, c->st.step, follow_stop);
   c->st.drive = drive;
   c->st.drive.defer_fin = false;   // holds inside the loop below only: not in the persistent kernel, not in a caller's own split-phase loop
   if (drive.persistent_try) {
@@ -1255,6 +1277,28 @@ int svnicp_get_minibatch_rows(svnicp_ctx* c, int64_t out2[2]) {
   const int rc = fetch(c, w, c->mb.ctl.p, sizeof w);
   if (rc) return rc;
   out2[0] = w[1]; out2[1] = c->mb.nq;
+  return SVNICP_OK;
+}
+
+// ---- Gaussian pose prior on the correction ----
+int svnicp_set_pose_prior(svnicp_ctx* c, const double mean6[6], const double info36[36]) {
+  CTX_CHECK(c);
+  if (!info36) { c->pr.set = false; return SVNICP_OK; }
+  if (!mean6) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_pose_prior: null mean");
+  PosePrior next;
+  const char* why = nullptr;
+  if (pose_prior::validate(mean6, info36, &next, &why)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_set_pose_prior: ") + why);
+  c->pr.next = next; c->pr.set = true;
+  std::memcpy(c->pr.mean6, mean6, sizeof c->pr.mean6);
+  std::memcpy(c->pr.info36, next.L, sizeof c->pr.info36);
+  c->run.have_candidates = false;   // the step chain follows the prior: svnicp_iter_accumulate refuses until the next svnicp_align_begin
+  return SVNICP_OK;
+}
+int svnicp_get_pose_prior(svnicp_ctx* c, int* on, double mean6[6], double info36[36]) {
+  CTX_CHECK(c);
+  if (on) *on = c->pr.set ? 1 : 0;
+  if (c->pr.set && mean6) std::memcpy(mean6, c->pr.mean6, sizeof c->pr.mean6);
+  if (c->pr.set && info36) std::memcpy(info36, c->pr.info36, sizeof c->pr.info36);
   return SVNICP_OK;
 }
 

@@ -219,7 +219,8 @@ struct UpdateArgs {
   double* uctl;        // multi-workgroup update path: small control / norm area
   unsigned long long* dbg;  // optional [8]: cycle stamps of the fused kernel's phases (SVNICP_DEBUG)
   const double* plane_Hb;   // point-to-plane mode: [P][42] = H | b as k_plane_finalize left them — the kernels then skip load_sums +
-                            // finalize_Hb (wave-uniform; nullptr in point mode)
+                            // finalize_Hb (wave-uniform; nullptr in point mode).  With a pose prior (pose_prior.hip), in either mode:
+                            // the record k_pose_prior wrote, the base record with the prior's terms added
 };
 size_t update_workspace_doubles(int P);
 // areas k_init_particles clears at the start of a registration (whole 32-bit words), and the control words it resets
@@ -245,6 +246,11 @@ const double* update_step_norms(const UpdateArgs& a);   // [P] norms the early-s
 hipError_t launch_reduce_partials(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* sums, const int* ctl,
                                   hipStream_t st);
 size_t update_uctl_doubles(int P);
+// ---------------- Gaussian pose prior on the correction (pose_prior.hip; PosePrior: pose_prior.hpp) ----------------
+struct PosePrior;
+// record [P][42] = particle_Hb(a) + the prior's JᵀΛJ | JᵀΛe at the poses a.R, a.t; `a` as the Stein step WITHOUT a prior would
+// get it (its plane_Hb is the plane record or nullptr, never `record`)
+hipError_t launch_pose_prior(const UpdateArgs& a, const PosePrior& pr, double* record, hipStream_t st);
 // ---------------- point-to-plane residual (plane_icp.hip) ----------------
 constexpr int kPlaneSums = 29;             // per (workgroup, particle): H upper triangle (21) | b (6) | accepted pairs | Σ w·r²
 struct PlaneArgs {

@@ -55,6 +55,7 @@ struct RegistrationFacts {
   bool normals_supplied = false;
   int normal_k = 16;
   int weighting = 0;                   // svnicp_set_particle_weighting: SVNICP_WEIGHT_* (0 = uniform, the reference)
+  bool prior = false;                  // svnicp_set_pose_prior: a Gaussian prior on the correction is added in front of the Stein step
   int nshard() const { return p_hi - p_lo; }
   bool whole_shard() const { return p_lo == 0 && p_hi == P; }
 };
@@ -84,6 +85,7 @@ inline const char* first_refusal(std::initializer_list<Refusal> ladder) {
 constexpr const char* kMinibatchRefusal = "svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ";
 constexpr const char* kPlaneRefusal = "svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ";
 constexpr const char* kWeightingRefusal = "svnicp_align: particle weighting (svnicp_set_particle_weighting) is not available here: ";
+constexpr const char* kPriorRefusal = "svnicp_align: the pose prior (svnicp_set_pose_prior) is not available here: ";
 constexpr const char* kScoringRefusal = "svnicp_score_particles: the last registration cannot be scored: ";
 
 // A cloud's row count: row indices are int32 everywhere behind stage A (cand, kidx, torig, full_idx, the Morton sorts'
@@ -138,6 +140,17 @@ inline const char* weighting_refusal(const RegistrationFacts& f, const Tuning& t
   if (f.weighting != 1) return "unknown weighting kind";
   if (f.svgd) return "SVGD mode: the weight option belongs to SVNICP's constructor only";
   return scoring_refusal(f, t);
+}
+// pose prior: what it is not combined with (all left for later).  What passes runs the prior's launch between the sums and the
+// Stein step: small_registration and plan_step keep the two shapes that have no place for it (SmallChain, single_fused) away.
+inline const char* prior_refusal(const RegistrationFacts& f, const Tuning& t) {
+  if (!f.prior) return nullptr;
+  return first_refusal({
+      {f.svgd, "SVGD mode: its gradient does not pass through the H | b record the prior is added to"},
+      {f.shard_set && !f.whole_shard(), "a partial particle shard (svnicp_set_shard) is set"},
+      {f.row_world > 1, "a source-row shard (svnicp_set_row_shard) is set"},
+      {t.persistent != 0, "option chain=persistent is set"},
+  });
 }
 // correspondence = full (the whole message): its per-particle searches feed the split accumulate kernel and run through
 // stage A's working set with K = 1 (stage_a_k1: StageAPlan::can_search(1)).  An empty particle shard searches nothing.
@@ -199,7 +212,7 @@ auto dispatch_lanes(int PW, int WP, F&& f) {
 // kSmallChainBlocks workgroups (plan_accumulate clamps its grid), so the update kernels add their records themselves
 inline bool small_registration(const AccumPlan& shape, const RegistrationFacts& f, const Tuning& t, int64_t Bi) {
   return shape.f32 == 3 && shape.grid_y == 1 && Bi * f.nshard() <= (1 << 19) && t.small_chain && f.P >= 2 && f.P <= 128 &&
-         f.P <= t.fused_update_max_p && !t.update_fused && f.row_world == 1 && f.whole_shard() && !t.full_corr && !f.plane;
+         f.P <= t.fused_update_max_p && !t.update_fused && f.row_world == 1 && f.whole_shard() && !t.full_corr && !f.plane && !f.prior;
 }
 // the stage-B plan of a registration as far as it does not depend on the device
 inline AccumPlan plan_stage_b(const RegistrationFacts& f, const Tuning& t, int64_t Bi) {
@@ -262,7 +275,7 @@ inline StepPlan plan_step(const RegistrationFacts& f, const Tuning& t, const Acc
   else if (f.P <= kMedianInlineMaxP && f.P <= t.fused_update_max_p && t.median_inline != 0) s.chain = StepChain::InlineMedian;
   else s.chain = StepChain::SideStream;
   s.single_fused = f.P == 1 && !f.svgd && f.row_world == 1 && f.p_lo == 0 && f.p_hi == 1 && !t.full_corr && t.single_fused && pl.f32 == 1 &&
-                   !f.plane;
+                   !f.plane && !f.prior;
   return s;
 }
 

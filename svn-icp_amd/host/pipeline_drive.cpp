@@ -16,7 +16,9 @@
 //      one more line per registered scan: "clear <scan>: points_removed";
 //      after those, seven more: seed_levels seed_keep seed_skip_fitness extent_xy extent_yaw step_xy step_yaw -- seed_levels > 0 turns
 //      PipelineConfig::seed_grid on with that x / y / yaw grid (1 = the flat grid, > 1 = the coarse-to-fine search), one more line per
-//      seeded scan: "seed <scan>: searched levels nodes_scored fitness_zero cost_zero cost correction[x] [y] [yaw]" with %.17g)
+//      seeded scan: "seed <scan>: searched levels nodes_scored fitness_zero cost_zero cost correction[x] [y] [yaw]" with %.17g;
+//      after those, seven more: prior_point_sigma sx sy sz srx sry srz -- prior_point_sigma > 0 turns PipelineConfig::prior_sigma on
+//      with those standard deviations, one more line per registered scan: "prior <scan>: prior_chi2" with %.17g)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -59,6 +61,10 @@ int main(int argc, char** argv) {
     const double exy = atof(argv[21]), eyaw = atof(argv[22]), sxy = atof(argv[23]), syaw = atof(argv[24]);
     cfg.seed_grid = std::make_pair(std::array<double, 6>{exy, exy, 0, 0, 0, eyaw}, std::array<double, 6>{sxy, sxy, 0, 0, 0, syaw});
     cfg.seed_levels = atoi(argv[18]); cfg.seed_keep = atoi(argv[19]); cfg.seed_skip_fitness = atof(argv[20]);
+  }
+  if (argc > 31 && atof(argv[25]) > 0) {
+    cfg.prior_point_sigma = atof(argv[25]);
+    cfg.prior_sigma = std::array<double, 6>{atof(argv[26]), atof(argv[27]), atof(argv[28]), atof(argv[29]), atof(argv[30]), atof(argv[31])};
   }
   try {
     svnicp::RegistrationPipeline pipe(cfg);
@@ -106,6 +112,7 @@ int main(int argc, char** argv) {
         printf("seed %d: %d %d %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", s, r.seed->searched ? 1 : 0, r.seed->levels,
                (long long)r.seed->nodes_scored, r.seed->fitness_zero, r.seed->cost_zero, r.seed->cost, r.seed->correction[0],
                r.seed->correction[1], r.seed->correction[5]);
+      if (cfg.prior_sigma && r.aligned) printf("prior %d: %.17g\n", s, r.prior_chi2);
       if (r.modes) {
         const svnicp_modes& m = *r.modes;
         printf("modes %d: %d %d %d %d", s, (int)m.n_modes, (int)m.n_reported, (int)m.nonfinite, (int)m.has_scores);

@@ -1020,6 +1020,12 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   int seed_keep = 8;                // with seed_levels > 1: nodes of a level that are expanded ("top": at least particle_count are kept)
   double seed_skip_fitness = 0.0;   // with seed_grid: > 0 = the prediction alone is scored first, and with inliers / rows at or above this
                                     // no search is made and the registration starts as without seeding; 0 = every scan is searched
+  // prior_sigma = six standard deviations > 0 (m, m, m, rad, rad, rad): every registration runs with a Gaussian prior on the
+  // correction (svnicp_set_pose_prior) centred on the registration's initial mean — the zero correction; with seed_mode "best"
+  // that is the SEEDED mean, not the prediction — with information prior_point_sigma^2 diag(1 / sigma^2), and
+  // ScanResult::prior_chi2 is filled; empty (the default) = off, no call is made
+  std::optional<std::array<double, 6>> prior_sigma;
+  double prior_point_sigma = 1.0;   // with prior_sigma: the point noise in m that turns the metric sigmas into the cost's units
 };
 
 struct ScanResult {
@@ -1036,6 +1042,8 @@ struct ScanResult {
   std::optional<svnicp_information> information;   // cfg.information != "off": H, b, eigen-structure, rank, step, cov at the result pose
   std::optional<svnicp_modes> modes;               // cfg.mode_link_*: the modes of the final particle set, heaviest first
   int64_t cleared = -1;                            // cfg.clear_seen_through: map points the scan saw through and the map dropped
+  double prior_chi2 = -1;                          // cfg.prior_sigma: e^T diag(1 / sigma^2) e of the returned correction (the prior's mean is
+                                                   // the zero correction), the innovation statistic a gate would read; -1 = off
   struct Seed {
     size_t index = 0;                      // the best node
     double cost = 0, cost_zero = 0;        // its cost; the cost of the zero correction (the prediction)
@@ -1077,6 +1085,11 @@ class RegistrationPipeline {
       throw std::invalid_argument("PipelineConfig: information must be \"off\", \"point\" or \"plane\"");
     if (cfg.information != "off" && !(cfg.eval_dist > 0)) throw std::invalid_argument("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)");
     if (cfg.information != "off" && !(cfg.info_huber > 0)) throw std::invalid_argument("PipelineConfig: info_huber must be > 0 (+inf = unweighted)");
+    if (cfg.prior_sigma) {
+      for (const double v : *cfg.prior_sigma)
+        if (!(std::isfinite(v) && v > 0)) throw std::invalid_argument("PipelineConfig: prior_sigma must be six finite standard deviations > 0 (m, m, m, rad, rad, rad)");
+      if (!(std::isfinite(cfg.prior_point_sigma) && cfg.prior_point_sigma > 0)) throw std::invalid_argument("PipelineConfig: prior_point_sigma must be finite and > 0 (m)");
+    }
     if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
     if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
     const bool mode_link = !(cfg.mode_link_trans < 0 && cfg.mode_link_rot < 0);
@@ -1264,6 +1277,12 @@ class RegistrationPipeline {
       solver_->add_cloud(src64.data(), (int64_t)source.size(), tgt64.data(), (int64_t)target.size(), init.data(), cfg_.particle_count);  // :582
       bytes_h2d_ += (src64.size() + tgt64.size()) * 8;
     }
+    if (cfg_.prior_sigma) {   // centred on the initial mean set below: the zero correction
+      const double zero6[6] = {0, 0, 0, 0, 0, 0};
+      double info[36] = {};
+      for (int i = 0; i < 6; ++i) info[7 * i] = cfg_.prior_point_sigma * cfg_.prior_point_sigma / ((*cfg_.prior_sigma)[i] * (*cfg_.prior_sigma)[i]);
+      solver_->set_pose_prior(zero6, info);
+    }
     solver_->set_initial_mean(guess.R.data(), guess.t.data());                                         // :598
     if (tap_) { tap_->source = src64; tap_->target = tgt64; tap_->particles = init; tap_->initial_guess = guess; }
     res.state = (int)solver_->stein_align();                                                           // :599
@@ -1283,6 +1302,10 @@ class RegistrationPipeline {
         for (int i = 0; i < 6; ++i) res.correction[i] = m.mean[0][i];
     }
     res.pose = guess * correction_to_pose(res.correction);                                             // updater_, :37-46
+    if (cfg_.prior_sigma) {   // no policy here: the number a gate would read
+      res.prior_chi2 = 0.0;
+      for (int i = 0; i < 6; ++i) { const double z = res.correction[i] / (*cfg_.prior_sigma)[i]; res.prior_chi2 += z * z; }
+    }
     if (cfg_.eval_dist > 0) {   // the number a caller may gate the map update on (no policy here)
       const svnicp_eval ev = solver_->evaluate(cfg_.eval_dist, res.pose.R.data(), res.pose.t.data());
       res.fitness = ev.fitness; res.inlier_rmse = ev.inlier_rmse;

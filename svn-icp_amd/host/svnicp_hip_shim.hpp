@@ -135,6 +135,15 @@ class SVGDICP {
     chk(svnicp_get_plane_stats(h_, o.data(), normal_passes));
     return o;
   }
+  // Gaussian pose prior on the correction (svnicp_hip.h "pose prior"): mean6 = [t ; rotation vector], info36 = Lambda row-major
+  // in the cost's units (sigma_pt^2 Sigma^-1); info36 == nullptr turns it off.  From the next registration on.
+  void set_pose_prior(const double* mean6, const double* info36) { chk(svnicp_set_pose_prior(h_, mean6, info36)); }
+  // true and mean6 / info36 filled (either may be nullptr) when a prior is set
+  bool pose_prior(double* mean6 = nullptr, double* info36 = nullptr) {
+    int on = 0;
+    chk(svnicp_get_pose_prior(h_, &on, mean6, info36));
+    return on != 0;
+  }
   // evaluate a registration (svnicp_hip.h "evaluate a registration"): fitness, inlier RMSE and, with normals, plane RMSE of
   // a pose (row-major R, t; map <- sensor) against the whole target; both NULL: the last registration's result
   svnicp_eval evaluate(double max_corr_dist, const double* R_rowmajor = nullptr, const double* t = nullptr) {

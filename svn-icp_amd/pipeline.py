@@ -1423,6 +1423,12 @@ class PipelineConfig:
     seed_levels: int = 1           # with seed_grid: > 1 = coarse-to-fine (search_poses): seed_grid is level 0, every further level is three times finer and expands the seed_keep best nodes of the one before; 1 = the flat grid
     seed_keep: int = 8             # with seed_levels > 1: nodes of a level that are expanded ("top": at least particle_count are kept)
     seed_skip_fitness: float = 0.0  # with seed_grid: > 0 = the prediction alone is scored first, and with inliers / rows at or above this no search is made and the registration starts as without seeding; 0 = every scan is searched
+    prior_sigma: tuple | None = None   # (sx, sy, sz m, srx, sry, srz rad) > 0: every registration runs with a Gaussian prior on the correction (svnicp_set_pose_prior) centred on the registration's initial mean — the zero correction; with seed_mode "best" that is the SEEDED mean, not the prediction — with information prior_point_sigma^2 diag(1 / sigma^2), and ScanResult.prior_chi2 is filled; None = off, no call is made
+    prior_point_sigma: float = 1.0     # with prior_sigma: the point noise in m that turns the metric sigmas into the cost's units (Lambda = sigma_pt^2 Sigma^-1)
+
+    def prior_information(self) -> np.ndarray:
+        """Lambda [6, 6] of prior_sigma and prior_point_sigma."""
+        return np.diag(float(self.prior_point_sigma) ** 2 / np.asarray(self.prior_sigma, np.float64) ** 2)
 
     def seed_nodes(self):
         """-> (corrections [C, 6], index of the zero correction) of seed_grid."""
@@ -1486,6 +1492,11 @@ class PipelineConfig:
             raise ValueError("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)")
         if self.information != "off" and not self.info_huber > 0:
             raise ValueError("PipelineConfig: info_huber must be > 0 (+inf = unweighted)")
+        if self.prior_sigma is not None:
+            if len(tuple(self.prior_sigma)) != 6 or not all(np.isfinite(v) and v > 0 for v in self.prior_sigma):
+                raise ValueError("PipelineConfig: prior_sigma must be six finite standard deviations > 0 (m, m, m, rad, rad, rad)")
+            if not (np.isfinite(self.prior_point_sigma) and self.prior_point_sigma > 0):
+                raise ValueError("PipelineConfig: prior_point_sigma must be finite and > 0 (m)")
         if self.map_normals and not self.gpu_map:
             raise ValueError("PipelineConfig: map_normals needs gpu_map=True (the normals are computed from the device map)")
         if self.map_normals and self.solver.residual != "plane":
@@ -1513,6 +1524,7 @@ class ScanResult:
     information: object | None = None        # cfg.information != "off": solver.RegistrationInformation at the result pose (H, b, eigen-structure, rank, step, cov)
     modes: object | None = None              # cfg.mode_link: solver.ParticleModes of the final particle set, heaviest first
     cleared: int | None = None               # cfg.clear_seen_through: map points the scan saw through and the map dropped
+    prior_chi2: float | None = None          # cfg.prior_sigma: e^T diag(1 / sigma^2) e of the returned correction (e = the correction itself: the prior's mean is the zero correction), the innovation statistic a gate would read
     seed: dict | None = None                 # cfg.seed_grid: {"index": best node, "cost": its cost, "cost_zero": the cost of the zero correction (the prediction), "correction": the correction applied to the initial mean ("top": zeros; with "best" initial_guess is prediction · correction_to_pose(correction)), "prediction": the constant-velocity prediction the grid is centred on, "nodes": the nodes handed over as particles ("top" only)}; cfg.seed_levels > 1: "index" gives way to "lattice" (the best node's integer vector on the finest lattice, "nodes" likewise [P, 6]) and "levels", "fine_step", "nodes_scored", "cost_level0" (level 0's best cost) and "fitness_zero" (inliers / rows of the prediction) are added; cfg.seed_skip_fitness > 0: "searched" and "fitness_zero" are added, and a scan that was not searched has only those two, "cost_zero" and "prediction"
 
 
@@ -1681,6 +1693,8 @@ class RegistrationPipeline:
             s.add_cloud(source, target, init)                                                                   # :583
             self.bytes_h2d += (source.shape[0] + target.shape[0]) * 24
         t1 = time.perf_counter()
+        if c.prior_sigma is not None:   # centred on the initial mean set below: the zero correction
+            s.set_pose_prior(np.zeros(6), c.prior_information())
         s.set_initial_mean(guess)                                                                               # :601
         state = s.stein_align()                                                                                 # :602
         if state != SteinICPState.ALIGN_SUCCESS:                                                                # :602-604
@@ -1698,6 +1712,8 @@ class RegistrationPipeline:
                          s.get_particle_weight(), t1 - t0, 0.0, int(state), with_normal)
         res.modes = modes
         res.seed = seed
+        if c.prior_sigma is not None:   # no policy here: the number a gate would read
+            res.prior_chi2 = float(np.sum((np.asarray(corr, np.float64) / np.asarray(c.prior_sigma, np.float64)) ** 2))
         if c.eval_dist > 0:   # the number a caller may gate the map update on (no policy here)
             ev = s.evaluate(c.eval_dist, pose)
             res.fitness, res.inlier_rmse = ev.fitness, ev.inlier_rmse

@@ -487,6 +487,27 @@ class _SolverBase:
                                                    C.byref(n)), "svnicp_get_plane_stats")
         return out, int(n.value)
 
+    # -- Gaussian pose prior on the correction (include/svnicp_hip.h "pose prior") ---------------------------------------------
+    def set_pose_prior(self, mean6=None, information=None) -> None:
+        """A Gaussian prior on the correction pose from the next registration on: ``mean6`` = [t ; rotation vector] in the
+        coordinates of ``get_transformation`` (None: zero), ``information`` the 6x6 matrix Lambda in the order (t, r) and in the
+        units of the cost: for a metric covariance Sigma and a point noise sigma_pt, sigma_pt**2 * inv(Sigma).
+        ``information=None`` turns the prior off.  SVGD mode refuses at ``stein_align``."""
+        dp = C.POINTER(C.c_double)
+        if information is None:
+            self._check(self._L.svnicp_set_pose_prior(self._h, None, None), "svnicp_set_pose_prior")
+            return
+        m = np.ascontiguousarray(np.zeros(6) if mean6 is None else np.asarray(mean6, np.float64).reshape(6))
+        lam = np.ascontiguousarray(np.asarray(information, np.float64).reshape(36))
+        self._check(self._L.svnicp_set_pose_prior(self._h, m.ctypes.data_as(dp), lam.ctypes.data_as(dp)), "svnicp_set_pose_prior")
+
+    def pose_prior(self):
+        """(mean6, information [6, 6]) of the prior the next registration runs with, or None when it is off."""
+        on, m, lam = C.c_int(0), np.zeros(6, np.float64), np.zeros((6, 6), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.svnicp_get_pose_prior(self._h, C.byref(on), m.ctypes.data_as(dp), lam.ctypes.data_as(dp)), "svnicp_get_pose_prior")
+        return (m, lam) if on.value else None
+
     # -- evaluate a registration (include/svnicp_hip.h "evaluate a registration") ---------------------------------------------
     def evaluate(self, max_corr_dist: float, pose=None) -> RegistrationEval:
         """Fitness, inlier RMSE and (with normals) plane RMSE of ``pose`` (4x4, map <- sensor) against the whole target, on
