@@ -464,6 +464,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   if (k == "knn") { if (v == "auto") t.knn = {}; else if (v == "v1") t.knn = {false, KnnKernel::Stream}; else if (v == "v2") t.knn = {false, KnnKernel::SeededScan};
                     else if (v == "brute") t.knn = {false, KnnKernel::Brute}; else if (v == "tiles") t.knn = {false, KnnKernel::Tiles}; else ok = false; }
   else if (k == "knn_prefilter") { if (v == "mfma") t.knn_prefilter_mfma = 1; else if (v == "valu") t.knn_prefilter_mfma = 0; else ok = false; }
+  else if (k == "seed_rank") { if (v == "bounded") t.seed_rank_full = 0; else if (v == "full") t.seed_rank_full = 1; else ok = false; }
   else if (k == "fallback_sliced_max") ok = num(-1, 1 << 20, &t.fallback_sliced_max);
   else if (k == "accum") { if (v == "f64") t.accum = 0; else if (v == "valu") t.accum = 1; else if (v == "split") t.accum = 3; else ok = false; }
   else if (k == "update") { if (v == "auto") t.update_fused = 0; else if (v == "fused") t.update_fused = 1; else ok = false; }

@@ -86,6 +86,7 @@ struct KnnTilesArgs {
   const float4* tile_a;           // [n_tiles][8][64]: (x', y', z', |t'|²) of the tile's 512 slots in MFMA A-operand order
   const float4* tile_o;           // [n_tiles]: the tile's origin (float32) | C_t = max |t'|₂, rounded up (+inf: no bound)
   int prefilter_mfma;             // 1: the scan kernel scores on the bf16 matrix pipe, 0: the float32 VALU loop
+  int seed_rank_full;             // 0: the seed kernel's rank phase scores only the tiles that can still be picked (seed_rank = bounded), 1: all of a visited group (full)
   int64_t M, Mp;
   int n_tiles;
   int64_t b_lo, b_hi;

@@ -335,6 +335,10 @@ __device__ void select_query(const KnnTilesArgs& a, int64_t r, const QRec& rec, 
   }
 }
 
+// BOUNDED (option seed_rank = bounded, the default): inside a visited group of 64 tiles the rank phase scores only the
+// tiles whose bound to the wave's query box can still enter a top-NSQ list; false (seed_rank = full): every tile of the
+// group.  The picks, and with them everything the kernel hands on, are the same (DESIGN §4.1 "bounded ranking").
+template <bool BOUNDED>
 __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x & (kWave - 1);
@@ -345,7 +349,7 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
   // (One wave per group did all four batches in sequence: 2048 long-running waves at C3, two per SIMD, the slowest 1.6x
   // the median, set the kernel time.)
   constexpr size_t kShared = sizeof(QD) * QW + sizeof(QF) * QW + 4 * sizeof(int) * QW + sizeof(unsigned int) * (MAX_TILES / 32);
-  constexpr size_t kScratch = sizeof(float2) * QB * kWave + 512;   // per wave: two minima per (query of the batch, lane); rank: 64 boxes
+  constexpr size_t kScratch = sizeof(float2) * QB * kWave + 512;   // per wave: two minima per (query of the batch, lane); rank: 64 boxes, 128 group keys
   static_assert(QB * WAVES == QW, "one batch per wave");
   QD* qd = reinterpret_cast<QD*>(smem);
   QF* qf = reinterpret_cast<QF*>(smem + sizeof(QD) * QW);
@@ -403,6 +407,10 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
     // each query (lane) picks its own NSQ nearest tiles: point-to-box bound, ties (inside several
     // boxes) broken toward the nearest box centre; the workgroup scans the union of all picks
     if (wave == 0) {
+      // The rank phase is one wave's serial work with the group's other three waves parked behind it, while the SIMD's
+      // other waves — tile loops of the CU's other workgroups — are issue-bound: it goes first.  (Measured over 12
+      // launches, alternating: C3 217 -> 205 us, C5 542 -> 506 us.)
+      __builtin_amdgcn_s_setprio(2);
       for (int e = lane; e < nwords; e += kWave) tbits[e] = 0u;
       wave_sync();
       const float px = qf[lane].x, py = qf[lane].y, pz = qf[lane].z;
@@ -417,21 +425,58 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
       // fourth-best score: no tile of a farther group can enter any top-NSQ list, so the picks equal those of a full
       // pass — at a cost that no longer grows with the number of tiles (2 M-point targets: 4096 tiles).
       const int n_groups = (n_tiles + kWave - 1) / kWave;  // <= 128
+      // The group boxes are folded 64 / GP groups at a time: GP lanes per group (the largest power of two with
+      // n_groups·GP <= 64, at least 8) read the group's tiles GP apart — a load touches 64 / GP runs of GP consecutive
+      // floats — and fold over their GP lanes: 6·log2(GP) shuffles per batch (C3: 8 groups, one batch, 18 shuffles; C5: 64
+      // groups, 8 batches) where a full-wave fold per group took 36 per group.  min / max do not depend on the order, so the
+      // boxes are those of the full-wave fold.  The keys pass through LDS to lane = group.
       unsigned int gkey[2] = {0xffffffffu, 0xffffffffu};     // lane's groups: bound (7 low mantissa bits cut) | group index
-      for (int g = 0; g < n_groups; ++g) {
-        const int tl = g * kWave + lane;
-        const float inf = __builtin_huge_valf();
-        float lo0 = inf, lo1 = inf, lo2 = inf, hi0 = -inf, hi1 = -inf, hi2 = -inf;
-        if (tl < n_tiles) { lo0 = bx_lo0[tl]; lo1 = bx_lo1[tl]; lo2 = bx_lo2[tl]; hi0 = bx_hi0[tl]; hi1 = bx_hi1[tl]; hi2 = bx_hi2[tl]; }
-        for (int off = 32; off > 0; off >>= 1) {
-          lo0 = __builtin_fminf(lo0, __shfl_xor(lo0, off, kWave)); hi0 = __builtin_fmaxf(hi0, __shfl_xor(hi0, off, kWave));
-          lo1 = __builtin_fminf(lo1, __shfl_xor(lo1, off, kWave)); hi1 = __builtin_fmaxf(hi1, __shfl_xor(hi1, off, kWave));
-          lo2 = __builtin_fminf(lo2, __shfl_xor(lo2, off, kWave)); hi2 = __builtin_fmaxf(hi2, __shfl_xor(hi2, off, kWave));
+      {
+        unsigned int* gk = reinterpret_cast<unsigned int*>(scratch + sizeof(float4) * 2 * kWave);   // [128], behind boxs
+        int lgp = 3;
+        while (lgp < 6 && (n_groups << (lgp + 1)) <= kWave) ++lgp;
+        const int GP = 1 << lgp, sub = lane & (GP - 1), gpb = kWave >> lgp;
+        for (int g0 = 0; g0 < n_groups; g0 += gpb) {
+          const int g = g0 + (lane >> lgp);
+          const float inf = __builtin_huge_valf();
+          float lo0 = inf, lo1 = inf, lo2 = inf, hi0 = -inf, hi1 = -inf, hi2 = -inf;
+          if (g < n_groups) {
+#pragma unroll 8
+            for (int i = sub; i < kWave; i += GP) {
+              const int tl = g * kWave + i;
+              if (tl < n_tiles) {
+                lo0 = __builtin_fminf(lo0, bx_lo0[tl]); lo1 = __builtin_fminf(lo1, bx_lo1[tl]); lo2 = __builtin_fminf(lo2, bx_lo2[tl]);
+                hi0 = __builtin_fmaxf(hi0, bx_hi0[tl]); hi1 = __builtin_fmaxf(hi1, bx_hi1[tl]); hi2 = __builtin_fmaxf(hi2, bx_hi2[tl]);
+              }
+            }
+          }
+          for (int off = GP >> 1; off > 0; off >>= 1) {   // stays inside the group's GP lanes
+            lo0 = __builtin_fminf(lo0, __shfl_xor(lo0, off, kWave)); hi0 = __builtin_fmaxf(hi0, __shfl_xor(hi0, off, kWave));
+            lo1 = __builtin_fminf(lo1, __shfl_xor(lo1, off, kWave)); hi1 = __builtin_fmaxf(hi1, __shfl_xor(hi1, off, kWave));
+            lo2 = __builtin_fminf(lo2, __shfl_xor(lo2, off, kWave)); hi2 = __builtin_fmaxf(hi2, __shfl_xor(hi2, off, kWave));
+          }
+          const float glb = box_lb2(wlo0, wlo1, wlo2, whi0, whi1, whi2, lo0, lo1, lo2, hi0, hi1, hi2);  // empty boxes give +inf
+          if (sub == 0 && g < n_groups) gk[g] = (glb < inf) ? ((__float_as_uint(glb) & ~127u) | (unsigned int)g) : 0xffffffffu;
         }
-        const float glb = box_lb2(wlo0, wlo1, wlo2, whi0, whi1, whi2, lo0, lo1, lo2, hi0, hi1, hi2);  // empty boxes give +inf or NaN
-        const unsigned int key = (glb < inf) ? ((__float_as_uint(glb) & ~127u) | (unsigned int)g) : 0xffffffffu;
-        if (lane == (g & (kWave - 1))) gkey[g >> 6] = key;
+        wave_sync();
+        if (lane < n_groups) gkey[0] = gk[lane];
+        if (lane + kWave < n_groups) gkey[1] = gk[lane + kWave];
       }
+      // one tile (its box at boxs[2·i]) against every query of the wave: insertion into the sorted top-NSQ lists
+      auto score_tile = [&](int i, int tile) {
+        const float4 b0 = boxs[2 * i], b1 = boxs[2 * i + 1];
+        const float l0 = b0.x, l1 = b0.y, l2 = b0.z, h0 = b0.w, h1 = b1.x, h2 = b1.y;
+        const float lb = box_lb2(px, py, pz, px, py, pz, l0, l1, l2, h0, h1, h2);
+        const float c0 = px - 0.5f * (l0 + h0), c1 = py - 0.5f * (l1 + h1), c2 = pz - 0.5f * (l2 + h2);
+        const float score = lb + 1e-3f * (c0 * c0 + c1 * c1 + c2 * c2);
+        unsigned long long key = (score < __builtin_huge_valf()) ? (((unsigned long long)__float_as_uint(score) << 32) | (unsigned int)tile) : ~0ull;
+#pragma unroll
+        for (int u = 0; u < NSQ; ++u) {
+          const unsigned long long lo = key < best[u] ? key : best[u];
+          key = key < best[u] ? best[u] : key;
+          best[u] = lo;
+        }
+      };
       for (;;) {
         unsigned int kmin = gkey[0] < gkey[1] ? gkey[0] : gkey[1];
         for (int off = 32; off > 0; off >>= 1) { const unsigned int o = __shfl_xor(kmin, off, kWave); kmin = o < kmin ? o : kmin; }
@@ -444,27 +489,58 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
         if (lane == (gsel & (kWave - 1))) gkey[gsel >> 6] = 0xffffffffu;
         const int t0 = gsel * kWave;
         const int tl = t0 + lane;
+        unsigned int tkey = 0xffffffffu;   // BOUNDED, lane = tile: bound between the wave's query box and the tile's box (6 low mantissa bits cut) | lane
         if (tl < n_tiles) {
-          boxs[2 * lane] = make_float4(bx_lo0[tl], bx_lo1[tl], bx_lo2[tl], bx_hi0[tl]);
-          boxs[2 * lane + 1] = make_float4(bx_hi1[tl], bx_hi2[tl], 0.f, 0.f);
+          const float l0 = bx_lo0[tl], l1 = bx_lo1[tl], l2 = bx_lo2[tl], h0 = bx_hi0[tl], h1 = bx_hi1[tl], h2 = bx_hi2[tl];
+          boxs[2 * lane] = make_float4(l0, l1, l2, h0);
+          boxs[2 * lane + 1] = make_float4(h1, h2, 0.f, 0.f);
+          if constexpr (BOUNDED) {
+            const float lbt = box_lb2(wlo0, wlo1, wlo2, whi0, whi1, whi2, l0, l1, l2, h0, h1, h2);
+            if (lbt < __builtin_huge_valf()) tkey = (__float_as_uint(lbt) & ~63u) | (unsigned int)lane;
+          }
         }
         wave_sync();
-        const int cntt = (n_tiles - t0) < kWave ? (n_tiles - t0) : kWave;
-#pragma unroll 4
-        for (int i = 0; i < cntt; ++i) {
-          const float4 b0 = boxs[2 * i], b1 = boxs[2 * i + 1];
-          const float l0 = b0.x, l1 = b0.y, l2 = b0.z, h0 = b0.w, h1 = b1.x, h2 = b1.y;
-          const int tile = t0 + i;
-          const float lb = box_lb2(px, py, pz, px, py, pz, l0, l1, l2, h0, h1, h2);
-          const float c0 = px - 0.5f * (l0 + h0), c1 = py - 0.5f * (l1 + h1), c2 = pz - 0.5f * (l2 + h2);
-          const float score = lb + 1e-3f * (c0 * c0 + c1 * c1 + c2 * c2);
-          unsigned long long key = (score < __builtin_huge_valf()) ? (((unsigned long long)__float_as_uint(score) << 32) | (unsigned int)tile) : ~0ull;
+        if constexpr (BOUNDED) {
+          // For every query q of the wave score(q, t) >= lb(q, t) >= LBt: box_lb2 is monotone in each gap, and the wave's box
+          // holds fl32(q) by its outward rounding; cutting mantissa bits only lowers LBt.  A tile with LBt above every active
+          // query's fourth-best score (a list that is not full votes to go on: its "score" is a NaN pattern) cannot enter a
+          // list now or later — the fourth-best scores only fall — so it is not scored.  Tiles are taken nearest first, which
+          // brings the fourth-best scores down soonest: the keys are sorted across the wave when more than a few tiles pass
+          // the group's own test (w4 above), and the group is left at the first tile that fails.  A tile whose box is empty
+          // or not finite has no key; its score could never be inserted either.
+          auto passes = [&]() { return __ballot(tkey != 0xffffffffu && __uint_as_float(tkey & ~63u) <= w4); };
+          unsigned long long todo = passes();
+          const bool sorted = __popcll(todo) > 4;
+          if (sorted) {
 #pragma unroll
-          for (int u = 0; u < NSQ; ++u) {  // insertion into the sorted top-NSQ
-            const unsigned long long lo = key < best[u] ? key : best[u];
-            key = key < best[u] ? best[u] : key;
-            best[u] = lo;
+            for (int k = 2; k <= kWave; k <<= 1)
+#pragma unroll
+              for (int j = k >> 1; j > 0; j >>= 1) {   // bitonic network over the lanes, ascending
+                const unsigned int o = (unsigned int)__shfl_xor((int)tkey, j, kWave);
+                const bool keep_min = ((lane & k) == 0) == ((lane & j) == 0);
+                const unsigned int mn = o < tkey ? o : tkey, mx = o < tkey ? tkey : o;
+                tkey = keep_min ? mn : mx;
+              }
+            todo = passes();
           }
+          while (todo) {
+            const int i = (int)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const unsigned int k = (unsigned int)__builtin_amdgcn_readlane((int)tkey, i);
+            const float lbt = __uint_as_float(k & ~63u);
+            const float b4 = __uint_as_float((unsigned int)(best[NSQ - 1] >> 32));
+            if (!__ballot(lane < nq && !(b4 < lbt))) {
+              if (sorted) break;
+              continue;
+            }
+            if (a.phase_cycles) pacc[7] += 1;
+            score_tile((int)(k & 63u), t0 + (int)(k & 63u));
+          }
+        } else {
+          const int cntt = (n_tiles - t0) < kWave ? (n_tiles - t0) : kWave;
+          if (a.phase_cycles) pacc[7] += cntt;
+#pragma unroll 4
+          for (int i = 0; i < cntt; ++i) score_tile(i, t0 + i);
         }
         wave_sync();
       }
@@ -473,6 +549,7 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
         for (int i = 0; i < NSQ; ++i)
           if (best[i] != ~0ull) { const unsigned int t = (unsigned int)(best[i] & 0xffffffffull); atomicOr(&tbits[t >> 5], 1u << (t & 31)); }
       }
+      __builtin_amdgcn_s_setprio(0);
     }
     phase_mark(0);
     __syncthreads();
@@ -562,7 +639,7 @@ __global__ __launch_bounds__(256) void k_knn_seed(KnnTilesArgs a) {
     for (int i = 0; i < 5; ++i) atomicAdd(&a.phase_cycles[i], pacc[i]);
     unsigned long long* pw = a.phase_cycles + 8 + 8 * ((size_t)grp * WAVES + wave);  // per-wave record
 #pragma unroll
-    for (int i = 0; i < 7; ++i) pw[i] = pacc[i];
+    for (int i = 0; i < 8; ++i) pw[i] = pacc[i];   // [7]: tiles scored in the rank phase (the totals' [7] is the scan kernel's)
   }
 }
 
@@ -942,10 +1019,10 @@ hipError_t launch_knn_tiles(const KnnTilesArgs& a, hipStream_t st) {
   if (a.n_tiles > MAX_TILES) return hipErrorInvalidValue;
   const size_t smem = sizeof(QD) * QW + sizeof(QF) * QW + 4 * sizeof(int) * QW + sizeof(unsigned int) * (MAX_TILES / 32) +
                       (sizeof(float2) * QB * kWave + 512) * WAVES;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_seed),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  auto seed = a.seed_rank_full ? k_knn_seed<false> : k_knn_seed<true>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seed), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_knn_seed, dim3((unsigned)nb), dim3(256), smem, st, a);
+  hipLaunchKernelGGL(seed, dim3((unsigned)nb), dim3(256), smem, st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 sgrid((unsigned)((nq + QW - 1) / QW));

@@ -16,7 +16,8 @@ namespace svnicp {
 struct Tuning {
   KnnOption knn;                 // stage A kernel: automatic, or v1 | v2 | tiles | brute (stage_a_plan.hpp: plan_stage_a)
   int knn_prefilter_mfma = 1;    // stage A tile scan: 1 = pre-filter on the bf16 matrix pipe (knn_prefilter = mfma), 0 = float32 VALU loop (valu)
-  int fallback_sliced_max = -1;  // stage A: failed queries redone by target slices up to this many (-1 default)
+  int seed_rank_full = 0;        // stage A tile seed: 0 = the rank phase skips tiles behind the wave-wide bound (seed_rank = bounded), 1 = scores every tile of a visited group (full, A/B)
+  int fallback_sliced_max = -1; // stage A: failed queries redone by target slices up to this many (-1 default)
   int accum = 3;                 // stage B: 0 f64 baseline, 1 f32 VALU search (fused), 3 search + accumulate kernels
   int update_fused = 0;          // Stein update: 1 = one fused kernel for 2 <= P <= fused_update_max_p
   int fused_update_max_p = 128;  // above this the Stein step runs as workgroup-parallel kernels

@@ -176,7 +176,9 @@ struct StageA {
               qb, h[0] / nwg, h[1] / nwg, h[2] / nwg, h[3] / nwg, h[4] / nwg);
       return SVNICP_OK;
     }
-    fprintf(stderr, "[svnicp] k_knn_tiles wave cycles: rank %llu seed %llu scan %llu barrier waits + hand-over %llu | counts: seed tiles %llu scan tiles %llu scan (query, tile) pairs %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
+    unsigned long long ranked = 0;   // tiles scored in the seed kernel's rank phase: [7] of the per-wave records
+    for (size_t w = 0; w < dbg_waves; ++w) ranked += h[8 + 8 * w + 7];
+    fprintf(stderr, "[svnicp] k_knn_tiles wave cycles: rank %llu seed %llu scan %llu barrier waits + hand-over %llu | counts: rank tiles scored %llu seed tiles %llu scan tiles %llu scan (query, tile) pairs %llu\n", h[0], h[1], h[2], h[3], ranked, h[4], h[5], h[6]);
     // per-wave records of k_knn_seed: [0] rank (wave 0 of a group only) [1] seed [3] barrier waits [5] tile loop [6] K-th bisection
     auto column = [&](const char* tag, int col, unsigned long long floor_) {
       std::vector<unsigned long long> v;
@@ -239,7 +241,7 @@ struct StageA {
       k.src = qsrc; k.pose = pose; k.qorder = qord;
       k.tx = tx.p; k.ty = ty.p; k.tz = tz.p; k.txf = txf.p; k.tyf = tyf.p; k.tzf = tzf.p;
       k.torig = torig.p; k.tile_box = tile_box.p; k.emax_bits = emax.p;
-      k.tile_a = tile_a.p; k.tile_o = tile_o.p; k.prefilter_mfma = e.tune.knn_prefilter_mfma;
+      k.tile_a = tile_a.p; k.tile_o = tile_o.p; k.prefilter_mfma = e.tune.knn_prefilter_mfma; k.seed_rank_full = e.tune.seed_rank_full;
       k.M = e.M; k.Mp = plan.Mp; k.n_tiles = (int)(plan.Mp / kTileSlots); k.b_lo = b_lo; k.b_hi = b_hi; k.K = K; k.S2 = plan.S2;
       k.pool = pool2.p; k.out_idx = out_idx; k.out_d2 = tbl ? nullptr : out_d2;
       k.tgt = e.tgt;
