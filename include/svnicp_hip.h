@@ -226,6 +226,42 @@ int svnicp_set_target_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t M, i
 int svnicp_get_target_normals(svnicp_ctx *ctx, double *outMx3);
 int svnicp_get_plane_stats(svnicp_ctx *ctx, double *outPx2, int64_t *normal_passes);
 
+/* ---- generalized-ICP residual (an extension) ---------------------------------------------------------
+ * svnicp_set_residual_gicp(huber_delta, normal_k, epsilon): from the next registration on, SVN mode weighs every pair by the
+ * combined covariance of BOTH local surfaces.  Notation of the plane residual: Rt | tt the particle's total pose, s the source
+ * point, q the search kernel's winner, e = Ts - q, n_q the winner's unit normal, n_s the source point's unit normal.
+ *   C(n) = I - (1 - epsilon) n n^T           regularised surface covariance: epsilon along the normal, 1 in the plane
+ *   m = Rt^T n_q,  u = Rt^T e,  S = C(m) + C(n_s),  W = 2 epsilon S^-1     (closed-form inverse in float64; cond(S) <= 1/epsilon)
+ *   rho = sqrt(u^T W u),  w = 1 for rho <= huber_delta else huber_delta / rho,  G = [I3 | -[s]x]
+ *   H = sum w G^T W G + 1e-6 I,  b = sum w G^T W u         over the accepted pairs; W is frozen at the linearisation pose, so b
+ *                                                          is the exact gradient of sum Huber(rho) with W held fixed
+ * The factor 2 epsilon gives the cost the plane residual's units: parallel normals weigh 1 along the normal and epsilon across
+ * it, W = (1 - epsilon) m m^T + epsilon I; epsilon = 1 gives W = I, the unweighted point-to-point cost.  huber_delta and the
+ * pose prior's prior_point_sigma keep their meaning.  epsilon: 0 = 1e-3, else in [1e-6, 1]; huber_delta > 0 (+inf = unweighted);
+ * normal_k 0 = 16, else 4..64, for BOTH clouds.
+ * Accepted pairs: d2 < max_dist (the project's gate), the winner has a normal AND the source row has one; a rejected pair
+ * contributes exact zeros.  Target normals: exactly as in plane mode (svnicp_set_target_normals, svnicp_get_target_normals,
+ * svnicp_map_query_normals, or the target's own pass).  Source normals: those of svnicp_set_source_normals, else estimated when
+ * the registration begins from each source point's normal_k nearest SOURCE points (the same kernel and validity rule as the
+ * target's pass, neighbours from a stage A whose target is the source cloud); kept until the source or normal_k changes.
+ * The mode is entered only here (svnicp_set_residual(2, ...) stays SVNICP_ERR_INVALID) and left by svnicp_set_residual(POINT |
+ * PLANE, ...).  It runs the plane residual's launches with its own accumulate kernel, so the Stein step, the pose prior, early
+ * stop, history, traces, svnicp_evaluate, svnicp_eval_information (forms point and plane), svnicp_score_particles and
+ * svnicp_particle_modes behave as on a plane-mode context; svnicp_plane_record_devptr / svnicp_plane_stats_devptr tap its
+ * records ([P][2] = {accepted pairs, sum w rho^2}).
+ * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID: everything plane mode refuses, and a source of fewer
+ * than normal_k points without supplied source normals. */
+#define SVNICP_RESIDUAL_GICP 2
+int svnicp_set_residual_gicp(svnicp_ctx *ctx, double huber_delta, int normal_k, double epsilon);
+/* optional: normals of the current source, double [B][3], host or device (copied): the rules of svnicp_set_target_normals.
+ * Must follow the svnicp_set_source / svnicp_set_clouds it belongs to, with the same B; dropped by the next one. */
+int svnicp_set_source_normals(svnicp_ctx *ctx, const double *n_xyz, int64_t B, int mem_kind);
+/* taps: the supplied or estimated unit normals of the source (SVNICP_ERR_INVALID before there are any); per particle
+ * {accepted pairs, sum w rho^2} of the last iteration run and the normal passes run so far, {target, source} (either pointer
+ * may be NULL; outPx2 needs a finished registration in generalized-ICP mode) */
+int svnicp_get_source_normals(svnicp_ctx *ctx, double *outBx3);
+int svnicp_get_gicp_stats(svnicp_ctx *ctx, double *outPx2, int64_t passes2[2]);
+
 /* ---- Gaussian pose prior on the correction (an extension: the reference's posterior has no prior) --
  * svnicp_set_pose_prior(ctx, mean6, info36): from the next svnicp_align_begin on, SVN mode minimises, per particle,
  * 1/2 sum w |e|^2 + 1/2 e^T Lambda e with e = [t_p - mu_t ; Log(R_mu^T R_p)], (R_p, t_p) the particle's CORRECTION pose (not
@@ -720,7 +756,7 @@ int svnicp_get_ambiguous_pairs(svnicp_ctx *ctx, int64_t *out);
  *   0 stage A (ordering + k_knn_tiles/k_knn_scan + fallback)   1 k_build_table*
  *   2 k_stein_search_bf16 (split stage B only)                 3 k_stein_accumulate* (fused variants: whole stage B)
  *   4 k_reduce_partials                                        5 k_particle_update / k_upd_*
- * (plane residual: 3 = k_plane_accumulate, 4 = k_plane_finalize) */
+ * (plane residual: 3 = k_plane_accumulate, 4 = k_plane_finalize; generalized-ICP residual: 3 = k_gicp_accumulate, 4 = the same) */
 #define SVNICP_KERNEL_CLASSES 6
 /* on: 0 = off, 1 = every class, otherwise a mask with bit (class + 1) set for each class to bracket (the event
  * pairs cost ~5 us of stream time each, so a timed run brackets only what it reports) */

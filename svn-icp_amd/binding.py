@@ -248,6 +248,10 @@ def load_library():
     L.svnicp_set_target_normals.argtypes = [vp, vp, C.c_int64, C.c_int]
     L.svnicp_get_target_normals.argtypes = [vp, dp]
     L.svnicp_get_plane_stats.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    L.svnicp_set_residual_gicp.argtypes = [vp, C.c_double, C.c_int, C.c_double]
+    L.svnicp_set_source_normals.argtypes = [vp, vp, C.c_int64, C.c_int]
+    L.svnicp_get_source_normals.argtypes = [vp, dp]
+    L.svnicp_get_gicp_stats.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     L.svnicp_evaluate.argtypes = [vp, dp, dp, C.c_double, C.POINTER(EvalStruct)]
     for name in ("svnicp_eval_index_devptr", "svnicp_eval_dist2_devptr"):
         getattr(L, name).argtypes = [vp]

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device_buffer.hpp"
+#include "gicp_pair_device.hpp"
 #include "information_solve.hpp"
 #include "kernels.hpp"
 #include "pose_prior.hpp"
@@ -101,6 +102,22 @@ struct PlaneState {
   DevBuf<int32_t> nbr;        // [rows of one pass block][normal_k] neighbour indices
   DevBuf<double> nbr_d2;
   DevBuf<double> partial, Hb, stats;   // [grid_x][Ppad][kPlaneSums], [P][42], [P][2] (the last two allocated max(P, Ppad) rows long)
+};
+
+// generalized-ICP residual (svnicp_set_residual_gicp; csrc/gicp_icp.hip).  It runs in plane mode's place
+// (PlaneState::residual == SVNICP_RESIDUAL_GICP, PlaneState::on, the same partial / Hb / stats) and adds the source's side.
+struct GicpState {
+  double eps = kGicpEpsilonDefault;
+  bool supplied = false;      // rec holds normals the caller gave for the current source (dropped by svnicp_set_source)
+  bool estimated = false;     // rec holds normals estimated from the current source with est_k neighbours
+  int est_k = 0;
+  int64_t passes = 0;         // source normal passes run since creation
+  bool on = false;            // the registration begun last runs the generalized-ICP residual
+  DevBuf<double> rec;         // [B][6] xyz | unit normal, 0 = no normal here
+  DevBuf<double> nsup;        // upload staging of supplied normals
+  StageA sa;                  // the source as its own target (M = B), planned for K = normal_k: the exact neighbours of the source's
+                              // normal pass, block by block in its own result buffers cand_idx / cand_d2
+  Pose0 ident{};              // … searched at the identity
 };
 
 // svnicp_evaluate (csrc/evaluate.hip): its own buffers, nothing of the registration's
@@ -194,7 +211,7 @@ struct svnicp_ctx {
   Pose0 pose0{};
   Tuning tune{};
   CloudState cloud; StageA sa; StageB sb; SteinState st;
-  Sharding shard; MiniBatch mb; PlaneState pl; PriorState pr; EvalState ev; ScoreState sc; ModesState md;
+  Sharding shard; MiniBatch mb; PlaneState pl; GicpState gi; PriorState pr; EvalState ev; ScoreState sc; ModesState md;
   Trace tr; Profiling prof; DebugCounters dbg; Progress run;
 };
 
@@ -237,15 +254,22 @@ static StageAEnv stage_a_env(const svnicp_ctx* c) {
   return {c->stream, c->tune, c->num_cus, c->prm.record_trace != 0, c->cloud.tgt.p, c->B, c->M, c->pose0};
 }
 
-// what the rules of registration_plan.hpp read of the context; plane, prior: what this registration runs with
-static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane, bool prior) {
+// stage A's view of the source cloud as a target of its own (the source's normal pass in generalized-ICP mode)
+static StageAEnv source_stage_a_env(const svnicp_ctx* c) {
+  return {c->stream, c->tune, c->num_cus, false, c->cloud.src.p, c->B, c->B, c->gi.ident};
+}
+
+// what the rules of registration_plan.hpp read of the context; plane, gicp, prior: what this registration runs with (gicp
+// runs the plane residual's launch shape: plane is then set as well)
+static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane, bool gicp, bool prior) {
   RegistrationFacts f;
   f.P = c->P; f.K = c->K; f.I = c->prm.iterations; f.B = c->B; f.M = c->M;
   f.svgd = c->prm.mode == SVNICP_MODE_SVGD; f.check_early_stop = c->prm.check_early_stop != 0; f.record_trace = c->prm.record_trace != 0;
   f.profiling = c->prof.on;
   f.shard_set = c->shard.set; f.p_lo = c->shard.p_lo; f.p_hi = c->shard.p_hi; f.row_world = c->shard.row_world;
   f.batch = c->mb.batch; f.explicit_tab = c->mb.explicit_tab; f.tab_I = c->mb.tab_I;
-  f.plane = plane; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
+  f.plane = plane || gicp; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
+  f.gicp = gicp; f.source_normals_supplied = c->gi.supplied;
   f.weighting = c->sc.kind;
   f.prior = prior;
   return f;
@@ -362,6 +386,7 @@ int svnicp_set_source(svnicp_ctx* c, const double* src, int64_t B, int mem_kind)
   if (const int rc = upload_cloud(c, c->cloud.src, src, B, mem_kind)) return rc;
   c->B = B;
   c->cloud.src_set = true;
+  c->gi.supplied = false; c->gi.estimated = false;   // normals belong to the source they were given or estimated for
   c->ev.mark_stale("the source changed since the last svnicp_evaluate");
   return SVNICP_OK;
 }
@@ -489,7 +514,7 @@ int svnicp_set_option(svnicp_ctx* c, const char* name, const char* value) {
   c->run.have_candidates = false;
   c->sa.held = TargetLayout::None;
   // svnicp_iter_accumulate now refuses until the next svnicp_align_begin; svnicp_iter_update goes on and follows the new options
-  if (c->run.began) c->st.step = plan_step(registration_facts(c, c->pl.on, c->pr.on), c->tune, c->sb.plan);
+  if (c->run.began) c->st.step = plan_step(registration_facts(c, c->pl.on, c->gi.on, c->pr.on), c->tune, c->sb.plan);
   return SVNICP_OK;
 }
 
@@ -524,7 +549,12 @@ static bool normal_pass_due(const svnicp_ctx* c) {
   return c->pl.on && !c->pl.supplied && !(c->pl.estimated && c->pl.est_k == c->pl.normal_k);
 }
 
+static bool source_normal_pass_due(const svnicp_ctx* c) {
+  return c->gi.on && !c->gi.supplied && !(c->gi.estimated && c->gi.est_k == c->pl.normal_k);
+}
+
 static int prepare_plane(svnicp_ctx* c);
+static int prepare_gicp(svnicp_ctx* c);
 int svnicp_align_begin(svnicp_ctx* c) {
   CTX_CHECK(c);
   if (!c->cloud.src_set || !c->cloud.tgt_set || !c->run.particles_set)
@@ -532,8 +562,9 @@ int svnicp_align_begin(svnicp_ctx* c) {
   if (bind(c)) return SVNICP_ERR_HIP;
   const int I = c->prm.iterations, P = c->P;
   const int64_t B = c->B;
-  const bool plane = c->pl.residual == SVNICP_RESIDUAL_PLANE;
-  const RegistrationFacts f = registration_facts(c, plane, c->pr.set);
+  const bool gicp = c->pl.residual == SVNICP_RESIDUAL_GICP;
+  const bool plane = c->pl.residual == SVNICP_RESIDUAL_PLANE || gicp;   // the generalized-ICP residual runs in the plane residual's place
+  const RegistrationFacts f = registration_facts(c, plane, gicp, c->pr.set);
   if (const char* why = minibatch_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kMinibatchRefusal) + why);
   if (c->mb.batch != 0 && c->mb.explicit_tab && !c->mb.tab_h.empty() && c->mb.tab_checked_B != B) {
     for (const int32_t v : c->mb.tab_h)
@@ -541,7 +572,9 @@ int svnicp_align_begin(svnicp_ctx* c) {
         return fail(c, SVNICP_ERR_INVALID, "svnicp_align: the mini-batch index table holds " + std::to_string(v) + ", outside [0, " + std::to_string(B) + ")");
     c->mb.tab_checked_B = B;
   }
-  if (const char* why = plane_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kPlaneRefusal) + why);
+  if (const char* why = gicp_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kGicpRefusal) + why);
+  if (!gicp)
+    if (const char* why = plane_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kPlaneRefusal) + why);
   if (const char* why = weighting_refusal(f, c->tune)) return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + why);
   if (f.weighting && score_tile_rows(P, c->K, true) < 1)
     return fail(c, SVNICP_ERR_INVALID, std::string(kWeightingRefusal) + "knn_count is too large for one row's candidates to fit the scoring kernel's LDS tile");
@@ -551,7 +584,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   // (the stage-A plan StageA::begin is about to make: every refusal comes before the context changes)
   const bool stage_a_k1 = StageA::plan_for(stage_a_env(c), r.Bq, c->K).can_search(1);
   if (const char* why = full_corr_refusal(f, c->tune, shape.f32, stage_a_k1)) return fail(c, SVNICP_ERR_INVALID, why);
-  c->pl.on = plane;
+  c->pl.on = plane; c->gi.on = gicp;
   c->pr.on = f.prior; c->pr.args = c->pr.next;
   c->ev.mark_stale("a registration began after the last svnicp_evaluate");   // svnicp_eval_information wants one afterwards
   c->sc.on = f.weighting != 0; c->sc.reg_refusal = scoring_refusal(f, c->tune);
@@ -629,6 +662,8 @@ int svnicp_align_begin(svnicp_ctx* c) {
   }
   if (plane)
     if (const int rc = prepare_plane(c)) return rc;
+  if (gicp)
+    if (const int rc = prepare_gicp(c)) return rc;
   c->st.step = plan_step(f, c->tune, c->sb.plan);
   c->run.began = true;
   c->st.finish_seen = false;
@@ -685,6 +720,33 @@ static int prepare_plane(svnicp_ctx* c) {
   if (rc) return rc;
   c->pl.estimated = true; c->pl.est_k = kn;
   c->pl.passes += 1;
+  return SVNICP_OK;
+}
+
+// generalized-ICP mode, behind prepare_plane: the source's record [B][6], estimated when no source normals were supplied and
+// the ones at hand were not estimated from this source with this normal_k.  The same per-point kernel as the target's pass;
+// the neighbours come from a stage A of the mode's own whose target is the source cloud (M = B), so whichever kernel family
+// it plans gives the exact normal_k nearest source points.  That stage A is planned for K = normal_k itself, so every family
+// can search (prepare_plane's refusal of the seeded scan is for a K other than the plan's), and its result buffers
+// [B][normal_k] hold one block's neighbour lists at a time.
+static int prepare_gicp(svnicp_ctx* c) {
+  const int kn = c->pl.normal_k;
+  if (!source_normal_pass_due(c)) return SVNICP_OK;
+  GicpState& g = c->gi;
+  g.ident = Pose0{};
+  g.ident.R0[0] = g.ident.R0[4] = g.ident.R0[8] = 1.0;
+  const int64_t B = c->B;
+  const StageAEnv env = source_stage_a_env(c);
+  g.sa.held = TargetLayout::None;   // the layout at hand is of an earlier source
+  if (const int rc = g.sa.begin(c, env, B, kn, {kn})) return rc;
+  HIPCHK(c, g.rec.ensure((size_t)B * 6));
+  const int rc = g.sa.search_blocks(c, env, c->cloud.src.p, B, kn, g.sa.cand_idx.p, g.sa.cand_d2.p, 0, [&](int64_t lo, int64_t n) {
+    HIPCHK(c, launch_target_normals(c->cloud.src.p, B, g.sa.cand_idx.p, lo, n, kn, g.rec.p, c->stream));
+    return (int)SVNICP_OK;
+  });
+  if (rc) return rc;
+  g.estimated = true; g.est_k = kn;
+  g.passes += 1;
   return SVNICP_OK;
 }
 
@@ -837,12 +899,20 @@ int svnicp_iter_accumulate(svnicp_ctx* c, int it) {
     HIPCHK(c, prof_end(c));
   }
   if (c->pl.on) {   // point-to-plane: the winner's record, Huber weight, H and b directly ([P][42] for the Stein step)
-    PlaneArgs pa{};
-    pa.src = c->cloud.src.p; pa.rec = c->pl.rec.p; pa.Rtot = c->st.Rtot.p; pa.B = c->B; pa.M = c->M; pa.p_lo = c->shard.p_lo; pa.p_hi = c->shard.p_hi;
-    pa.max_dist = c->prm.max_dist; pa.delta = c->pl.delta; pa.partial = c->pl.partial.p; pa.ctl = c->st.ctl.p;
-    pa.kidx = c->sb.kidx.p; pa.kbest = c->sb.kbest.p; pa.corr = a.corr;
     HIPCHK(c, prof_begin(c, KC_ACCUM));
-    HIPCHK(c, launch_plane_accumulate(c->sb.plan, pa, c->stream));
+    if (c->gi.on) {   // generalized ICP: the same place, inputs and records, and the source's record beside the target's
+      GicpArgs ga{};
+      ga.srec = c->gi.rec.p; ga.rec = c->pl.rec.p; ga.Rtot = c->st.Rtot.p; ga.B = c->B; ga.M = c->M; ga.p_lo = c->shard.p_lo; ga.p_hi = c->shard.p_hi;
+      ga.max_dist = c->prm.max_dist; ga.delta = c->pl.delta; ga.eps = c->gi.eps; ga.partial = c->pl.partial.p; ga.ctl = c->st.ctl.p;
+      ga.kidx = c->sb.kidx.p; ga.kbest = c->sb.kbest.p; ga.corr = a.corr;
+      HIPCHK(c, launch_gicp_accumulate(c->sb.plan, ga, c->stream));
+    } else {
+      PlaneArgs pa{};
+      pa.src = c->cloud.src.p; pa.rec = c->pl.rec.p; pa.Rtot = c->st.Rtot.p; pa.B = c->B; pa.M = c->M; pa.p_lo = c->shard.p_lo; pa.p_hi = c->shard.p_hi;
+      pa.max_dist = c->prm.max_dist; pa.delta = c->pl.delta; pa.partial = c->pl.partial.p; pa.ctl = c->st.ctl.p;
+      pa.kidx = c->sb.kidx.p; pa.kbest = c->sb.kbest.p; pa.corr = a.corr;
+      HIPCHK(c, launch_plane_accumulate(c->sb.plan, pa, c->stream));
+    }
     HIPCHK(c, prof_end(c));
     HIPCHK(c, prof_begin(c, KC_REDUCE));
     HIPCHK(c, launch_plane_finalize(c->pl.partial.p, c->sb.plan.grid_x, c->sb.plan.Ppad, c->shard.p_lo, nshard, c->pl.Hb.p, c->pl.stats.p,
@@ -984,7 +1054,7 @@ static int align_enqueue(svnicp_ctx* c, bool follow_stop) {
   if ((rc = svnicp_stage_candidates(c, 0, c->B))) return rc;
   if ((rc = svnicp_build_candidate_table(c))) return rc;
   c->st.small_launched = false;
-  const DrivePlan drive = plan_drive(registration_facts(c, c->pl.on, c->pr.on), c->tune, c->sb.plan, c->st.step, follow_stop);
+  const DrivePlan drive = plan_drive(registration_facts(c, c->pl.on, c->gi.on, c->pr.on), c->tune, c->sb.plan, c->st.step, follow_stop);
   c->st.drive = drive;
   c->st.drive.defer_fin = false;   // holds inside the loop below only: not in the persistent kernel, not in a caller's own split-phase loop
   if (drive.persistent_try) {
@@ -1346,6 +1416,53 @@ int svnicp_get_plane_stats(svnicp_ctx* c, double* outPx2, int64_t* normal_passes
   if (normal_passes) *normal_passes = c->pl.passes;
   if (!outPx2) return SVNICP_OK;
   if (!c->run.have_result || !c->pl.on) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_plane_stats: no registration with the point-to-plane residual yet");
+  return fetch(c, outPx2, c->pl.stats.p, (size_t)c->P * 16);
+}
+
+// ---- generalized-ICP residual ----
+int svnicp_set_residual_gicp(svnicp_ctx* c, double huber_delta, int normal_k, double epsilon) {
+  CTX_CHECK(c);
+  if (!(huber_delta > 0.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual_gicp: huber_delta must be positive (+inf: no down-weighting)");
+  if (normal_k != 0 && (normal_k < 4 || normal_k > 64)) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual_gicp: normal_k must be 0 (= 16) or in 4..64");
+  if (epsilon != 0.0 && !(epsilon >= kGicpEpsilonMin && epsilon <= 1.0))
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_set_residual_gicp: epsilon must be 0 (= 1e-3) or in [1e-6, 1]");
+  c->pl.residual = SVNICP_RESIDUAL_GICP; c->pl.delta = huber_delta; c->pl.normal_k = normal_k ? normal_k : 16;
+  c->gi.eps = epsilon != 0.0 ? epsilon : kGicpEpsilonDefault;
+  c->run.have_candidates = false;   // the stage-B plan follows the residual: svnicp_iter_accumulate refuses until the next svnicp_align_begin
+  return SVNICP_OK;
+}
+
+int svnicp_set_source_normals(svnicp_ctx* c, const double* n_xyz, int64_t B, int mem_kind) {
+  CTX_CHECK(c);
+  if (!n_xyz) return fail(c, SVNICP_ERR_INVALID, "svnicp_set_source_normals: null argument");
+  if (!c->cloud.src_set || B != c->B)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_set_source_normals: must follow the svnicp_set_source it belongs to, with the same point count");
+  if (bind(c)) return SVNICP_ERR_HIP;
+  HIPCHK(c, c->gi.nsup.ensure((size_t)B * 3));
+  HIPCHK(c, c->gi.rec.ensure((size_t)B * 6));
+  HIPCHK(c, hipMemcpyAsync(c->gi.nsup.p, n_xyz, (size_t)B * 24, mem_kind == SVNICP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_pack_normals(c->cloud.src.p, c->gi.nsup.p, B, c->gi.rec.p, c->stream));
+  if (mem_kind != SVNICP_MEM_DEVICE) HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may reuse its host buffer
+  c->gi.supplied = true; c->gi.estimated = false;
+  return SVNICP_OK;
+}
+
+int svnicp_get_source_normals(svnicp_ctx* c, double* outBx3) {
+  CTX_CHECK(c);
+  if (!outBx3) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_source_normals: null argument");
+  if (!c->gi.supplied && !c->gi.estimated) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_source_normals: no normals supplied or estimated for this source yet");
+  std::vector<double> rec((size_t)c->B * 6);
+  if (const int rc = fetch(c, rec.data(), c->gi.rec.p, rec.size() * 8)) return rc;
+  for (int64_t i = 0; i < c->B; ++i)
+    for (int d = 0; d < 3; ++d) outBx3[3 * i + d] = rec[6 * i + 3 + d];
+  return SVNICP_OK;
+}
+
+int svnicp_get_gicp_stats(svnicp_ctx* c, double* outPx2, int64_t passes2[2]) {
+  CTX_CHECK(c);
+  if (passes2) { passes2[0] = c->pl.passes; passes2[1] = c->gi.passes; }
+  if (!outPx2) return SVNICP_OK;
+  if (!c->run.have_result || !c->gi.on) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_gicp_stats: no registration with the generalized-ICP residual yet");
   return fetch(c, outPx2, c->pl.stats.p, (size_t)c->P * 16);
 }
 

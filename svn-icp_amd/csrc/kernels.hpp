@@ -276,6 +276,25 @@ hipError_t launch_pack_normals(const double* tgt, const double* nrm, int64_t M, 
 hipError_t launch_plane_accumulate(const AccumPlan& plan, PlaneArgs a, hipStream_t st);
 hipError_t launch_plane_finalize(const double* partial, int nblk, int Ppad, int p_lo, int n_particles, double* Hb, double* stats,
                                  const int* ctl, hipStream_t st);
+// ---------------- generalized-ICP residual (gicp_icp.hip) ----------------
+// the accumulate kernel only: its records have plane mode's layout (kPlaneSums) and go through launch_plane_finalize; the
+// source's record [B][6] is made by launch_target_normals / launch_pack_normals with the source as the cloud
+struct GicpArgs {
+  const double* srec;   // [B][6] source xyz | unit normal (0 = no normal here)
+  const double* rec;    // [M][6] target xyz | unit normal (0 = no normal here)
+  const double* Rtot;   // [P][12]
+  int64_t B, M;
+  int p_lo, p_hi;
+  int Ppad;             // set by the launcher from the plan, like pts_per_block
+  int pts_per_block;
+  double max_dist, delta, eps;
+  double* partial;      // [plan.grid_x][Ppad][kPlaneSums]
+  const int* ctl;       // ctl[0] = stop flag
+  const int32_t* kidx;  // [B][Ppad] the search kernel's winner (target index)
+  const uint8_t* kbest; // [B][Ppad] … and its slot among the K candidates (read for the trace only)
+  int32_t* corr;        // optional trace [P][B] (this iteration), or nullptr
+};
+hipError_t launch_gicp_accumulate(const AccumPlan& plan, GicpArgs a, hipStream_t st);
 // ---------------- evaluate a registration (evaluate.hip) ----------------
 constexpr int kEvalRecord = 5;   // per workgroup: evaluated, inliers, plane inliers (counts, exact in float64), sum d2, sum r2
 constexpr int kEvalResult = 8;   // the record's five totals | fitness, inlier rmse, plane rmse

@@ -16,6 +16,8 @@
 #pragma once
 #include "kernels.hpp"
 
+#define SVNICP_CONST_AS __attribute__((address_space(4)))   // read-only for the launch: wave-uniform addresses become s_load
+
 namespace svnicp {
 namespace {
 

@@ -19,8 +19,6 @@ namespace svnicp {
 
 namespace {
 
-#define SVNICP_CONST_AS __attribute__((address_space(4)))   // read-only for the launch: wave-uniform addresses become s_load
-
 // ---------------------------------------------------------------------------------------------
 // normals
 // ---------------------------------------------------------------------------------------------

@@ -55,6 +55,8 @@ struct RegistrationFacts {
   bool plane = false;                  // svnicp_set_residual: point-to-plane
   bool normals_supplied = false;
   int normal_k = 16;
+  bool gicp = false;                   // svnicp_set_residual_gicp: generalized ICP (then `plane` is set too: it runs the plane residual's launch shape)
+  bool source_normals_supplied = false;
   int weighting = 0;                   // svnicp_set_particle_weighting: SVNICP_WEIGHT_* (0 = uniform, the reference)
   bool prior = false;                  // svnicp_set_pose_prior: a Gaussian prior on the correction is added in front of the Stein step
   int nshard() const { return p_hi - p_lo; }
@@ -85,6 +87,7 @@ inline const char* first_refusal(std::initializer_list<Refusal> ladder) {
 }
 constexpr const char* kMinibatchRefusal = "svnicp_align: mini-batch mode (svnicp_set_minibatch) is not available here: ";
 constexpr const char* kPlaneRefusal = "svnicp_align: the point-to-plane residual (svnicp_set_residual) is not available here: ";
+constexpr const char* kGicpRefusal = "svnicp_align: the generalized-ICP residual (svnicp_set_residual_gicp) is not available here: ";
 constexpr const char* kWeightingRefusal = "svnicp_align: particle weighting (svnicp_set_particle_weighting) is not available here: ";
 constexpr const char* kPriorRefusal = "svnicp_align: the pose prior (svnicp_set_pose_prior) is not available here: ";
 constexpr const char* kScoringRefusal = "svnicp_score_particles: the last registration cannot be scored: ";
@@ -121,6 +124,17 @@ inline const char* plane_refusal(const RegistrationFacts& f, const Tuning& t) {
       {t.accum != 3, "option accum is not split: the plane kernel consumes the search kernel's winner index"},
       {f.K > 128, "knn_count exceeds 128: the plane kernel consumes the matrix-pipe search kernel's winner index"},
       {!f.normals_supplied && f.M < f.normal_k, "the target has fewer points than normal_k and no normals were supplied"},
+  });
+}
+// generalized-ICP residual: everything the plane residual is not combined with (its accumulate kernel has the plane
+// kernel's place and inputs), and a source too small for its own normal pass
+inline const char* gicp_refusal(const RegistrationFacts& f, const Tuning& t) {
+  if (!f.gicp) return nullptr;
+  RegistrationFacts as_plane = f;
+  as_plane.plane = true;
+  if (const char* why = plane_refusal(as_plane, t)) return why;
+  return first_refusal({
+      {!f.source_normals_supplied && f.B < f.normal_k, "the source has fewer points than normal_k and no source normals were supplied"},
   });
 }
 // scoring the particles through the registration's candidate table (svnicp_score_particles): what the registration must

@@ -13,7 +13,6 @@ namespace svnicp {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-#define SVNICP_CONST_AS __attribute__((address_space(4)))   // read-only for the launch: wave-uniform addresses become s_load
 
 __device__ __forceinline__ float pack_slot(float v, unsigned int mask, unsigned int bits) {
   return __uint_as_float((__float_as_uint(v) & ~mask) | bits);

@@ -6,6 +6,7 @@
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
 //      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
 //      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2;
+//      map_normals 2: the generalized-ICP residual, the target's normals from the map as with 1, the source's from the solver's pass;
 //      eval_dist > 0: PipelineConfig::eval_dist, every registered scan is evaluated and one more line per scan is printed:
 //      "eval <scan>: fitness inlier_rmse plane_rmse plane_inliers" with %.17g, -1 where a figure does not exist;
 //      information point|plane: PipelineConfig::information (needs eval_dist > 0), one more line per registered scan:
@@ -49,7 +50,9 @@ int main(int argc, char** argv) {
   cfg.gpu_prep = argc > 8 && atoi(argv[8]) >= 2;
   cfg.deskew = argc > 9 && atoi(argv[9]) != 0;
   cfg.segmentation = argc > 10 && atoi(argv[10]) != 0;
-  cfg.plane = cfg.map_normals = argc > 11 && atoi(argv[11]) != 0;
+  cfg.map_normals = argc > 11 && atoi(argv[11]) != 0;
+  cfg.gicp = cfg.map_normals && atoi(argv[11]) == 2;
+  cfg.plane = cfg.map_normals && !cfg.gicp;
   cfg.eval_dist = argc > 12 ? atof(argv[12]) : 0.0;
   if (argc > 13) cfg.information = argv[13];
   if (argc > 16 && std::string(argv[14]) != "off") {

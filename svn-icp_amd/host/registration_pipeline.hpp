@@ -987,7 +987,10 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   bool plane = false;          // the Huber-weighted point-to-plane residual (svnicp_set_residual; not in the reference)
   double huber_delta = 0.1;    // with plane: weight 1 up to this |r|, huber_delta / |r| beyond
   int normal_k = 16;           // with plane: neighbours a target normal is estimated from (4..64)
-  bool map_normals = false;    // with plane and gpu_map: the target's normals come from the map's own voxels
+  bool gicp = false;           // the generalized-ICP residual (svnicp_set_residual_gicp; not in the reference): huber_delta and normal_k as
+                               // with plane; the source's normals come from the solver's own pass over the source
+  double gicp_epsilon = 1e-3;  // with gicp: a surface's covariance along its normal, in units of the in-plane one ([1e-6, 1])
+  bool map_normals = false;    // with plane or gicp, and gpu_map: the target's normals come from the map's own voxels
                                // (DeviceVoxelMap::QueryNormals) instead of the solver's pass over the target
   double eval_dist = 0.0;      // > 0: every registered scan is evaluated at its result pose with this inlier gate
                                // (svnicp_evaluate) before the map update; 0 = off, no call is made
@@ -1091,7 +1094,8 @@ class RegistrationPipeline {
       if (!(std::isfinite(cfg.prior_point_sigma) && cfg.prior_point_sigma > 0)) throw std::invalid_argument("PipelineConfig: prior_point_sigma must be finite and > 0 (m)");
     }
     if (cfg.map_normals && !cfg.gpu_map) throw std::invalid_argument("PipelineConfig: map_normals needs gpu_map (the normals are computed from the device map)");
-    if (cfg.map_normals && !cfg.plane) throw std::invalid_argument("PipelineConfig: map_normals needs plane (point mode uses no normals)");
+    if (cfg.plane && cfg.gicp) throw std::invalid_argument("PipelineConfig: plane and gicp are two residuals, choose one");
+    if (cfg.map_normals && !cfg.plane && !cfg.gicp) throw std::invalid_argument("PipelineConfig: map_normals needs plane or gicp (point mode uses no normals)");
     const bool mode_link = !(cfg.mode_link_trans < 0 && cfg.mode_link_rot < 0);
     if (mode_link && !(std::isfinite(cfg.mode_link_trans) && cfg.mode_link_trans >= 0 && std::isfinite(cfg.mode_link_rot) && cfg.mode_link_rot >= 0))
       throw std::invalid_argument("PipelineConfig: mode_link must be (link_trans, link_rot), both finite and >= 0");
@@ -1125,6 +1129,7 @@ class RegistrationPipeline {
       VoxelHashMap(1.0, 1.0, 1).ClearSeenThrough(Cloud{}, Pose3{}, cfg.seg_params, clear_opt_);   // validates sensor and options (throws)
     }
     if (cfg.plane) { cfg_.solver.residual = "plane"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; }
+    if (cfg.gicp) { cfg_.solver.residual = "gicp"; cfg_.solver.huber_delta = cfg.huber_delta; cfg_.solver.normal_k = cfg.normal_k; cfg_.solver.gicp_epsilon = cfg.gicp_epsilon; }
     if (cfg.gpu_map) dmap_ = std::make_unique<DeviceVoxelMap>(cfg.map_voxel_size, cfg.map_range, cfg.map_voxel_max_points, cfg.device);
     if (cfg.gpu_map && cfg.gpu_prep) dprep_ = std::make_unique<DevicePrep>(cfg.device);
   }

@@ -31,9 +31,10 @@ struct SteinICPParam {  // SVGDICP.h:41-57 (same names and defaults; solver-rele
   double convergence_threshold = 1e-5;
   int KNN_count = 100;
   bool SVN_full_grad = true;
-  std::string residual = "point";   // "point" (the reference) | "plane": Huber-weighted point-to-plane (svnicp_hip.h, not in the reference)
+  std::string residual = "point";   // "point" (the reference) | "plane": Huber-weighted point-to-plane | "gicp": generalized ICP (svnicp_hip.h, neither in the reference)
   double huber_delta = 0.1;         // plane residual: weight 1 up to this |r|, huber_delta / |r| beyond
   int normal_k = 16;                // plane residual: neighbours a target normal is estimated from (4..64)
+  double gicp_epsilon = 1e-3;       // gicp residual: a surface's covariance along its normal, in units of the in-plane one ([1e-6, 1])
 };
 
 // SVNICP.h:25-27.  use_weight_mean alone is as inert as in the reference (particle_weight_ stays ones / P); with weight_dist > 0
@@ -56,7 +57,7 @@ class SVGDICP {
                 : p.optimizer == "SGD" ? SVNICP_OPT_SGD : p.optimizer == "Adagrad" ? SVNICP_OPT_ADAGRAD : SVNICP_OPT_NONE;
     if (svnicp_create(&q, device, init_pose.data(), P_, &h_) != 0) throw std::runtime_error(svnicp_last_error(nullptr));
     if (p.use_minibatch) { batch_ = p.batch_size; chk(svnicp_set_minibatch(h_, p.batch_size, p.minibatch_seed)); }
-    if (p.residual != "point") set_residual(p.residual, p.huber_delta, p.normal_k);
+    if (p.residual != "point") set_residual(p.residual, p.huber_delta, p.normal_k, p.gicp_epsilon);
   }
   virtual ~SVGDICP() { svnicp_destroy(h_); }
   SVGDICP(const SVGDICP&) = delete;
@@ -120,8 +121,9 @@ class SVGDICP {
   }
   std::array<int64_t, 2> get_minibatch_rows() { std::array<int64_t, 2> o{}; chk(svnicp_get_minibatch_rows(h_, o.data())); return o; }
   // point-to-plane residual (svnicp_hip.h "point-to-plane residual")
-  void set_residual(const std::string& residual, double huber_delta = 0.1, int normal_k = 16) {
-    if (residual != "point" && residual != "plane") throw std::runtime_error("set_residual: \"point\" or \"plane\"");
+  void set_residual(const std::string& residual, double huber_delta = 0.1, int normal_k = 16, double gicp_epsilon = 1e-3) {
+    if (residual == "gicp") { chk(svnicp_set_residual_gicp(h_, huber_delta, normal_k, gicp_epsilon)); return; }   // svnicp_hip.h "generalized-ICP residual"
+    if (residual != "point" && residual != "plane") throw std::runtime_error("set_residual: \"point\", \"plane\" or \"gicp\"");
     chk(svnicp_set_residual(h_, residual == "plane" ? SVNICP_RESIDUAL_PLANE : SVNICP_RESIDUAL_POINT, huber_delta, normal_k));
   }
   // normals of the current target, [M][3] in host memory; call after add_cloud
@@ -133,6 +135,15 @@ class SVGDICP {
   std::vector<double> get_plane_stats(int64_t* normal_passes = nullptr) {
     std::vector<double> o((size_t)2 * P_);
     chk(svnicp_get_plane_stats(h_, o.data(), normal_passes));
+    return o;
+  }
+  // generalized-ICP residual: normals of the current source, [B][3] in host memory; call after add_cloud
+  void set_source_normals(const double* n_xyz, int64_t B) { chk(svnicp_set_source_normals(h_, n_xyz, B, SVNICP_MEM_HOST)); }
+  std::vector<double> get_source_normals(int64_t B) { std::vector<double> o((size_t)B * 3); chk(svnicp_get_source_normals(h_, o.data())); return o; }
+  // {accepted pairs, sum w rho^2} per particle of the last iteration run; passes2 = {target, source} normal passes run so far
+  std::vector<double> get_gicp_stats(int64_t* passes2 = nullptr) {
+    std::vector<double> o((size_t)2 * P_);
+    chk(svnicp_get_gicp_stats(h_, o.data(), passes2));
     return o;
   }
   // Gaussian pose prior on the correction (svnicp_hip.h "pose prior"): mean6 = [t ; rotation vector], info36 = Lambda row-major

@@ -1410,7 +1410,7 @@ class PipelineConfig:
     info_huber: float = float("inf")   # with information: its Huber delta (+inf = unweighted)
     weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
     weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
-    map_normals: bool = False      # with gpu_map and solver.residual == "plane": the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
+    map_normals: bool = False      # with gpu_map and solver.residual == "plane" or "gicp" (whose source normals stay the solver's own pass): the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
     mode_link: tuple | None = None  # (link_trans m, link_rot rad): after every registration the particles are grouped into modes (svnicp_particle_modes) in ScanResult.modes; None = off, no call is made
     mode_max: int = 8              # with mode_link: modes reported in full (1..32)
     mode_select: str = "mean"      # "heaviest": the correction is the first mode's mean instead of the global mean, and the pose, the evaluate, the information and the map update follow it; needs mode_link
@@ -1499,8 +1499,8 @@ class PipelineConfig:
                 raise ValueError("PipelineConfig: prior_point_sigma must be finite and > 0 (m)")
         if self.map_normals and not self.gpu_map:
             raise ValueError("PipelineConfig: map_normals needs gpu_map=True (the normals are computed from the device map)")
-        if self.map_normals and self.solver.residual != "plane":
-            raise ValueError('PipelineConfig: map_normals needs solver.residual == "plane" (point mode uses no normals)')
+        if self.map_normals and self.solver.residual not in ("plane", "gicp"):
+            raise ValueError('PipelineConfig: map_normals needs solver.residual == "plane" or "gicp" (point mode uses no normals)')
 
 
 @dataclass

@@ -53,9 +53,10 @@ class SteinICPParam:  # include/core/SVGDICP.h:41-57 (same field names and defau
     SVN_full_grad: bool = True
     record_trace: bool = False       # test hook (not in the reference)
     minibatch_seed: int = 0          # seed of the generated mini-batch tables (not in the reference: see minibatch_indices)
-    residual: str = "point"          # "point" (the reference) | "plane": Huber-weighted point-to-plane (not in the reference)
+    residual: str = "point"          # "point" (the reference) | "plane": Huber-weighted point-to-plane | "gicp": generalized ICP (neither in the reference)
     huber_delta: float = 0.1         # plane residual: weight 1 up to this |r|, huber_delta / |r| beyond (inf = unweighted)
     normal_k: int = 16               # plane residual: neighbours of a target point its normal is estimated from (4..64)
+    gicp_epsilon: float = 1e-3       # gicp residual: a surface's covariance along its normal, in units of the in-plane one ([1e-6, 1])
 
 
 @dataclass
@@ -264,7 +265,7 @@ class _SolverBase:
         if parameters.use_minibatch:
             self.set_minibatch(int(parameters.batch_size), int(parameters.minibatch_seed))
         if parameters.residual != "point":
-            self.set_residual(parameters.residual, float(parameters.huber_delta), int(parameters.normal_k))
+            self.set_residual(parameters.residual, float(parameters.huber_delta), int(parameters.normal_k), float(parameters.gicp_epsilon))
         w = self.weight_config
         if self._mode == 0 and w.use_weight_mean and w.weight_dist > 0:   # the option belongs to SVNICP's constructor only
             self.set_particle_weighting("softmin", float(w.weight_dist), float(w.temperature))
@@ -439,10 +440,15 @@ class _SolverBase:
     # -- point-to-plane residual (include/svnicp_hip.h "point-to-plane residual") ---------------------------------------------
     _RESIDUAL = {"point": 0, "plane": 1}
 
-    def set_residual(self, residual: str = "plane", huber_delta: float = 0.1, normal_k: int = 16) -> None:
-        """"point" (the reference's residual) or "plane" (Huber-weighted point-to-plane) from the next registration on."""
+    def set_residual(self, residual: str = "plane", huber_delta: float = 0.1, normal_k: int = 16, gicp_epsilon: float = 1e-3) -> None:
+        """"point" (the reference's residual), "plane" (Huber-weighted point-to-plane) or "gicp" (generalized ICP: both
+        clouds' normals weigh every pair; ``gicp_epsilon`` is read in that mode only) from the next registration on."""
+        if residual == "gicp":
+            self._check(self._L.svnicp_set_residual_gicp(self._h, float(huber_delta), int(normal_k), float(gicp_epsilon)),
+                        "svnicp_set_residual_gicp")
+            return
         if residual not in self._RESIDUAL:
-            raise ValueError('residual must be "point" or "plane"')
+            raise ValueError('residual must be "point", "plane" or "gicp"')
         self._check(self._L.svnicp_set_residual(self._h, self._RESIDUAL[residual], float(huber_delta), int(normal_k)),
                     "svnicp_set_residual")
 
@@ -486,6 +492,41 @@ class _SolverBase:
         self._check(self._L.svnicp_get_plane_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_double)) if with_sums else None,
                                                    C.byref(n)), "svnicp_get_plane_stats")
         return out, int(n.value)
+
+    # -- generalized-ICP residual (include/svnicp_hip.h "generalized-ICP residual") ---------------------------------------------
+    def set_source_normals(self, normals) -> None:
+        """Normals of the current source, [B, 3] (numpy, or a float64 CUDA torch tensor); call after ``add_cloud``.  The
+        rules of ``set_target_normals``; read by the "gicp" residual only."""
+        if _is_torch_cuda(normals):
+            import torch
+            n = normals.to(torch.float64).contiguous()
+            if n.dim() != 2 or n.shape[1] != 3:
+                raise ValueError("normals must be [B, 3]")
+            torch.cuda.current_stream(n.device).synchronize()
+            self._keep_source_normals = n
+            ptr, B, kind = C.c_void_p(n.data_ptr()), int(n.shape[0]), 1
+        else:
+            n = np.ascontiguousarray(np.asarray(normals, np.float64))
+            if n.ndim != 2 or n.shape[1] != 3:
+                raise ValueError("normals must be [B, 3]")
+            ptr, B, kind = n.ctypes.data_as(C.c_void_p), int(n.shape[0]), 0
+        self._check(self._L.svnicp_set_source_normals(self._h, ptr, B, kind), "svnicp_set_source_normals")
+
+    def get_source_normals(self) -> np.ndarray:
+        """The supplied or estimated unit normals of the source, [B, 3]; rows without a normal are 0."""
+        out = np.zeros((self._B, 3), np.float64)
+        self._check(self._L.svnicp_get_source_normals(self._h, out.ctypes.data_as(C.POINTER(C.c_double))),
+                    "svnicp_get_source_normals")
+        return out
+
+    def get_gicp_stats(self, with_sums: bool = True) -> tuple:
+        """(per particle [P, 2] = {accepted pairs, sum w rho^2} of the last iteration run, (target, source) normal passes run
+        so far); ``with_sums=False`` returns (None, passes) and needs no registration."""
+        out = np.zeros((self._P, 2), np.float64) if with_sums else None
+        n = (C.c_int64 * 2)(0, 0)
+        self._check(self._L.svnicp_get_gicp_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_double)) if with_sums else None, n),
+                    "svnicp_get_gicp_stats")
+        return out, (int(n[0]), int(n[1]))
 
     # -- Gaussian pose prior on the correction (include/svnicp_hip.h "pose prior") ---------------------------------------------
     def set_pose_prior(self, mean6=None, information=None) -> None:
