@@ -247,7 +247,8 @@ int svnicp_get_plane_stats(svnicp_ctx *ctx, double *outPx2, int64_t *normal_pass
  * The mode is entered only here (svnicp_set_residual(2, ...) stays SVNICP_ERR_INVALID) and left by svnicp_set_residual(POINT |
  * PLANE, ...).  It runs the plane residual's launches with its own accumulate kernel, so the Stein step, the pose prior, early
  * stop, history, traces, svnicp_evaluate, svnicp_eval_information (forms point and plane), svnicp_score_particles and
- * svnicp_particle_modes behave as on a plane-mode context; svnicp_plane_record_devptr / svnicp_plane_stats_devptr tap its
+ * svnicp_particle_modes behave as on a plane-mode context (the information matrix of THIS objective is
+ * svnicp_eval_information_gicp); svnicp_plane_record_devptr / svnicp_plane_stats_devptr tap its
  * records ([P][2] = {accepted pairs, sum w rho^2}).
  * Refused by svnicp_align / svnicp_align_begin with SVNICP_ERR_INVALID: everything plane mode refuses, and a source of fewer
  * than normal_k points without supplied source normals. */
@@ -380,16 +381,43 @@ int svnicp_get_eval_pairs(svnicp_ctx *ctx, int32_t *idxB, double *d2B);   /* hos
  *   rank         the number of eigval[i] > f * eigval[5].
  *   H+, step     H+ = sum over the `rank` largest of v v^T / lambda;  step = -H+ b (the Gauss-Newton step in the tangent
  *                above: a stationary result has |step| near 0);  no component along a direction below the floor.
- *   sigma2, cov  dof = dim * pairs - rank with dim = 3 (point) or 1 (plane);  sigma2 = sum_wr2 / dof if dof > 0 else 0;
+ *   sigma2, cov  dof = dim * pairs - rank with dim = 3 (point, GICP) or 1 (plane);  sigma2 = sum_wr2 / dof if dof > 0 else 0;
  *                cov = sigma2 * H+: the Gauss-Newton covariance of the pose AT this one pose, in the tangent above -- not
  *                svnicp_get_cov_matrix, which is the particle spread in correction coordinates.
  *   edge cases   a zero H gives rank 0, zero eigenvalues, step, sigma2 and cov (the eigenvectors are the unit axes) and no
- *                NaN.  A non-finite entry of H or b (or sum_wr2), a form, floor or struct_size as above: SVNICP_ERR_INVALID. */
+ *                NaN.  A non-finite entry of H or b (or sum_wr2), a form, floor or struct_size as above: SVNICP_ERR_INVALID.
+ *                Forms 0, 1 and 3 are known (2 is not a form).
+ *
+ * svnicp_eval_information_gicp(ctx, huber_delta, epsilon, eig_floor_ratio, out): the same in the generalized-ICP objective of
+ * svnicp_set_residual_gicp, sum Huber(sqrt(u^T W u)) -- what a filter or a degeneracy gate must be handed after a registration
+ * in that mode.  A function of its own because the form has one more argument;
+ * svnicp_eval_information(ctx, 3, ...) stays refused as an unknown form.  Everything said above holds (tangent, both,
+ * determinism, side effects, sharded, the solve), and:
+ *   rows         those of the LAST svnicp_evaluate, as above: its pose, gate, nearest target index, d2 and q.  No second
+ *                search and no normal pass.  A row contributes iff it is one of evaluate's plane inliers (an inlier whose
+ *                target normal n_q is non-zero) and the context holds a normal n_s for the source row: a row of the packed
+ *                source record that is not all zero, the rule of the mode's accumulate kernel.
+ *   GICP form    e = q - p, u = R^T e, m = R^T n_q, G = [I3 | -hat(s)], C(x) = I - (1 - epsilon) x x^T;
+ *   (form 3)     W = 2 epsilon (C(m) + C(n_s))^-1   (closed-form inverse in float64, cond <= 1 / epsilon);
+ *                rho = sqrt(max(u^T W u, 0)),  w = 1 if rho <= delta else delta / rho;
+ *                H += w G^T W G;  b += w G^T W u;  sum_w += w;  sum_wr2 += w rho^2;  pairs += 1.
+ *                W is frozen at the evaluated pose, as in the solver, so b is the exact gradient of sum Huber(rho) with W
+ *                held fixed, and step is near 0 at a converged registration of that mode.  H is the clean normal matrix.
+ *                epsilon = 1 gives the point form's H and b on these rows; parallel normals (n_s = m) and delta = +inf give
+ *                (1 - epsilon) of the plane form's H plus epsilon of the point form's.
+ *   epsilon      0 = 1e-3, else in [1e-6, 1] (svnicp_set_residual_gicp's rule).  The caller's choice, independent of the
+ *                residual the solver ran and of its epsilon, as the form is.
+ *   when         as svnicp_eval_information, and also refused with SVNICP_ERR_INVALID: epsilon out of range; a last
+ *                svnicp_evaluate with has_normals = 0; a context without normals of the current source (they come from
+ *                svnicp_set_source_normals, or from a registration in generalized-ICP mode that estimated them, and are
+ *                dropped with the source).
+ *   result       form = SVNICP_INFO_GICP; the struct and every other field as above, dim = 3 in the solve. */
 #define SVNICP_INFO_POINT 0
 #define SVNICP_INFO_PLANE 1
+#define SVNICP_INFO_GICP 3
 typedef struct svnicp_information {
   int32_t struct_size;     /* in: sizeof(svnicp_information) */
-  int32_t form;            /* SVNICP_INFO_POINT | SVNICP_INFO_PLANE */
+  int32_t form;            /* SVNICP_INFO_POINT | SVNICP_INFO_PLANE | SVNICP_INFO_GICP */
   int64_t pairs;           /* contributing rows, exact */
   int32_t rank;            /* eigenvalues above the floor */
   int32_t reserved;
@@ -404,6 +432,7 @@ typedef struct svnicp_information {
   double R[9], t[3];       /* the evaluated pose (row-major) */
 } svnicp_information;
 int svnicp_eval_information(svnicp_ctx *ctx, int form, double huber_delta, double eig_floor_ratio, svnicp_information *out);
+int svnicp_eval_information_gicp(svnicp_ctx *ctx, double huber_delta, double epsilon, double eig_floor_ratio, svnicp_information *out);
 int svnicp_information_solve(svnicp_information *io);   /* host only: no context, no device */
 
 /* ---- score and weight the particles (an extension: the reference declares ParticleWeightOpt::use_weight_mean,

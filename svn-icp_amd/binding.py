@@ -62,6 +62,7 @@ class InformationStruct(C.Structure):
 
 
 INFO_POINT, INFO_PLANE = 0, 1   # SVNICP_INFO_POINT, SVNICP_INFO_PLANE
+INFO_GICP = 3                   # SVNICP_INFO_GICP (2 is not a form)
 MODES_MAX = 32                  # SVNICP_MODES_MAX
 
 
@@ -258,6 +259,7 @@ def load_library():
         getattr(L, name).restype = vp
     L.svnicp_get_eval_pairs.argtypes = [vp, ip, dp]
     L.svnicp_eval_information.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(InformationStruct)]
+    L.svnicp_eval_information_gicp.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.POINTER(InformationStruct)]
     L.svnicp_information_solve.argtypes = [C.POINTER(InformationStruct)]
     L.svnicp_score_particles.argtypes = [vp, C.c_double, dp, dp]
     L.svnicp_set_particle_weighting.argtypes = [vp, C.c_int, C.c_double, C.c_double]

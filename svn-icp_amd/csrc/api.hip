@@ -1568,19 +1568,25 @@ int svnicp_get_eval_pairs(svnicp_ctx* c, int32_t* idxB, double* d2B) {
 // ---- information matrix of a registration ----
 int svnicp_information_solve(svnicp_information* io) { return svnicp_info::solve(io, nullptr); }
 
-int svnicp_eval_information(svnicp_ctx* c, int form, double huber_delta, double eig_floor_ratio, svnicp_information* out) {
-  CTX_CHECK(c);
-  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: null result struct");
-  if (out->struct_size != (int32_t)sizeof(svnicp_information)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: svnicp_information.struct_size mismatch");
-  if (form != SVNICP_INFO_POINT && form != SVNICP_INFO_PLANE) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: unknown form (SVNICP_INFO_POINT or SVNICP_INFO_PLANE)");
-  if (!(huber_delta > 0.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: huber_delta must be positive and not NaN (+inf: unweighted)");
-  if (!(eig_floor_ratio >= 0.0 && eig_floor_ratio < 1.0)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: eig_floor_ratio must lie in [0, 1) (0: the default, 1e-12)");
+// What the two entry points share once the form is known: the remaining argument checks, the freshness of the last evaluate,
+// the two launches, the copy and the host solve.  fn names the entry point in every refusal; eps is read by the GICP form only.
+static int information_of_last_evaluate(svnicp_ctx* c, const char* fn, int form, double huber_delta, double eps, double eig_floor_ratio,
+                                        svnicp_information* out) {
+  const std::string who = std::string(fn) + ": ";
+  if (!(huber_delta > 0.0)) return fail(c, SVNICP_ERR_INVALID, who + "huber_delta must be positive and not NaN (+inf: unweighted)");
+  if (!(eig_floor_ratio >= 0.0 && eig_floor_ratio < 1.0)) return fail(c, SVNICP_ERR_INVALID, who + "eig_floor_ratio must lie in [0, 1) (0: the default, 1e-12)");
   EvalState& ev = c->ev;
   if (!ev.fresh || !ev.have || ev.rows != c->B)
-    return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_eval_information: ") + ev.stale + ": call svnicp_evaluate first (the sums run over its rows; it "
+    return fail(c, SVNICP_ERR_INVALID, who + ev.stale + ": call svnicp_evaluate first (the sums run over its rows; it "
                                        "must have succeeded since the source, the target or the target normals last changed and since the last registration began)");
   if (form == SVNICP_INFO_PLANE && !ev.normals)
-    return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: the plane form needs target normals, and the last svnicp_evaluate had has_normals = 0");
+    return fail(c, SVNICP_ERR_INVALID, who + "the plane form needs target normals, and the last svnicp_evaluate had has_normals = 0");
+  const bool gicp = form == SVNICP_INFO_GICP;
+  if (gicp && !ev.normals)
+    return fail(c, SVNICP_ERR_INVALID, who + "the GICP form needs target normals, and the last svnicp_evaluate had has_normals = 0");
+  if (gicp && !c->gi.supplied && !c->gi.estimated)
+    return fail(c, SVNICP_ERR_INVALID, who + "the context holds no normals of the current source (svnicp_set_source_normals, or a registration in "
+                                             "generalized-ICP mode that estimated them)");
   if (bind(c)) return SVNICP_ERR_HIP;
   const int64_t B = c->B, nblk = evaluate_blocks(B);
   HIPCHK(c, ev.info_partial.ensure((size_t)nblk * kInfoPlaneRecord)); HIPCHK(c, ev.info_result.ensure(kInfoResult));
@@ -1588,7 +1594,8 @@ int svnicp_eval_information(svnicp_ctx* c, int form, double huber_delta, double 
   InfoArgs a{};
   a.src = c->cloud.src.p; a.q = ev.q.p; a.tgt = c->cloud.tgt.p; a.rec = ev.normals ? c->pl.rec.p : nullptr; a.idx = ev.idx.p; a.d2 = ev.d2.p;
   a.B = B; a.M = c->M; a.thr2 = ev.max_corr_dist * ev.max_corr_dist; a.delta = huber_delta; a.T = ev.T; a.partial = ev.info_partial.p;
-  HIPCHK(c, launch_information(form, a, ev.info_result.p, c->stream));
+  a.srec = gicp ? c->gi.rec.p : nullptr; a.eps = eps;
+  HIPCHK(c, launch_information(gicp ? 2 : form, a, ev.info_result.p, c->stream));
   HIPCHK(c, hipMemcpyAsync(ev.h_info.p, ev.info_result.p, kInfoResult * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const double* r = ev.h_info.p;
@@ -1599,9 +1606,28 @@ int svnicp_eval_information(svnicp_ctx* c, int form, double huber_delta, double 
   o.pairs = (int64_t)r[42]; o.sum_w = r[43]; o.sum_wr2 = r[44];
   std::memcpy(o.R, ev.T.R, sizeof o.R); std::memcpy(o.t, ev.T.t, sizeof o.t);
   const char* why = nullptr;
-  if (const int rc = svnicp_info::solve(&o, &why)) return fail(c, rc, std::string("svnicp_eval_information: ") + (why ? why : "svnicp_information_solve failed"));
+  if (const int rc = svnicp_info::solve(&o, &why)) return fail(c, rc, who + (why ? why : "svnicp_information_solve failed"));
   *out = o;
   return SVNICP_OK;
+}
+
+int svnicp_eval_information(svnicp_ctx* c, int form, double huber_delta, double eig_floor_ratio, svnicp_information* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: null result struct");
+  if (out->struct_size != (int32_t)sizeof(svnicp_information)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: svnicp_information.struct_size mismatch");
+  if (form != SVNICP_INFO_POINT && form != SVNICP_INFO_PLANE)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information: unknown form (SVNICP_INFO_POINT or SVNICP_INFO_PLANE; the GICP form is svnicp_eval_information_gicp)");
+  return information_of_last_evaluate(c, "svnicp_eval_information", form, huber_delta, 0.0, eig_floor_ratio, out);
+}
+
+int svnicp_eval_information_gicp(svnicp_ctx* c, double huber_delta, double epsilon, double eig_floor_ratio, svnicp_information* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information_gicp: null result struct");
+  if (out->struct_size != (int32_t)sizeof(svnicp_information)) return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information_gicp: svnicp_information.struct_size mismatch");
+  if (epsilon != 0.0 && !(epsilon >= kGicpEpsilonMin && epsilon <= 1.0))   // svnicp_set_residual_gicp's rule
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_eval_information_gicp: epsilon must be 0 (= 1e-3) or in [1e-6, 1]");
+  return information_of_last_evaluate(c, "svnicp_eval_information_gicp", SVNICP_INFO_GICP, huber_delta, epsilon != 0.0 ? epsilon : kGicpEpsilonDefault,
+                                      eig_floor_ratio, out);
 }
 
 // ---- score and weight the particles ----

@@ -1,5 +1,6 @@
 // gicp_pair_device.hpp — one pair of the generalized-ICP residual: the combined weight of the two surfaces
-// and the pair's terms of H, b and the statistics.  Stated once for k_gicp_accumulate (gicp_icp.hip).
+// and the pair's terms of H, b and the statistics.  Stated once for k_gicp_accumulate (gicp_icp.hip) and for the GICP form
+// of the information matrix (information.hip).
 //
 // In the source frame, with m = Rtᵀ n_q (the winner's unit normal), n the source point's unit normal, u = Rtᵀ (Ts − q):
 //   C(x) = I − (1 − ε) x xᵀ          regularised surface covariance: ε along the normal, 1 in the plane
@@ -38,10 +39,11 @@ SVNICP_GICP_FN void gicp_weight(double m0, double m1, double m2, double n0, doub
   W[0] = k * c00; W[1] = k * c01; W[2] = k * c02; W[3] = k * c11; W[4] = k * c12; W[5] = k * c22;
 }
 
-// One pair into the 29 sums.  s: the source point, u = Rtᵀ e, m = Rtᵀ n_q, n: the source normal.  ok == false: every operand
-// is selected to zero first (never multiplied: a non-finite point must not leak a NaN), so the pair adds exact zeros.
-SVNICP_GICP_FN void gicp_accumulate_pair(double (&acc)[kGicpSums], bool ok, double s0, double s1, double s2, double u0, double u1, double u2,
-                                         double m0, double m1, double m2, double n0, double n1, double n2, double eps, double delta) {
+// One pair into the 29 sums; returns the pair's Huber weight w (0 for a rejected pair).  s: the source point, u = Rtᵀ e,
+// m = Rtᵀ n_q, n: the source normal.  ok == false: every operand is selected to zero first (never multiplied: a non-finite point
+// must not leak a NaN), so the pair adds exact zeros.
+SVNICP_GICP_FN double gicp_pair_sums(double (&acc)[kGicpSums], bool ok, double s0, double s1, double s2, double u0, double u1, double u2,
+                                     double m0, double m1, double m2, double n0, double n1, double n2, double eps, double delta) {
   s0 = ok ? s0 : 0.0; s1 = ok ? s1 : 0.0; s2 = ok ? s2 : 0.0;
   u0 = ok ? u0 : 0.0; u1 = ok ? u1 : 0.0; u2 = ok ? u2 : 0.0;
   m0 = ok ? m0 : 0.0; m1 = ok ? m1 : 0.0; m2 = ok ? m2 : 0.0;
@@ -76,6 +78,45 @@ SVNICP_GICP_FN void gicp_accumulate_pair(double (&acc)[kGicpSums], bool ok, doub
   acc[24] += s1 * b2 - s2 * b1; acc[25] += s2 * b0 - s0 * b2; acc[26] += s0 * b1 - s1 * b0;
   acc[27] += ok ? 1.0 : 0.0;
   acc[28] += w * rho2;
+  return w;
+}
+
+// k_gicp_accumulate's pair: the sums alone.
+SVNICP_GICP_FN void gicp_accumulate_pair(double (&acc)[kGicpSums], bool ok, double s0, double s1, double s2, double u0, double u1, double u2,
+                                         double m0, double m1, double m2, double n0, double n1, double n2, double eps, double delta) {
+  (void)gicp_pair_sums(acc, ok, s0, s1, s2, u0, u1, u2, m0, m1, m2, n0, n1, n2, eps, delta);
+}
+
+// One row of svnicp_eval_information_gicp (information.hip) as the plane form's 30-value record:
+//   pairs, w, w ρ² | the 21 upper-triangle entries of w GᵀWG, row-major | the 6 of w GᵀWu
+// R: the evaluated pose's rotation, row-major; s: the source row; e = q − p; nq: the nearest target's normal; ns: the source
+// row's normal.  `on`: the row is one of evaluate's inliers.  It contributes iff both normals are non-zero, k_gicp_accumulate's
+// rule; otherwise every operand is selected to zero before any product and the record is exact zeros.  The pair's terms are
+// gicp_pair_sums' on sums that start at zero, so the algebra is stated once.
+constexpr int kGicpInfoRecord = 30;
+SVNICP_GICP_FN void gicp_information_row(double (&v)[kGicpInfoRecord], bool on, const double* R, double s0, double s1, double s2,
+                                         double e0, double e1, double e2, double nq0, double nq1, double nq2,
+                                         double ns0, double ns1, double ns2, double eps, double delta) {
+  const bool ok = on && (nq0 != 0.0 || nq1 != 0.0 || nq2 != 0.0) && (ns0 != 0.0 || ns1 != 0.0 || ns2 != 0.0);
+  const double g0 = ok ? e0 : 0.0, g1 = ok ? e1 : 0.0, g2 = ok ? e2 : 0.0;
+  const double h0 = ok ? nq0 : 0.0, h1 = ok ? nq1 : 0.0, h2 = ok ? nq2 : 0.0;
+  const double u0 = R[0] * g0 + R[3] * g1 + R[6] * g2;   // u = Rᵀ e
+  const double u1 = R[1] * g0 + R[4] * g1 + R[7] * g2;
+  const double u2 = R[2] * g0 + R[5] * g1 + R[8] * g2;
+  const double m0 = R[0] * h0 + R[3] * h1 + R[6] * h2;   // m = Rᵀ n_q
+  const double m1 = R[1] * h0 + R[4] * h1 + R[7] * h2;
+  const double m2 = R[2] * h0 + R[5] * h1 + R[8] * h2;
+  double t[kGicpSums];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int i = 0; i < kGicpSums; ++i) t[i] = 0.0;
+  const double w = gicp_pair_sums(t, ok, s0, s1, s2, u0, u1, u2, m0, m1, m2, ns0, ns1, ns2, eps, delta);
+  v[0] = t[27]; v[1] = w; v[2] = t[28];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 27; ++i) v[3 + i] = t[i];
 }
 
 }  // namespace svnicp

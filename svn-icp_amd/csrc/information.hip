@@ -1,15 +1,20 @@
 // information.hip — the device half of svnicp_eval_information (include/svnicp_hip.h "information matrix of a registration",
 // DESIGN.md §4.13): the Gauss-Newton normal equations H, b of the last svnicp_evaluate's pairs, right perturbation
 // T Exp([v ; omega]).  Two kernels, no search: every row's q, nearest target index and d2 are the ones evaluate left.
-//   k_information_pairs<form>     per row the terms of the form's sums, per workgroup ONE record
+//   k_information_pairs<form>     per row the terms of the form's sums, per workgroup ONE record (form 2: the GICP form of
+//                                 svnicp_eval_information_gicp, §4.13.1)
 //   k_information_finalize<form>  one workgroup adds the records in a fixed order and expands them to H[36] | b[6] | pairs,
 //                                 sum w, sum w r^2
 // No atomics: workgroup w owns rows [256 w, 256 w + 256) (evaluate's layout), every record is folded by fold_record
 // (lane_fold_device.hpp), so the order of every addition depends on B alone.
 #include "kernels.hpp"
 #include "lane_fold_device.hpp"
+#include "gicp_pair_device.hpp"
 
 namespace svnicp {
+
+static_assert(kGicpInfoRecord == kInfoPlaneRecord, "the GICP form is folded and finalized as the plane form's record");
+
 namespace {
 
 constexpr int NT = 256;
@@ -21,6 +26,9 @@ template <int FORM> struct Rec { static constexpr int n = FORM == 0 ? kInfoPoint
 //                    sum w (s x c) (3), c = R^T e
 // Plane record (30): pairs, sum w, sum w r^2 | sum w j j^T upper triangle, row-major (21) | sum w r j (6), j = [m ; s x m],
 //                    m = R^T n
+// GICP record (30):  the plane record's layout: pairs, sum w, sum w rho^2 | sum w G^T W G upper triangle, row-major (21) |
+//                    sum w G^T W u (6); one row's record is gicp_information_row (gicp_pair_device.hpp), where the pair algebra
+//                    of k_gicp_accumulate is stated
 // Operands of rows that do not contribute are SELECTED to zero before any product, so a NaN or inf row reaches no sum.
 template <int FORM>
 __global__ __launch_bounds__(NT) void k_information_pairs(InfoArgs a) {
@@ -53,6 +61,12 @@ __global__ __launch_bounds__(NT) void k_information_pairs(InfoArgs a) {
       v[9] = w * (s1 * s1); v[10] = w * (s1 * s2); v[11] = w * (s2 * s2);
       v[12] = w * c0; v[13] = w * c1; v[14] = w * c2;
       v[15] = w * (s1 * c2 - s2 * c1); v[16] = w * (s2 * c0 - s0 * c2); v[17] = w * (s0 * c1 - s1 * c0);
+    } else if constexpr (FORM == 2) {   // constexpr: the call takes a 30-value record
+      // one gathered target normal, one coalesced source normal; launched with rec and srec only.  A row that is not an
+      // inlier passes on = false and its operands are never multiplied
+      const double* ns = a.srec + 6 * b + 3;
+      gicp_information_row(v, inlier, R, a.src[3 * b], a.src[3 * b + 1], a.src[3 * b + 2], e0, e1, e2, p[3], p[4], p[5], ns[0], ns[1], ns[2],
+                           a.eps, a.delta);
     } else {
       const double n0 = p[3], n1 = p[4], n2 = p[5];   // FORM 1 is launched with rec only
       const bool on = inlier && (n0 != 0.0 || n1 != 0.0 || n2 != 0.0);
@@ -128,14 +142,15 @@ __global__ __launch_bounds__(NT) void k_information_finalize(const double* __res
 }  // namespace
 
 hipError_t launch_information(int form, const InfoArgs& a, double* result, hipStream_t st) {
-  if (a.B <= 0 || a.M <= 0 || (form != 0 && form != 1) || (form == 1 && !a.rec)) return hipErrorInvalidValue;
+  if (a.B <= 0 || a.M <= 0 || form < 0 || form > 2 || (form != 0 && !a.rec) || (form == 2 && !a.srec)) return hipErrorInvalidValue;
   const int64_t nblk = evaluate_blocks(a.B);
   if (form == 0) hipLaunchKernelGGL(k_information_pairs<0>, dim3((unsigned)nblk), dim3(NT), 0, st, a);
-  else hipLaunchKernelGGL(k_information_pairs<1>, dim3((unsigned)nblk), dim3(NT), 0, st, a);
+  else if (form == 1) hipLaunchKernelGGL(k_information_pairs<1>, dim3((unsigned)nblk), dim3(NT), 0, st, a);
+  else hipLaunchKernelGGL(k_information_pairs<2>, dim3((unsigned)nblk), dim3(NT), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (form == 0) hipLaunchKernelGGL(k_information_finalize<0>, dim3(1), dim3(NT), 0, st, a.partial, nblk, result);
-  else hipLaunchKernelGGL(k_information_finalize<1>, dim3(1), dim3(NT), 0, st, a.partial, nblk, result);
+  else hipLaunchKernelGGL(k_information_finalize<1>, dim3(1), dim3(NT), 0, st, a.partial, nblk, result);   // the GICP record has the plane record's layout
   return hipGetLastError();
 }
 

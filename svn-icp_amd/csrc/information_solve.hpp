@@ -87,7 +87,9 @@ inline int solve(svnicp_information* io, const char** why) {
   reason = nullptr;
   if (!io) { reason = "null struct"; return SVNICP_ERR_INVALID; }
   if (io->struct_size != (int32_t)sizeof(svnicp_information)) { reason = "svnicp_information.struct_size mismatch"; return SVNICP_ERR_INVALID; }
-  if (io->form != SVNICP_INFO_POINT && io->form != SVNICP_INFO_PLANE) { reason = "unknown form (SVNICP_INFO_POINT or SVNICP_INFO_PLANE)"; return SVNICP_ERR_INVALID; }
+  if (io->form != SVNICP_INFO_POINT && io->form != SVNICP_INFO_PLANE && io->form != SVNICP_INFO_GICP) {
+    reason = "unknown form (SVNICP_INFO_POINT, SVNICP_INFO_PLANE or SVNICP_INFO_GICP)"; return SVNICP_ERR_INVALID;
+  }
   if (!(io->eig_floor_ratio >= 0.0 && io->eig_floor_ratio < 1.0)) { reason = "eig_floor_ratio must lie in [0, 1)"; return SVNICP_ERR_INVALID; }
   if (io->pairs < 0) { reason = "pairs is negative"; return SVNICP_ERR_INVALID; }
   bool finite = std::isfinite(io->sum_wr2);
@@ -125,7 +127,7 @@ inline int solve(svnicp_information* io, const char** why) {
       for (int j = 0; j < 6; ++j) pinv[6 * i + j] += (v[i] * v[j]) * inv;
     }
   }
-  const int64_t dof = (io->form == SVNICP_INFO_POINT ? 3 : 1) * io->pairs - rank;
+  const int64_t dof = (io->form == SVNICP_INFO_PLANE ? 1 : 3) * io->pairs - rank;   // the GICP form's rho is a 3-vector's whitened norm
   io->sigma2 = dof > 0 ? io->sum_wr2 / (double)dof : 0.0;
   for (int i = 0; i < 36; ++i) io->cov[i] = io->sigma2 * pinv[i];
   return SVNICP_OK;

@@ -329,8 +329,11 @@ struct InfoArgs {
   double delta;         // Huber delta, +inf = unweighted
   EvalPose T;           // that evaluate's pose
   double* partial;      // [evaluate_blocks(B)][record of the form]
+  const double* srec;   // the GICP form only: [B][6] source xyz | unit normal, 0 = no normal here (nullptr for the other forms)
+  double eps;           // the GICP form only: epsilon of the surface covariances
 };
-// form 0 = point, 1 = plane (SVNICP_INFO_*).  k_information_pairs + k_information_finalize: result[kInfoResult] in device memory
+// form 0 = point, 1 = plane (SVNICP_INFO_*), 2 = the GICP form of svnicp_eval_information_gicp (gicp_pair_device.hpp; the record
+// has the plane form's layout).  k_information_pairs + k_information_finalize: result[kInfoResult] in device memory
 hipError_t launch_information(int form, const InfoArgs& a, double* result, hipStream_t st);
 // ---------------- score and weight the particles (particle_score.hip) ----------------
 constexpr int kScoreRecord = 5;        // per (workgroup, particle): evaluated, inliers, plane inliers (exact counts), sum d2, sum r2

@@ -2,14 +2,14 @@
 // dumps, per scan, what the pipeline handed to the solver and what it got back.  Used by tests/test_pipeline_gpu.py, which
 // replays the dumped solver inputs through the CPU oracle and through svn-icp_amd/pipeline.py.
 //   g++ -std=c++17 -I include -I svn-icp_amd/host pipeline_drive.cpp -L svn-icp_amd -lsvnicp_hip -o pipeline_drive
-//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist] [information off|point|plane] [modes off|mean|heaviest link_trans link_rot] [clear 0|1]
+//   pipeline_drive scans.bin out.bin P iterations knn voxel [particles.bin|-] [gpu_map 0|1|2] [deskew 0|1] [segment 0|1] [map_normals 0|1] [eval_dist] [information off|point|plane|gicp] [modes off|mean|heaviest link_trans link_rot] [clear 0|1]
 //     (gpu_map 2: device map + device pre-processing; deskew 1: PipelineConfig::deskew, OdometryPipeline.cpp:551-554;
 //      segment 1: PipelineConfig::segmentation with the HDL-64E sensor, USE_Segmentation, :328-355;
 //      map_normals 1: the point-to-plane residual with the normals of the device map's own voxels, needs gpu_map 1 or 2;
 //      map_normals 2: the generalized-ICP residual, the target's normals from the map as with 1, the source's from the solver's pass;
 //      eval_dist > 0: PipelineConfig::eval_dist, every registered scan is evaluated and one more line per scan is printed:
 //      "eval <scan>: fitness inlier_rmse plane_rmse plane_inliers" with %.17g, -1 where a figure does not exist;
-//      information point|plane: PipelineConfig::information (needs eval_dist > 0), one more line per registered scan:
+//      information point|plane|gicp: PipelineConfig::information (needs eval_dist > 0; gicp needs map_normals 2), one more line per registered scan:
 //      "info <scan>: pairs rank eigval[0] ... eigval[5]" with %.17g;
 //      modes mean|heaviest link_trans link_rot: PipelineConfig::mode_link_* / mode_select_heaviest, one more line per registered scan:
 //      "modes <scan>: n_modes n_reported nonfinite has_scores" and per reported mode " | label count best mass mean[0..5]" with %.17g;

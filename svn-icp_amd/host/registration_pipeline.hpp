@@ -995,7 +995,9 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   double eval_dist = 0.0;      // > 0: every registered scan is evaluated at its result pose with this inlier gate
                                // (svnicp_evaluate) before the map update; 0 = off, no call is made
   std::string information = "off";   // "point" | "plane": after that evaluate, the Gauss-Newton information matrix of its pairs
-                                     // (svnicp_eval_information) in ScanResult::information; needs eval_dist > 0.  "off": no call
+                                     // (svnicp_eval_information) in ScanResult::information; needs eval_dist > 0.  "gicp": the same in
+                                     // the generalized-ICP objective (svnicp_eval_information_gicp, with gicp_epsilon); only with
+                                     // the gicp residual.  "off": no call
   double info_huber = HUGE_VAL;      // with information: its Huber delta (+inf = unweighted)
   double weight_dist = 0.0;    // > 0: every registration ends with one scoring of the particles at this gate and soft-min weights
                                // (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures
@@ -1084,8 +1086,10 @@ class RegistrationPipeline {
     if (!(std::isfinite(cfg.weight_dist) && cfg.weight_dist >= 0)) throw std::invalid_argument("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)");
     if (cfg.weight_dist > 0 && !(std::isfinite(cfg.weight_temperature) && cfg.weight_temperature > 0))
       throw std::invalid_argument("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)");
-    if (cfg.information != "off" && cfg.information != "point" && cfg.information != "plane")
+    if (cfg.information != "off" && cfg.information != "point" && cfg.information != "plane" && cfg.information != "gicp")
       throw std::invalid_argument("PipelineConfig: information must be \"off\", \"point\" or \"plane\"");
+    if (cfg.information == "gicp" && !cfg.gicp && cfg.solver.residual != "gicp")
+      throw std::invalid_argument("PipelineConfig: information \"gicp\" needs solver.residual == \"gicp\" (only then does the context hold the normals of both clouds)");
     if (cfg.information != "off" && !(cfg.eval_dist > 0)) throw std::invalid_argument("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)");
     if (cfg.information != "off" && !(cfg.info_huber > 0)) throw std::invalid_argument("PipelineConfig: info_huber must be > 0 (+inf = unweighted)");
     if (cfg.prior_sigma) {
@@ -1315,7 +1319,9 @@ class RegistrationPipeline {
       const svnicp_eval ev = solver_->evaluate(cfg_.eval_dist, res.pose.R.data(), res.pose.t.data());
       res.fitness = ev.fitness; res.inlier_rmse = ev.inlier_rmse;
       if (ev.has_normals) { res.plane_rmse = ev.plane_rmse; res.plane_inliers = ev.plane_inliers; }
-      if (cfg_.information != "off")   // what a filter or a gate may read; no policy here either
+      if (cfg_.information == "gicp")   // what a filter or a gate may read; no policy here either
+        res.information = solver_->information_gicp(cfg_.info_huber, cfg_.solver.gicp_epsilon);
+      else if (cfg_.information != "off")
         res.information = solver_->information(cfg_.information == "plane" ? SVNICP_INFO_PLANE : SVNICP_INFO_POINT, cfg_.info_huber);
     }
     if (cfg_.clear_seen_through) {   // no policy here either: every registered scan clears, with the densest cloud the step has

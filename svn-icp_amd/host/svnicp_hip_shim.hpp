@@ -178,6 +178,14 @@ class SVGDICP {
     chk(svnicp_eval_information(h_, form, huber_delta, eig_floor_ratio, &o));
     return o;
   }
+  // the same in the generalized-ICP objective (svnicp_eval_information_gicp): needs normals of both clouds in the context;
+  // gicp_epsilon = 0: 1e-3
+  svnicp_information information_gicp(double huber_delta = HUGE_VAL, double gicp_epsilon = 0.0, double eig_floor_ratio = 0.0) {
+    svnicp_information o{};
+    o.struct_size = (int32_t)sizeof o;
+    chk(svnicp_eval_information_gicp(h_, huber_delta, gicp_epsilon, eig_floor_ratio, &o));
+    return o;
+  }
   // svnicp_information_solve without the library: every derived field from io.form, pairs, sum_wr2, eig_floor_ratio, H and b
   // (for instance the sums of several row-sharded contexts added up)
   static void information_solve(svnicp_information& io) {

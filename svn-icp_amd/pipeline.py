@@ -1406,7 +1406,7 @@ class PipelineConfig:
     solver: SteinICPParam = field(default_factory=lambda: SteinICPParam(iterations=20, lr=1.0, max_dist=1.0, KNN_count=100))
     seed: int = 0
     eval_dist: float = 0.0         # > 0: every registered scan is evaluated at its result pose with this inlier gate (svnicp_evaluate) before the map update; 0 = off, no call is made
-    information: str = "off"       # "point" | "plane": after that evaluate, the Gauss-Newton information matrix of its pairs (svnicp_eval_information) in ScanResult.information; needs eval_dist > 0.  "off": no call is made
+    information: str = "off"       # "point" | "plane": after that evaluate, the Gauss-Newton information matrix of its pairs (svnicp_eval_information) in ScanResult.information; needs eval_dist > 0.  "gicp": the same in the generalized-ICP objective (svnicp_eval_information_gicp, with solver.gicp_epsilon); only with solver.residual == "gicp".  "off": no call is made
     info_huber: float = float("inf")   # with information: its Huber delta (+inf = unweighted)
     weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
     weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
@@ -1486,8 +1486,10 @@ class PipelineConfig:
             raise ValueError("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)")
         if self.weight_dist > 0 and not (np.isfinite(self.weight_temperature) and self.weight_temperature > 0):
             raise ValueError("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)")
-        if self.information not in ("off", "point", "plane"):
+        if self.information not in ("off", "point", "plane", "gicp"):
             raise ValueError('PipelineConfig: information must be "off", "point" or "plane"')
+        if self.information == "gicp" and self.solver.residual != "gicp":
+            raise ValueError('PipelineConfig: information "gicp" needs solver.residual == "gicp" (only then does the context hold the normals of both clouds)')
         if self.information != "off" and not self.eval_dist > 0:
             raise ValueError("PipelineConfig: information needs eval_dist > 0 (its rows are the evaluate's)")
         if self.information != "off" and not self.info_huber > 0:

@@ -103,14 +103,14 @@ class RegistrationEval:
 class RegistrationInformation:
     """struct svnicp_information (include/svnicp_hip.h, "information matrix of a registration"): the Gauss-Newton normal
     equations of the last ``evaluate``'s pairs, tangent T * Exp([v ; omega]) (translation first), and their eigen-structure."""
-    form: str                  # "point" | "plane"
+    form: str                  # "point" | "plane" | "gicp"
     pairs: int                 # contributing rows
     rank: int                  # eigenvalues above eig_floor_ratio * the largest
     huber_delta: float
     eig_floor_ratio: float
     max_corr_dist: float       # the gate of the evaluate the rows came from
     sum_w: float
-    sum_wr2: float             # sum of w d2 (point) or w r^2 (plane)
+    sum_wr2: float             # sum of w d2 (point), w r^2 (plane) or w rho^2 (gicp)
     sigma2: float              # sum_wr2 / (dim * pairs - rank), 0 when that is not positive
     H: np.ndarray              # [6, 6]
     b: np.ndarray              # [6]
@@ -156,7 +156,8 @@ def _modes_from_struct(o) -> ParticleModes:
                          arr("cost_mean", np.float64), arr("mean", np.float64, 6), arr("cov", np.float64, 6, 6), T)
 
 
-_INFO_FORMS = {"point": binding.INFO_POINT, "plane": binding.INFO_PLANE}
+_INFO_FORMS = {"point": binding.INFO_POINT, "plane": binding.INFO_PLANE, "gicp": binding.INFO_GICP}
+_INFO_NAMES = {v: k for k, v in _INFO_FORMS.items()}
 
 
 def _information_from_struct(o) -> RegistrationInformation:
@@ -164,7 +165,7 @@ def _information_from_struct(o) -> RegistrationInformation:
     T = np.eye(4)
     T[:3, :3] = arr("R", 3, 3)
     T[:3, 3] = arr("t", 3)
-    return RegistrationInformation("plane" if o.form == binding.INFO_PLANE else "point", int(o.pairs), int(o.rank), float(o.huber_delta),
+    return RegistrationInformation(_INFO_NAMES[int(o.form)], int(o.pairs), int(o.rank), float(o.huber_delta),
                                    float(o.eig_floor_ratio), float(o.max_corr_dist), float(o.sum_w), float(o.sum_wr2), float(o.sigma2),
                                    arr("H", 6, 6), arr("b", 6), arr("eigval", 6), arr("eigvec", 6, 6), arr("eig_t", 3), arr("vec_t", 3, 3),
                                    arr("eig_r", 3), arr("vec_r", 3, 3), arr("step", 6), arr("cov", 6, 6), T)
@@ -569,14 +570,23 @@ class _SolverBase:
         return RegistrationEval(bool(e.has_normals), int(e.rows), int(e.evaluated), int(e.inliers), int(e.plane_inliers),
                                 float(e.sum_d2), float(e.sum_r2), float(e.fitness), float(e.inlier_rmse), float(e.plane_rmse), T)
 
-    def information(self, form="plane", huber_delta: float = float("inf"), eig_floor_ratio: float = 0.0) -> RegistrationInformation:
+    def information(self, form="plane", huber_delta: float = float("inf"), eig_floor_ratio: float = 0.0,
+                    gicp_epsilon: float | None = None) -> RegistrationInformation:
         """The Gauss-Newton information matrix H, gradient b, their eigen-structure, rank, step -H+ b and covariance over the
-        pairs of the last ``evaluate`` (include/svnicp_hip.h "information matrix of a registration"); ``form`` "point" or
-        "plane" is independent of the residual the solver ran."""
+        pairs of the last ``evaluate`` (include/svnicp_hip.h "information matrix of a registration"); ``form`` "point",
+        "plane" or "gicp" is independent of the residual the solver ran.  "gicp" (svnicp_eval_information_gicp) is the
+        generalized-ICP objective: it needs normals of both clouds in the context, and ``gicp_epsilon`` (None: this solver's
+        ``SteinICPParam.gicp_epsilon``) is its surface regularisation."""
         o = binding.InformationStruct()
         o.struct_size = C.sizeof(binding.InformationStruct)
-        self._check(self._L.svnicp_eval_information(self._h, int(_INFO_FORMS.get(form, form)), float(huber_delta), float(eig_floor_ratio),
-                                                    C.byref(o)), "svnicp_eval_information")
+        code = int(_INFO_FORMS.get(form, form))
+        if code == binding.INFO_GICP:
+            eps = self.config.gicp_epsilon if gicp_epsilon is None else gicp_epsilon
+            self._check(self._L.svnicp_eval_information_gicp(self._h, float(huber_delta), float(eps), float(eig_floor_ratio), C.byref(o)),
+                        "svnicp_eval_information_gicp")
+        else:
+            self._check(self._L.svnicp_eval_information(self._h, code, float(huber_delta), float(eig_floor_ratio), C.byref(o)),
+                        "svnicp_eval_information")
         return _information_from_struct(o)
 
     def get_eval_pairs(self) -> tuple:
