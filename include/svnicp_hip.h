@@ -18,6 +18,7 @@
 #ifndef SVNICP_HIP_H
 #define SVNICP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -489,6 +490,67 @@ int svnicp_score_particles(svnicp_ctx *ctx, double max_corr_dist, double *outPx6
 #define SVNICP_WEIGHT_SOFTMIN 1
 int svnicp_set_particle_weighting(svnicp_ctx *ctx, int kind, double max_corr_dist, double temperature);
 int svnicp_get_particle_scores(svnicp_ctx *ctx, double *outPx6, double *posesPx12);  /* of the last scoring, whoever ran it */
+
+/* ---- score and weight the particles in the objective the solver minimised ----------------------
+ * svnicp_score_particles knows one cost, the mean truncated squared point distance.  After a registration with the plane
+ * residual (svnicp_set_residual) or the generalized-ICP residual (svnicp_set_residual_gicp) that is not what the iterations
+ * minimised: sliding along a wall costs nothing there and a lot in the point cost.  These three score and weight in either
+ * residual's own terms.  Purely additive: svnicp_score_particles, svnicp_set_particle_weighting and every getter are unchanged.
+ * svnicp_score_particles_objective(ctx, obj, outPx6, posesPx12):
+ *   shared       poses, transformed point, winner, the classes `evaluated` and `inlier`, index clamping, determinism, `when`
+ *                and the four refusals are those of svnicp_score_particles, word for word.  The output is the same [P][6]
+ *                device block: svnicp_get_particle_scores, the weights, the weighted statistics and svnicp_particle_modes'
+ *                best / cost_min / cost_mean read its field 5 whatever form wrote it.
+ *   form         SVNICP_SCORE_POINT: exactly svnicp_score_particles(max_corr_dist) -- the same launches, the same bits;
+ *                huber_delta and epsilon are checked and not used.  SVNICP_SCORE_PLANE, SVNICP_SCORE_GICP: below.
+ *                SVNICP_SCORE_AS_SOLVED resolves at the call from the registration begun last: point residual -> POINT;
+ *                plane -> PLANE with the solver's huber_delta; GICP -> GICP with the solver's huber_delta and epsilon (a
+ *                huber_delta or epsilon passed with AS_SOLVED is checked and then replaced by the solver's).
+ *                An explicit form is the caller's choice, independent of the residual that ran, as with
+ *                svnicp_eval_information: a point-mode registration followed by svnicp_set_target_normals and form PLANE is fine.
+ *   out          forms PLANE and GICP, per particle: {evaluated, inliers, accepted, sum_d2, sum_h, cost}.
+ *   robust term  for x >= 0: h(x) = x*x if x <= delta else delta*(2*x - delta): twice Huber's rho, so delta = +inf gives x*x
+ *                and the unit stays m^2, as for the point cost and the temperature.  The branch is a select.  h is continuous.
+ *   PLANE        accepted: a plane inlier exactly as in svnicp_score_particles (an inlier, the context holds target normals,
+ *                the winner's normal n is non-zero).  r = (n0*e0 + n1*e1) + n2*e2, sum_h = sum h(|r|) with x*x = r*r.  With
+ *                delta = +inf the fields 0..4 equal svnicp_score_particles' fields 0..4 bit for bit.
+ *   GICP         accepted: a plane inlier whose source row has a non-zero normal in the context's packed source record (the
+ *                rule of the mode's accumulate kernel).  u = R^T e, m = R^T n, W = 2 eps (C(m) + C(n_s))^-1 (the closed form
+ *                of svnicp_eval_information_gicp), rho2 = max(u^T W u, 0), sum_h = sum h(sqrt(rho2)); inside delta the term is
+ *                rho2 itself, no square root.
+ *   cost         cap = h(max_corr_dist); cost = (sum_h + (B - accepted) * cap) / B.  The cap is derived, not chosen: |n| = 1
+ *                and W's eigenvalues lie in [epsilon, 1], so x <= |e| < max_corr_dist and every accepted pair costs at most
+ *                cap: a particle cannot lower its cost by shedding pairs.  Rows without a normal (target or, for GICP, source)
+ *                cost cap for every particle alike.  The cost is finite.
+ *   refused      SVNICP_ERR_INVALID with the reason in svnicp_last_error: a struct_size mismatch; an unknown form; a
+ *                max_corr_dist that is not finite and > 0; huber_delta negative or NaN; epsilon neither 0 nor in [1e-6, 1];
+ *                PLANE without normals of the current target in the context (no normal pass is ever run by a scoring); GICP
+ *                without them, or without normals of the current source (svnicp_set_source_normals, or a registration in
+ *                generalized-ICP mode that estimated them); knn_count too large for one row's candidates to fit the kernel's
+ *                LDS tile; and everything svnicp_score_particles refuses.
+ * svnicp_set_particle_weighting_objective(ctx, kind, obj, temperature): SVNICP_WEIGHT_SOFTMIN makes every following
+ * registration end with one scoring in obj in place of the point cost; with AS_SOLVED the form is resolved at each
+ * svnicp_align_begin (a form that then lacks its normals refuses the registration).  The weights and the weighted statistics
+ * are computed as under svnicp_set_particle_weighting, with its refusals (SVGD mode, the two shards, mini-batch,
+ * correspondence=full); a later svnicp_set_particle_weighting puts the point cost back.  SVNICP_WEIGHT_UNIFORM (obj may be
+ * NULL) runs exactly the launches of a context that never called either setter.
+ * svnicp_get_score_objective(ctx, out): the RESOLVED objective of the last scoring, whoever ran it (form never AS_SOLVED;
+ * huber_delta and epsilon as used, 0 where the form has none); SVNICP_ERR_INVALID before there is one.
+ * Not in the cost: the pose prior's chi^2.  Not available: shards, mini-batch, weighting in SVGD mode. */
+#define SVNICP_SCORE_AS_SOLVED (-1)  /* the residual of the registration begun last */
+#define SVNICP_SCORE_POINT 0         /* svnicp_score_particles' cost, unchanged */
+#define SVNICP_SCORE_PLANE 1
+#define SVNICP_SCORE_GICP  2
+typedef struct svnicp_score_objective {
+  size_t struct_size;     /* in: sizeof(svnicp_score_objective) */
+  int    form;            /* one of the four above */
+  double max_corr_dist;   /* finite, > 0: the gate, as today */
+  double huber_delta;     /* > 0, +inf = no robust weight; 0 = the solver's own (svnicp_set_residual / _gicp) */
+  double epsilon;         /* GICP only: 0 = the solver's own, else [1e-6, 1]: svnicp_set_residual_gicp's rule and constants */
+} svnicp_score_objective;
+int svnicp_score_particles_objective(svnicp_ctx *ctx, const svnicp_score_objective *obj, double *outPx6, double *posesPx12);
+int svnicp_set_particle_weighting_objective(svnicp_ctx *ctx, int kind, const svnicp_score_objective *obj, double temperature);
+int svnicp_get_score_objective(svnicp_ctx *ctx, svnicp_score_objective *out);  /* the RESOLVED objective of the last scoring */
 
 /* ---- particle modes: the particle set clustered on the device (an extension: the reference publishes particles and weights
  * and stops there; every getter above collapses the set into one mean, which lies between the peaks of a posterior that has

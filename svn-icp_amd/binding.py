@@ -64,6 +64,13 @@ class InformationStruct(C.Structure):
 INFO_POINT, INFO_PLANE = 0, 1   # SVNICP_INFO_POINT, SVNICP_INFO_PLANE
 INFO_GICP = 3                   # SVNICP_INFO_GICP (2 is not a form)
 MODES_MAX = 32                  # SVNICP_MODES_MAX
+SCORE_AS_SOLVED, SCORE_POINT, SCORE_PLANE, SCORE_GICP = -1, 0, 1, 2   # SVNICP_SCORE_*
+
+
+class ScoreObjectiveStruct(C.Structure):
+    """struct svnicp_score_objective (include/svnicp_hip.h)."""
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int), ("max_corr_dist", C.c_double), ("huber_delta", C.c_double),
+                ("epsilon", C.c_double)]
 
 
 class ModesOptStruct(C.Structure):
@@ -264,6 +271,9 @@ def load_library():
     L.svnicp_score_particles.argtypes = [vp, C.c_double, dp, dp]
     L.svnicp_set_particle_weighting.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     L.svnicp_get_particle_scores.argtypes = [vp, dp, dp]
+    L.svnicp_score_particles_objective.argtypes = [vp, C.POINTER(ScoreObjectiveStruct), dp, dp]
+    L.svnicp_set_particle_weighting_objective.argtypes = [vp, C.c_int, C.POINTER(ScoreObjectiveStruct), C.c_double]
+    L.svnicp_get_score_objective.argtypes = [vp, C.POINTER(ScoreObjectiveStruct)]
     L.svnicp_particle_modes.argtypes = [vp, C.POINTER(ModesOptStruct), C.POINTER(ModesStruct)]
     L.svnicp_get_mode_labels.argtypes = [vp, ip]
     for name in declared_symbols():

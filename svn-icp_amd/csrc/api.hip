@@ -143,7 +143,10 @@ struct EvalState {
 // svnicp_score_particles / svnicp_set_particle_weighting (csrc/particle_score.hip): its own buffers
 struct ScoreState {
   int kind = SVNICP_WEIGHT_UNIFORM;        // what the next registration ends with
-  double gate = 0.0, temperature = 0.0;
+  ScoreObjective cfg;                      // … scored in this objective, as configured (svnicp_set_particle_weighting: the point cost at its gate)
+  double temperature = 0.0;
+  ScoreObjective begun;                    // cfg resolved by the svnicp_align_begin of the registration begun last
+  ScoreObjective last;                     // the resolved objective of the scoring `scores` holds (svnicp_get_score_objective)
   bool on = false;                         // the registration begun last ends with a scoring and weighted statistics
   const char* reg_refusal = nullptr;       // why the registration begun last cannot be scored (registration_plan.hpp: scoring_refusal)
   DevBuf<double> partial, scores, poses, w;   // [score_blocks(B)][Ppad][kScoreRecord], [P][kScoreFields], [P][12], [P]
@@ -271,6 +274,9 @@ static RegistrationFacts registration_facts(const svnicp_ctx* c, bool plane, boo
   f.plane = plane || gicp; f.normals_supplied = c->pl.supplied; f.normal_k = c->pl.normal_k;
   f.gicp = gicp; f.source_normals_supplied = c->gi.supplied;
   f.weighting = c->sc.kind;
+  f.weighting_form = resolve_score_objective(c->sc.cfg, f.plane, gicp, c->pl.delta, c->gi.eps).form;
+  f.target_normals = f.plane || c->pl.supplied || c->pl.estimated;
+  f.source_normals = gicp || c->gi.supplied || c->gi.estimated;
   f.prior = prior;
   return f;
 }
@@ -588,6 +594,7 @@ int svnicp_align_begin(svnicp_ctx* c) {
   c->pr.on = f.prior; c->pr.args = c->pr.next;
   c->ev.mark_stale("a registration began after the last svnicp_evaluate");   // svnicp_eval_information wants one afterwards
   c->sc.on = f.weighting != 0; c->sc.reg_refusal = scoring_refusal(f, c->tune);
+  c->sc.begun = resolve_score_objective(c->sc.cfg, plane, gicp, c->pl.delta, c->gi.eps);
   c->mb.on = r.mb; c->mb.have = false; c->mb.check = false;
   c->mb.rows = r.mb ? r.Bt : 0;
   c->mb.nq = r.mb ? r.Bq : 0;
@@ -973,9 +980,12 @@ int svnicp_iter_update(svnicp_ctx* c, int it) {
 }
 
 // k_particle_score + k_particle_score_finalize on the context's stream: sc.scores [P][6] and sc.poses [P][12] (a copy of the
-// total poses that were scored: the next svnicp_set_particles rewrites Rtot)
-static int enqueue_scoring(svnicp_ctx* c, double gate) {
+// total poses that were scored: the next svnicp_set_particles rewrites Rtot), in the resolved objective `o` (the point form:
+// the launches and arguments of svnicp_score_particles)
+static int enqueue_scoring(svnicp_ctx* c, const ScoreObjective& o) {
   const bool normals = c->pl.supplied || c->pl.estimated;
+  if (const char* why = score_normals_refusal(o.form, normals, c->gi.supplied || c->gi.estimated))
+    return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + why);
   if (score_tile_rows(c->P, c->K, normals) < 1)
     return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + "knn_count is too large for one row's candidates to fit the scoring kernel's LDS tile");
   ScoreState& sc = c->sc;
@@ -985,10 +995,14 @@ static int enqueue_scoring(svnicp_ctx* c, double gate) {
   HIPCHK(c, sc.poses.ensure((size_t)c->P * 12));
   ScoreArgs a{};
   a.src = c->cloud.src.p; a.tgt = c->cloud.tgt.p; a.rec = normals ? c->pl.rec.p : nullptr; a.cand = c->sa.cand_idx.p; a.Rtot = c->st.Rtot.p;
-  a.B = c->B; a.M = c->M; a.K = c->K; a.P = c->P; a.thr2 = gate * gate; a.partial = sc.partial.p;
+  a.B = c->B; a.M = c->M; a.K = c->K; a.P = c->P; a.thr2 = o.gate * o.gate; a.partial = sc.partial.p;
+  if (o.form != kScorePoint) {
+    a.form = o.form; a.delta = o.delta; a.eps = o.eps; a.cap = robust_cost(o.gate, a.thr2, o.delta);
+    a.srec = o.form == kScoreGicp ? c->gi.rec.p : nullptr;
+  }
   HIPCHK(c, launch_particle_score(a, sc.scores.p, c->stream));
   HIPCHK(c, hipMemcpyAsync(sc.poses.p, c->st.Rtot.p, (size_t)c->P * 12 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  sc.have = true; sc.P = c->P; sc.of_result = true;
+  sc.have = true; sc.P = c->P; sc.of_result = true; sc.last = o;
   return SVNICP_OK;
 }
 
@@ -999,7 +1013,7 @@ int svnicp_finish(svnicp_ctx* c) {
   HIPCHK(c, hipEventRecord(c->prof.ev[2], c->stream));
   StatsArgs s{c->st.pose_out.p, c->P, c->prm.mode, c->st.stats.p};
   if (c->sc.on) {   // one scoring at the poses the iterations left, the weights, the reference's weighted expressions
-    if (const int rc = enqueue_scoring(c, c->sc.gate)) return rc;
+    if (const int rc = enqueue_scoring(c, c->sc.begun)) return rc;
     HIPCHK(c, c->sc.w.ensure((size_t)c->P));
     HIPCHK(c, launch_particle_weights(c->sc.scores.p, c->P, c->sc.temperature, c->sc.w.p, c->stream));
     HIPCHK(c, launch_stats_weighted(s, c->sc.w.p, c->stream));
@@ -1653,7 +1667,9 @@ int svnicp_score_particles(svnicp_ctx* c, double max_corr_dist, double* outPx6, 
   if (c->sc.reg_refusal) return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + c->sc.reg_refusal);
   if (const int rc = svnicp_synchronize(c)) return rc;   // an asynchronous registration has finished and its checks have run
   if (bind(c)) return SVNICP_ERR_HIP;
-  if (const int rc = enqueue_scoring(c, max_corr_dist)) return rc;
+  ScoreObjective point;
+  point.gate = max_corr_dist;
+  if (const int rc = enqueue_scoring(c, point)) return rc;
   if (!outPx6 && !posesPx12) { HIPCHK(c, hipStreamSynchronize(c->stream)); return SVNICP_OK; }
   return svnicp_get_particle_scores(c, outPx6, posesPx12);
 }
@@ -1667,7 +1683,58 @@ int svnicp_set_particle_weighting(svnicp_ctx* c, int kind, double max_corr_dist,
       return fail(c, SVNICP_ERR_INVALID, "svnicp_set_particle_weighting: temperature must be finite and positive");
   }
   c->sc.kind = kind;   // an unknown kind is refused by svnicp_align_begin
-  c->sc.gate = max_corr_dist; c->sc.temperature = temperature;
+  c->sc.cfg = ScoreObjective{}; c->sc.cfg.gate = max_corr_dist;   // the point cost (back, after svnicp_set_particle_weighting_objective)
+  c->sc.temperature = temperature;
+  return SVNICP_OK;
+}
+
+// ---- … in the objective the solver minimised ----
+// the caller's struct as the rules of registration_plan.hpp take it; nullptr: nothing was refused
+static const char* read_score_objective(const svnicp_score_objective* obj, ScoreObjective& o) {
+  if (!obj) return "null svnicp_score_objective";
+  if (obj->struct_size != sizeof(svnicp_score_objective)) return "svnicp_score_objective.struct_size mismatch";
+  o.form = obj->form; o.gate = obj->max_corr_dist; o.delta = obj->huber_delta; o.eps = obj->epsilon;
+  return score_objective_refusal(o, kGicpEpsilonMin);
+}
+
+int svnicp_score_particles_objective(svnicp_ctx* c, const svnicp_score_objective* obj, double* outPx6, double* posesPx12) {
+  CTX_CHECK(c);
+  ScoreObjective o;
+  if (const char* why = read_score_objective(obj, o)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_score_particles_objective: ") + why);
+  if (!c->run.have_result)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_score_particles_objective: no finished registration yet (the candidate table belongs to one)");
+  if (!c->run.have_candidates)
+    return fail(c, SVNICP_ERR_INVALID, "svnicp_score_particles_objective: the source, the target, the initial mean, K or an option changed since the last registration: "
+                                       "register again first (the candidate table belongs to that registration)");
+  if (c->sc.reg_refusal) return fail(c, SVNICP_ERR_INVALID, std::string(kScoringRefusal) + c->sc.reg_refusal);
+  o = resolve_score_objective(o, c->pl.on, c->gi.on, c->pl.delta, c->gi.eps);
+  if (const int rc = svnicp_synchronize(c)) return rc;   // an asynchronous registration has finished and its checks have run
+  if (bind(c)) return SVNICP_ERR_HIP;
+  if (const int rc = enqueue_scoring(c, o)) return rc;
+  if (!outPx6 && !posesPx12) { HIPCHK(c, hipStreamSynchronize(c->stream)); return SVNICP_OK; }
+  return svnicp_get_particle_scores(c, outPx6, posesPx12);
+}
+
+int svnicp_set_particle_weighting_objective(svnicp_ctx* c, int kind, const svnicp_score_objective* obj, double temperature) {
+  CTX_CHECK(c);
+  ScoreObjective o;
+  if (kind != SVNICP_WEIGHT_UNIFORM) {
+    if (const char* why = read_score_objective(obj, o)) return fail(c, SVNICP_ERR_INVALID, std::string("svnicp_set_particle_weighting_objective: ") + why);
+    if (!(temperature > 0.0) || !std::isfinite(temperature))
+      return fail(c, SVNICP_ERR_INVALID, "svnicp_set_particle_weighting_objective: temperature must be finite and positive");
+  }
+  c->sc.kind = kind;   // an unknown kind is refused by svnicp_align_begin
+  c->sc.cfg = o; c->sc.temperature = temperature;
+  return SVNICP_OK;
+}
+
+int svnicp_get_score_objective(svnicp_ctx* c, svnicp_score_objective* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_score_objective: null result struct");
+  if (!c->sc.have) return fail(c, SVNICP_ERR_INVALID, "svnicp_get_score_objective: no scoring yet (svnicp_score_particles, svnicp_score_particles_objective, or a weighted registration)");
+  const ScoreObjective& o = c->sc.last;
+  out->struct_size = sizeof(svnicp_score_objective);
+  out->form = o.form; out->max_corr_dist = o.gate; out->huber_delta = o.delta; out->epsilon = o.eps;
   return SVNICP_OK;
 }
 

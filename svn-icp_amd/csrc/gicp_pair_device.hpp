@@ -1,6 +1,6 @@
 // gicp_pair_device.hpp — one pair of the generalized-ICP residual: the combined weight of the two surfaces
-// and the pair's terms of H, b and the statistics.  Stated once for k_gicp_accumulate (gicp_icp.hip) and for the GICP form
-// of the information matrix (information.hip).
+// and the pair's terms of H, b and the statistics.  Stated once for k_gicp_accumulate (gicp_icp.hip), for the GICP form
+// of the information matrix (information.hip) and for the GICP form of the particle scores (particle_score.hip).
 //
 // In the source frame, with m = Rtᵀ n_q (the winner's unit normal), n the source point's unit normal, u = Rtᵀ (Ts − q):
 //   C(x) = I − (1 − ε) x xᵀ          regularised surface covariance: ε along the normal, 1 in the plane
@@ -17,8 +17,10 @@
 
 #if defined(__HIPCC__)
 #define SVNICP_GICP_FN __device__ __forceinline__
+#define SVNICP_GICP_HOST_FN __host__ __device__ __forceinline__   // the host states a scoring's cap with the device's own function
 #else
 #define SVNICP_GICP_FN inline
+#define SVNICP_GICP_HOST_FN inline
 #endif
 
 namespace svnicp {
@@ -39,6 +41,41 @@ SVNICP_GICP_FN void gicp_weight(double m0, double m1, double m2, double n0, doub
   W[0] = k * c00; W[1] = k * c01; W[2] = k * c02; W[3] = k * c11; W[4] = k * c12; W[5] = k * c22;
 }
 
+// The pair's metric terms, before any robust weight: W = gicp_weight(m, n, ε), v = W u, and ρ² = max(uᵀ v, 0) (returned).
+// Stated once for gicp_pair_sums (H, b, the statistics) and gicp_pair_cost (the particle scores).
+SVNICP_GICP_FN double gicp_pair_metric(double u0, double u1, double u2, double m0, double m1, double m2, double n0, double n1, double n2,
+                                       double eps, double (&W)[6], double (&v)[3]) {
+  gicp_weight(m0, m1, m2, n0, n1, n2, eps, W);
+  v[0] = (W[0] * u0 + W[1] * u1) + W[2] * u2;   // W u
+  v[1] = (W[1] * u0 + W[3] * u1) + W[4] * u2;
+  v[2] = (W[2] * u0 + W[4] * u1) + W[5] * u2;
+  const double q = (u0 * v[0] + u1 * v[1]) + u2 * v[2];
+  return q > 0.0 ? q : 0.0;                     // W is positive definite: a negative value is round-off of a zero
+}
+
+// h(x) for x >= 0, handed x and its square x2: x2 inside δ, δ (2x − δ) beyond — twice Huber's ρ, so δ = +inf gives x2 itself
+// and the unit stays m².  The branch is a select, and the outer term is formed from a δ that is selected to zero inside: never
+// a product with an unselected inf.  Stated once for the plane and the GICP form of the particle scores.
+SVNICP_GICP_HOST_FN double robust_cost(double x, double x2, double delta) {
+  const bool in = x <= delta;
+  const double d = in ? 0.0 : delta;
+  return in ? x2 : d * (2.0 * x - d);
+}
+
+// One pair of the particle scores' GICP form (particle_score.hip): h(√ρ²) with ρ² as gicp_pair_sums forms
+// it, 0 for a rejected pair; `accepted` is 1.0 or 0.0.  ok == false: every operand is selected to zero first, as below.
+SVNICP_GICP_FN double gicp_pair_cost(bool ok, double u0, double u1, double u2, double m0, double m1, double m2, double n0, double n1, double n2,
+                                     double eps, double delta, double& accepted, double* rho2_out = nullptr) {
+  u0 = ok ? u0 : 0.0; u1 = ok ? u1 : 0.0; u2 = ok ? u2 : 0.0;
+  m0 = ok ? m0 : 0.0; m1 = ok ? m1 : 0.0; m2 = ok ? m2 : 0.0;
+  n0 = ok ? n0 : 0.0; n1 = ok ? n1 : 0.0; n2 = ok ? n2 : 0.0;
+  double W[6], v[3];
+  const double rho2 = gicp_pair_metric(u0, u1, u2, m0, m1, m2, n0, n1, n2, eps, W, v);
+  if (rho2_out) *rho2_out = rho2;
+  accepted = ok ? 1.0 : 0.0;
+  return robust_cost(sqrt(rho2), rho2, delta);   // inside δ the term is ρ² itself; a rejected pair: ρ² = 0, h = 0 exactly
+}
+
 // One pair into the 29 sums; returns the pair's Huber weight w (0 for a rejected pair).  s: the source point, u = Rtᵀ e,
 // m = Rtᵀ n_q, n: the source normal.  ok == false: every operand is selected to zero first (never multiplied: a non-finite point
 // must not leak a NaN), so the pair adds exact zeros.
@@ -48,13 +85,9 @@ SVNICP_GICP_FN double gicp_pair_sums(double (&acc)[kGicpSums], bool ok, double s
   u0 = ok ? u0 : 0.0; u1 = ok ? u1 : 0.0; u2 = ok ? u2 : 0.0;
   m0 = ok ? m0 : 0.0; m1 = ok ? m1 : 0.0; m2 = ok ? m2 : 0.0;
   n0 = ok ? n0 : 0.0; n1 = ok ? n1 : 0.0; n2 = ok ? n2 : 0.0;
-  double W[6];
-  gicp_weight(m0, m1, m2, n0, n1, n2, eps, W);
-  const double v0 = (W[0] * u0 + W[1] * u1) + W[2] * u2;   // W u
-  const double v1 = (W[1] * u0 + W[3] * u1) + W[4] * u2;
-  const double v2 = (W[2] * u0 + W[4] * u1) + W[5] * u2;
-  const double q = (u0 * v0 + u1 * v1) + u2 * v2;
-  const double rho2 = q > 0.0 ? q : 0.0;                    // W is positive definite: a negative value is round-off of a zero
+  double W[6], v[3];
+  const double rho2 = gicp_pair_metric(u0, u1, u2, m0, m1, m2, n0, n1, n2, eps, W, v);
+  const double v0 = v[0], v1 = v[1], v2 = v[2];
   const double rho = sqrt(rho2);
   const double w = ok ? (rho <= delta ? 1.0 : delta / rho) : 0.0;   // Huber: 1 inside delta, delta / ρ outside
   double ww[6];

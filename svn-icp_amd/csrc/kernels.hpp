@@ -336,7 +336,7 @@ struct InfoArgs {
 // has the plane form's layout).  k_information_pairs + k_information_finalize: result[kInfoResult] in device memory
 hipError_t launch_information(int form, const InfoArgs& a, double* result, hipStream_t st);
 // ---------------- score and weight the particles (particle_score.hip) ----------------
-constexpr int kScoreRecord = 5;        // per (workgroup, particle): evaluated, inliers, plane inliers (exact counts), sum d2, sum r2
+constexpr int kScoreRecord = 5;        // per (workgroup, particle): evaluated, inliers, plane inliers (exact counts), sum d2, sum r2 (forms 1, 2: accepted, sum h)
 constexpr int kScoreFields = 6;        // per particle: the record's five totals | cost  (SVNICP_SCORE_FIELDS)
 constexpr int kScoreRowsPerBlock = 64; // source rows a workgroup owns: a multiple of every row step of the geometry
 struct ScoreArgs {
@@ -350,6 +350,11 @@ struct ScoreArgs {
   int Ppad, TH;         // set by the launcher: padded particle count, source rows per LDS tile
   double thr2;          // max_corr_dist^2
   double* partial;      // [score_blocks(B)][Ppad][kScoreRecord]
+  // svnicp_score_particles_objective; all zero: the point cost above
+  int form;             // SVNICP_SCORE_POINT | _PLANE | _GICP (resolved, never AS_SOLVED); forms 1 and 2 need rec, form 2 srec
+  const double* srec;   // [B][6] source xyz | unit normal (GicpState::rec), form 2
+  double delta, eps;    // the robust term's delta (+inf: none), the GICP epsilon
+  double cap;           // h(max_corr_dist): what a row that is not accepted costs in forms 1 and 2
 };
 int64_t score_blocks(int64_t B);
 int score_padded_particles(int P, int K);

@@ -1,6 +1,7 @@
 // particle_score.hip — svnicp_score_particles / svnicp_set_particle_weighting (include/svnicp_hip.h "score and weight the
 // particles"): every particle's total pose scored through the candidate table of the registration, by the
-// nearest-of-K rule the iterations use.  Three kernels:
+// nearest-of-K rule the iterations use — in the point cost, or (svnicp_score_particles_objective, §4.12.1) in the plane or the
+// generalized-ICP residual the solver minimised: k_particle_score's FORM.  Three kernels:
 //   k_particle_score           lanes along the particles (ParticleLanes, lane_fold_device.hpp), source rows in LDS tiles: the
 //                              K candidate rows of a tile are gathered once, cooperatively (indices coalesced, the target
 //                              rows or xyz | normal records behind them), and every particle lane reads them as broadcasts.
@@ -11,6 +12,7 @@
 // [64 x, 64 x + 64); inside it row b belongs to slot b mod STEP of the workgroup whatever the tile height, so every
 // addition happens in an order that depends on B and P alone.
 #include "kernels.hpp"
+#include "gicp_pair_device.hpp"
 #include "lane_fold_device.hpp"
 
 namespace svnicp {
@@ -21,7 +23,10 @@ constexpr int kTileBytes = 40 * 1024;   // a tile of candidate rows: three workg
 constexpr int kTileRowsMax = 16;        // rows of a tile: the row slots of the narrowest geometry (16 particles per wave)
 constexpr int kTileBytesMax = 64 * 1024;   // one source row's candidates at most (K = 620 with normals: 29 KB)
 
-template <int PW, int WP>
+// FORM (SVNICP_SCORE_*): 0 = the point cost, 1 = the Huber-weighted plane residual, 2 = the generalized-ICP
+// residual.  Staging, the winner loop, the row slots and the fold are shared: only the tail after the winner differs.  Forms 1
+// and 2 always stage the 48-byte records; their record is {evaluated, inliers, accepted, sum d2, sum h}.
+template <int FORM, int PW, int WP>
 __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
   extern __shared__ __align__(16) double lds[];
   using Lanes = ParticleLanes<PW, WP>;
@@ -35,7 +40,7 @@ __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
 
   double Rt[9], tt[3];
   load_pose(a.Rtot + 12 * (size_t)(pvalid ? pidx : 0), Rt, tt);
-  const bool normals = a.rec != nullptr;
+  const bool normals = FORM != 0 || a.rec != nullptr;
   const int W = normals ? 6 : 3;
   const int K = a.K;
   double ev = 0.0, in = 0.0, pin = 0.0, sd = 0.0, sr = 0.0;   // the counts are exact in float64 (B < 2^31)
@@ -89,7 +94,32 @@ __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
       ev += evaluated ? 1.0 : 0.0;
       in += inlier ? 1.0 : 0.0;
       sd += inlier ? best : 0.0;
-      if (normals) {
+      if constexpr (FORM != 0) {
+        const double* q = row + (size_t)kb * W;
+        const bool pli = inlier && (q[3] != 0.0 || q[4] != 0.0 || q[5] != 0.0);
+        if constexpr (FORM == 1) {   // form 0's expressions; h(|r|) in r * r's place (delta = +inf: r * r itself)
+          const double e0 = pli ? T0 - q[0] : 0.0, e1 = pli ? T1 - q[1] : 0.0, e2 = pli ? T2 - q[2] : 0.0;
+          const double n0 = pli ? q[3] : 0.0, n1 = pli ? q[4] : 0.0, n2 = pli ? q[5] : 0.0;
+          const double res = (n0 * e0 + n1 * e1) + n2 * e2;
+          pin += pli ? 1.0 : 0.0;
+          sr += robust_cost(fabs(res), res * res, a.delta);
+        } else {                     // k_gicp_accumulate's pair: the row's source normal is one address for every particle lane
+          const double* sn = a.srec + 6 * (size_t)(t0 + r);
+          const double ns0 = sn[3], ns1 = sn[4], ns2 = sn[5];
+          const bool ok = pli && (ns0 != 0.0 || ns1 != 0.0 || ns2 != 0.0);
+          const double g0 = ok ? T0 - q[0] : 0.0, g1 = ok ? T1 - q[1] : 0.0, g2 = ok ? T2 - q[2] : 0.0;
+          const double h0 = ok ? q[3] : 0.0, h1 = ok ? q[4] : 0.0, h2 = ok ? q[5] : 0.0;
+          const double u0 = Rt[0] * g0 + Rt[3] * g1 + Rt[6] * g2;   // u = Rtᵀ e
+          const double u1 = Rt[1] * g0 + Rt[4] * g1 + Rt[7] * g2;
+          const double u2 = Rt[2] * g0 + Rt[5] * g1 + Rt[8] * g2;
+          const double m0 = Rt[0] * h0 + Rt[3] * h1 + Rt[6] * h2;   // m = Rtᵀ n_q
+          const double m1 = Rt[1] * h0 + Rt[4] * h1 + Rt[7] * h2;
+          const double m2 = Rt[2] * h0 + Rt[5] * h1 + Rt[8] * h2;
+          double accepted;
+          sr += gicp_pair_cost(ok, u0, u1, u2, m0, m1, m2, ns0, ns1, ns2, a.eps, a.delta, accepted);
+          pin += accepted;
+        }
+      } else if (normals) {
         const double* q = row + (size_t)kb * W;
         const bool pli = inlier && (q[3] != 0.0 || q[4] != 0.0 || q[5] != 0.0);   // a zero row: no normal here
         // a rejected pair's operands are selected to zero, not multiplied: a non-finite point must not leak a NaN
@@ -109,9 +139,10 @@ __global__ __launch_bounds__(NT) void k_particle_score(ScoreArgs a) {
 
 // scores[p] = {evaluated, inliers, plane inliers, sum d2, sum r2, cost} from the workgroups' records, added by
 // reduce_block_records (lane_fold_device.hpp); a workgroup's 16 entries are the five sums of three particles (one entry
-// idle).  cost = (sum_d2 + (B - inliers) * thr2) / B.
+// idle).  cost = (sum + (B - count) * cap) / B with (count, sum, cap) = (inliers, sum_d2, thr2) of the point cost, (accepted,
+// sum_h, h(max_corr_dist)) of the plane and GICP forms: count_f and sum_f are the two fields' places in the record.
 __global__ __launch_bounds__(NT) void k_particle_score_finalize(const double* __restrict__ partial, int nblk, int Ppad, int P, double rows,
-                                                                 double thr2, double* __restrict__ scores) {
+                                                                 int count_f, int sum_f, double cap, double* __restrict__ scores) {
   __shared__ double tot[16];
   const int el = threadIdx.x & 15, bl = threadIdx.x >> 4;
   const int p = (int)blockIdx.x * 3 + el / kScoreRecord, f = el % kScoreRecord;
@@ -123,8 +154,8 @@ __global__ __launch_bounds__(NT) void k_particle_score_finalize(const double* __
   }
   __syncthreads();
   if (bl == 0 && valid && f == 0) {
-    const double inl = tot[el + 1], sum_d2 = tot[el + 3];
-    scores[(size_t)p * kScoreFields + 5] = (sum_d2 + (rows - inl) * thr2) / rows;
+    const double cnt = tot[el + count_f], sum = tot[el + sum_f];
+    scores[(size_t)p * kScoreFields + 5] = (sum + (rows - cnt) * cap) / rows;
   }
 }
 
@@ -154,12 +185,12 @@ __global__ __launch_bounds__(NT) void k_particle_weights(const double* __restric
   for (int p = tid; p < P; p += NT) w[p] = w[p] / Z;
 }
 
-template <int PW, int WP>
+template <int FORM, int PW, int WP>
 hipError_t launch_s(const ScoreArgs& a, int grid_y, hipStream_t st) {
   constexpr int WB = 4 / WP;
-  const size_t tile = (size_t)a.TH * a.K * (a.rec ? 6 : 3) * sizeof(double);
+  const size_t tile = (size_t)a.TH * a.K * (FORM != 0 || a.rec ? 6 : 3) * sizeof(double);
   const size_t red = (size_t)(WB - 1) * (WP * PW) * kScoreRecord * sizeof(double);   // at most 3 * 64 * 5 * 8 = 7.5 KB
-  hipLaunchKernelGGL((k_particle_score<PW, WP>), dim3((unsigned)score_blocks(a.B), grid_y), dim3(NT), tile > red ? tile : red, st, a);
+  hipLaunchKernelGGL((k_particle_score<FORM, PW, WP>), dim3((unsigned)score_blocks(a.B), grid_y), dim3(NT), tile > red ? tile : red, st, a);
   return hipGetLastError();
 }
 
@@ -188,12 +219,19 @@ hipError_t launch_particle_score(ScoreArgs a, double* scores, hipStream_t st) {
   if (a.B <= 0 || a.M <= 0 || a.P <= 0 || a.K < 1) return hipErrorInvalidValue;
   const AccumPlan sh = score_shape(a.P, a.K);
   a.Ppad = sh.Ppad;
-  a.TH = score_tile_rows(a.P, a.K, a.rec != nullptr);
+  if (a.form < 0 || a.form > 2 || (a.form != 0 && !a.rec) || (a.form == 2 && !a.srec)) return hipErrorInvalidValue;
+  a.TH = score_tile_rows(a.P, a.K, a.form != 0 || a.rec != nullptr);
   if (a.TH < 1) return hipErrorInvalidValue;   // refused, never overflowed
-  const hipError_t e = dispatch_lanes(sh.PW, sh.WP, [&](auto l) { return launch_s<l.PW, l.WP>(a, sh.grid_y, st); });
+  const hipError_t e = dispatch_lanes(sh.PW, sh.WP, [&](auto l) {
+    if (a.form == 1) return launch_s<1, l.PW, l.WP>(a, sh.grid_y, st);
+    if (a.form == 2) return launch_s<2, l.PW, l.WP>(a, sh.grid_y, st);
+    return launch_s<0, l.PW, l.WP>(a, sh.grid_y, st);
+  });
   if (e != hipSuccess) return e;
+  // the point cost: a row that is no inlier costs the gate; the other forms: a row that is not accepted costs h(gate)
+  const bool point = a.form == 0;
   hipLaunchKernelGGL(k_particle_score_finalize, dim3((a.P + 2) / 3), dim3(NT), 0, st, a.partial, (int)score_blocks(a.B), a.Ppad, a.P,
-                     (double)a.B, a.thr2, scores);
+                     (double)a.B, point ? 1 : 2, point ? 3 : 4, point ? a.thr2 : a.cap, scores);
   return hipGetLastError();
 }
 

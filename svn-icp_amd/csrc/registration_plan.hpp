@@ -58,6 +58,9 @@ struct RegistrationFacts {
   bool gicp = false;                   // svnicp_set_residual_gicp: generalized ICP (then `plane` is set too: it runs the plane residual's launch shape)
   bool source_normals_supplied = false;
   int weighting = 0;                   // svnicp_set_particle_weighting: SVNICP_WEIGHT_* (0 = uniform, the reference)
+  int weighting_form = 0;              // … in which cost: the resolved SVNICP_SCORE_* form (0 = the point cost; _objective setter: 1 plane, 2 GICP)
+  bool target_normals = false;         // the context holds normals of the current target, or this registration estimates them
+  bool source_normals = false;         // … of the current source
   bool prior = false;                  // svnicp_set_pose_prior: a Gaussian prior on the correction is added in front of the Stein step
   int nshard() const { return p_hi - p_lo; }
   bool whole_shard() const { return p_lo == 0 && p_hi == P; }
@@ -148,13 +151,51 @@ inline const char* scoring_refusal(const RegistrationFacts& f, const Tuning& t) 
       {t.full_corr != 0, "option correspondence=full is set: the iterations did not search the candidate table"},
   });
 }
-// weighting the particle set at the end of a registration (nullptr: nothing, or the weights are uniform).  The setter
-// itself refuses a non-finite or non-positive max_corr_dist or temperature.
+// the objective a scoring runs in (svnicp_score_objective, include/svnicp_hip.h).  form: SVNICP_SCORE_*
+struct ScoreObjective {
+  int form = 0;                          // -1 = as solved, 0 = point, 1 = plane, 2 = GICP
+  double gate = 0.0, delta = 0.0, eps = 0.0;
+};
+constexpr int kScoreAsSolved = -1, kScorePoint = 0, kScorePlane = 1, kScoreGicp = 2;
+// what the struct's values themselves must satisfy, whoever takes them (the scoring, the weighting setter); eps_min:
+// svnicp_set_residual_gicp's lower bound
+inline const char* score_objective_refusal(const ScoreObjective& o, double eps_min) {
+  return first_refusal({
+      {o.form < kScoreAsSolved || o.form > kScoreGicp, "unknown form (SVNICP_SCORE_AS_SOLVED, _POINT, _PLANE or _GICP)"},
+      {!(o.gate > 0.0) || !(o.gate <= 1.7976931348623157e308), "max_corr_dist must be finite and positive"},
+      {!(o.delta >= 0.0), "huber_delta must be positive (+inf: no robust weight) or 0 (the solver's own)"},
+      {o.eps != 0.0 && !(o.eps >= eps_min && o.eps <= 1.0), "epsilon must be 0 (the solver's own) or in [1e-6, 1]"},
+  });
+}
+// AS_SOLVED becomes the form of the residual that ran (or is about to run), with the solver's delta and epsilon; an
+// explicit form keeps its own and takes the solver's where it says 0.  The point form has neither.
+inline ScoreObjective resolve_score_objective(ScoreObjective o, bool ran_plane, bool ran_gicp, double solver_delta, double solver_eps) {
+  if (o.form == kScoreAsSolved) {
+    o.form = ran_gicp ? kScoreGicp : ran_plane ? kScorePlane : kScorePoint;
+    o.delta = solver_delta; o.eps = solver_eps;
+  }
+  if (o.delta == 0.0) o.delta = solver_delta;
+  if (o.eps == 0.0) o.eps = solver_eps;
+  if (o.form == kScorePoint) o.delta = 0.0;
+  if (o.form != kScoreGicp) o.eps = 0.0;
+  return o;
+}
+// the normals a resolved form reads (no normal pass is ever run by a scoring)
+inline const char* score_normals_refusal(int form, bool target_normals, bool source_normals) {
+  return first_refusal({
+      {form == kScorePlane && !target_normals, "form PLANE needs normals of the current target in the context (svnicp_set_target_normals, or a registration that estimated them)"},
+      {form == kScoreGicp && !target_normals, "form GICP needs normals of the current target in the context (svnicp_set_target_normals, or a registration that estimated them)"},
+      {form == kScoreGicp && !source_normals, "form GICP needs normals of the current source in the context (svnicp_set_source_normals, or a registration in generalized-ICP mode that estimated them)"},
+  });
+}
+// weighting the particle set at the end of a registration (nullptr: nothing, or the weights are uniform).  The setters
+// themselves refuse a non-finite or non-positive max_corr_dist or temperature.
 inline const char* weighting_refusal(const RegistrationFacts& f, const Tuning& t) {
   if (f.weighting == 0) return nullptr;
   if (f.weighting != 1) return "unknown weighting kind";
   if (f.svgd) return "SVGD mode: the weight option belongs to SVNICP's constructor only";
-  return scoring_refusal(f, t);
+  if (const char* why = scoring_refusal(f, t)) return why;
+  return score_normals_refusal(f.weighting_form, f.target_normals, f.source_normals);
 }
 // pose prior: what it is not combined with (all left for later).  What passes runs the prior's launch between the sums and the
 // Stein step: small_registration and plan_step keep the two shapes that have no place for it (SmallChain, single_fused) away.

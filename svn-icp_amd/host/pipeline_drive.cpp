@@ -19,7 +19,9 @@
 //      PipelineConfig::seed_grid on with that x / y / yaw grid (1 = the flat grid, > 1 = the coarse-to-fine search), one more line per
 //      seeded scan: "seed <scan>: searched levels nodes_scored fitness_zero cost_zero cost correction[x] [y] [yaw]" with %.17g;
 //      after those, seven more: prior_point_sigma sx sy sz srx sry srz -- prior_point_sigma > 0 turns PipelineConfig::prior_sigma on
-//      with those standard deviations, one more line per registered scan: "prior <scan>: prior_chi2" with %.17g)
+//      with those standard deviations, one more line per registered scan: "prior <scan>: prior_chi2" with %.17g;
+//      after those, three more: weight_dist weight_temperature weight_cost -- weight_dist > 0 turns PipelineConfig::weight_dist /
+//      weight_temperature on, weight_cost point|solved is PipelineConfig::weight_cost)
 // scans.bin : int32 n_scans, then per scan { f64 stamp, int32 n, n x 3 float32 } — with deskew 1 followed by n x f64 point stamps
 // particles : optional f64 [n_scans][6][P] (otherwise the built-in uniform prior sampler)
 // out.bin   : per scan { int32 aligned, f64 pose[12], guess[12], corr[6], var[6], cov[36], int64 B, M, f64 src[3B], tgt[3M], init[6P] }
@@ -69,6 +71,7 @@ int main(int argc, char** argv) {
     cfg.prior_point_sigma = atof(argv[25]);
     cfg.prior_sigma = std::array<double, 6>{atof(argv[26]), atof(argv[27]), atof(argv[28]), atof(argv[29]), atof(argv[30]), atof(argv[31])};
   }
+  if (argc > 34) { cfg.weight_dist = atof(argv[32]); cfg.weight_temperature = atof(argv[33]); cfg.weight_cost = argv[34]; }
   try {
     svnicp::RegistrationPipeline pipe(cfg);
     svnicp::Tap tap;

@@ -1002,6 +1002,9 @@ struct PipelineConfig {  // field names follow the node's parameters (OdometryPi
   double weight_dist = 0.0;    // > 0: every registration ends with one scoring of the particles at this gate and soft-min weights
                                // (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures
   double weight_temperature = 0.0;   // with weight_dist: the soft-min temperature in m^2, > 0
+  std::string weight_cost = "point"; // with weight_dist: "point" = the mean truncated squared point distance (no call changes);
+                                     // "solved" = the residual the registration runs with, plane or generalized-ICP, with the
+                                     // solver's huber_delta and epsilon (svnicp_set_particle_weighting_objective)
   // mode_link_trans >= 0 (with mode_link_rot >= 0): after every registration the particles are grouped into modes
   // (svnicp_particle_modes) in ScanResult::modes; negative (the default) = off, no call is made
   double mode_link_trans = -1.0, mode_link_rot = -1.0;
@@ -1086,6 +1089,9 @@ class RegistrationPipeline {
     if (!(std::isfinite(cfg.weight_dist) && cfg.weight_dist >= 0)) throw std::invalid_argument("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)");
     if (cfg.weight_dist > 0 && !(std::isfinite(cfg.weight_temperature) && cfg.weight_temperature > 0))
       throw std::invalid_argument("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)");
+    if (cfg.weight_cost != "point" && cfg.weight_cost != "solved") throw std::invalid_argument("PipelineConfig: weight_cost must be \"point\" or \"solved\"");
+    if (cfg.weight_cost != "point" && !(cfg.weight_dist > 0))
+      throw std::invalid_argument("PipelineConfig: weight_cost \"solved\" needs weight_dist > 0 (it names the cost of that weighting)");
     if (cfg.information != "off" && cfg.information != "point" && cfg.information != "plane" && cfg.information != "gicp")
       throw std::invalid_argument("PipelineConfig: information must be \"off\", \"point\" or \"plane\"");
     if (cfg.information == "gicp" && !cfg.gicp && cfg.solver.residual != "gicp")
@@ -1200,7 +1206,7 @@ class RegistrationPipeline {
     }
     std::vector<double> src64;
     if (!dprep_) src64 = widen(source);                                                                // ICPUtils.cpp:27-43
-    if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{cfg_.weight_dist > 0, cfg_.weight_dist, cfg_.weight_temperature}, cfg_.device);
+    if (!solver_) solver_ = std::make_unique<SVNICP>(cfg_.solver, init, ParticleWeightOpt{cfg_.weight_dist > 0, cfg_.weight_dist, cfg_.weight_temperature, cfg_.weight_cost}, cfg_.device);
     bool search = (bool)cfg_.seed_grid;
     const double gate = cfg_.seed_gate > 0 ? cfg_.seed_gate : cfg_.map_voxel_size;
     double fitness_zero = -1;

@@ -39,8 +39,10 @@ struct SteinICPParam {  // SVGDICP.h:41-57 (same names and defaults; solver-rele
 
 // SVNICP.h:25-27.  use_weight_mean alone is as inert as in the reference (particle_weight_ stays ones / P); with weight_dist > 0
 // as well (not in the reference) every registration ends with one scoring of the particles at that gate (metres) and soft-min
-// weights of `temperature` (m^2, > 0) that the getters honour (svnicp_hip.h "score and weight the particles")
-struct ParticleWeightOpt { bool use_weight_mean = false; double weight_dist = 0.0; double temperature = 0.0; };
+// weights of `temperature` (m^2, > 0) that the getters honour (svnicp_hip.h "score and weight the particles").  weight_cost:
+// "point" (the mean truncated squared point distance) or "solved": the residual the registration ran with, plane or
+// generalized-ICP, with the solver's own huber_delta and epsilon (svnicp_set_particle_weighting_objective)
+struct ParticleWeightOpt { bool use_weight_mean = false; double weight_dist = 0.0; double temperature = 0.0; std::string weight_cost = "point"; };
 
 class SVGDICP {
  public:
@@ -210,6 +212,28 @@ class SVGDICP {
   void set_particle_weighting(int kind, double max_corr_dist = 0.0, double temperature = 0.0) {
     chk(svnicp_set_particle_weighting(h_, kind, max_corr_dist, temperature));
   }
+  // … in the objective the solver minimised (svnicp_hip.h): form SVNICP_SCORE_*; huber_delta / epsilon 0: the solver's own.
+  // The block is {evaluated, inliers, accepted, sum d2, sum h, cost} in the forms PLANE and GICP
+  static svnicp_score_objective score_objective(int form, double max_corr_dist, double huber_delta = 0.0, double epsilon = 0.0) {
+    svnicp_score_objective o{};
+    o.struct_size = sizeof o; o.form = form; o.max_corr_dist = max_corr_dist; o.huber_delta = huber_delta; o.epsilon = epsilon;
+    return o;
+  }
+  std::vector<double> score_particles_objective(const svnicp_score_objective& obj, std::vector<double>* poses = nullptr) {
+    std::vector<double> o((size_t)P_ * SVNICP_SCORE_FIELDS);
+    if (poses) poses->assign((size_t)P_ * 12, 0.0);
+    chk(svnicp_score_particles_objective(h_, &obj, o.data(), poses ? poses->data() : nullptr));
+    return o;
+  }
+  void set_particle_weighting_objective(int kind, const svnicp_score_objective& obj, double temperature) {
+    chk(svnicp_set_particle_weighting_objective(h_, kind, &obj, temperature));
+  }
+  svnicp_score_objective get_score_objective() {   // the resolved objective of the last scoring
+    svnicp_score_objective o{};
+    o.struct_size = sizeof o;
+    chk(svnicp_get_score_objective(h_, &o));
+    return o;
+  }
   // particle modes (svnicp_hip.h "particle modes"): the connected components of the particles' link graph, heaviest first, with
   // mass, mean, covariance, total pose and best-scored member.  particles6xP == nullptr: the last registration's set with its
   // weights; else a host [6][P] block of the caller's (no registration needed) with weightsP [P] or equal weights
@@ -248,7 +272,10 @@ class SVNICP final : public SVGDICP {
  public:
   SVNICP(const SteinICPParam& p, const std::vector<double>& init_pose, const ParticleWeightOpt& w = {}, int device = 0)
       : SVGDICP(p, init_pose, device, SVNICP_MODE_SVN) {
-    if (w.use_weight_mean && w.weight_dist > 0) set_particle_weighting(SVNICP_WEIGHT_SOFTMIN, w.weight_dist, w.temperature);
+    if (!(w.use_weight_mean && w.weight_dist > 0)) return;
+    if (w.weight_cost == "point") set_particle_weighting(SVNICP_WEIGHT_SOFTMIN, w.weight_dist, w.temperature);
+    else if (w.weight_cost == "solved") set_particle_weighting_objective(SVNICP_WEIGHT_SOFTMIN, score_objective(SVNICP_SCORE_AS_SOLVED, w.weight_dist), w.temperature);
+    else throw std::invalid_argument("ParticleWeightOpt: weight_cost must be \"point\" or \"solved\"");
   }
 };
 

@@ -1410,6 +1410,7 @@ class PipelineConfig:
     info_huber: float = float("inf")   # with information: its Huber delta (+inf = unweighted)
     weight_dist: float = 0.0       # > 0: every registration ends with one scoring of the particles at this gate and soft-min weights (svnicp_set_particle_weighting): correction, variance, cov and weights are the weighted figures; 0 = off, the reference's equal weights
     weight_temperature: float = 0.0   # with weight_dist: the soft-min temperature in m^2, > 0
+    weight_cost: str = "point"     # with weight_dist: "point" = the mean truncated squared point distance (no call changes); "solved" = the residual the registration runs with, plane or generalized-ICP, with the solver's huber_delta and epsilon (svnicp_set_particle_weighting_objective)
     map_normals: bool = False      # with gpu_map and solver.residual == "plane" or "gicp" (whose source normals stay the solver's own pass): the target's normals come from the map's own voxels (svnicp_map_query_normals) instead of the solver's pass over the target
     mode_link: tuple | None = None  # (link_trans m, link_rot rad): after every registration the particles are grouped into modes (svnicp_particle_modes) in ScanResult.modes; None = off, no call is made
     mode_max: int = 8              # with mode_link: modes reported in full (1..32)
@@ -1486,6 +1487,10 @@ class PipelineConfig:
             raise ValueError("PipelineConfig: weight_dist must be finite and >= 0 (0 = equal weights)")
         if self.weight_dist > 0 and not (np.isfinite(self.weight_temperature) and self.weight_temperature > 0):
             raise ValueError("PipelineConfig: weight_dist > 0 needs a finite weight_temperature > 0 (m^2)")
+        if self.weight_cost not in ("point", "solved"):
+            raise ValueError('PipelineConfig: weight_cost must be "point" or "solved"')
+        if self.weight_cost != "point" and not self.weight_dist > 0:
+            raise ValueError('PipelineConfig: weight_cost "solved" needs weight_dist > 0 (it names the cost of that weighting)')
         if self.information not in ("off", "point", "plane", "gicp"):
             raise ValueError('PipelineConfig: information must be "off", "point" or "plane"')
         if self.information == "gicp" and self.solver.residual != "gicp":
@@ -1667,7 +1672,7 @@ class RegistrationPipeline:
             self.poses.append(guess); self.times.append(stamp)
             return ScanResult(stamp, guess, guess, preprocessing_s=time.perf_counter() - t0)
         if self._solver is None:
-            self._solver = SVNICP(c.solver, init, ParticleWeightOpt(c.weight_dist > 0, c.weight_dist, c.weight_temperature), device=self.device)
+            self._solver = SVNICP(c.solver, init, ParticleWeightOpt(c.weight_dist > 0, c.weight_dist, c.weight_temperature, c.weight_cost), device=self.device)
         s = self._solver
         seed = None
         if c.seed_grid is not None:

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 
 import numpy as np
 
@@ -65,10 +65,16 @@ class ParticleWeightOpt:  # include/core/SVNICP.h:25-27
     (SVNICP.cpp:32, :46).  With ``weight_dist > 0`` as well (not in the reference) every registration of an ``SVNICP`` ends
     with one scoring of the particles at the gate ``weight_dist`` (metres) and soft-min weights of temperature
     ``temperature`` (m^2, > 0), which get_transformation / get_distribution / get_cov_matrix / get_particle_weight then
-    honour (include/svnicp_hip.h, "score and weight the particles")."""
+    honour (include/svnicp_hip.h, "score and weight the particles").  ``weight_cost``: "point" (the mean truncated squared
+    point distance) or "solved": the residual the registration ran with, plane or generalized-ICP, with the solver's own
+    huber_delta and epsilon ("score and weight the particles in the objective the solver minimised")."""
     use_weight_mean: bool = False
     weight_dist: float = 0.0
     temperature: float = 0.0
+    weight_cost: InitVar[str] = "point"   # an attribute, not one of the reference's three fields (fields() / asdict() keep those)
+
+    def __post_init__(self, weight_cost):
+        self.weight_cost = weight_cost
 
 
 @dataclass
@@ -79,8 +85,23 @@ class ParticleScores:
     plane_inliers: np.ndarray  # [P] inliers whose winner has a normal (0 without normals)
     sum_d2: np.ndarray         # [P] over the inliers
     sum_r2: np.ndarray         # [P] over the plane inliers
-    cost: np.ndarray           # [P] (sum_d2 + (B - inliers) * max_corr_dist^2) / B
+    cost: np.ndarray           # [P] (sum_d2 + (B - inliers) * max_corr_dist^2) / B; forms "plane", "gicp": (sum_h + (B - accepted) * h(max_corr_dist)) / B
     poses: np.ndarray          # [P, 3, 4] the total poses that were scored, [R | t]
+    # The objective that was scored (svnicp_get_score_objective: resolved, never "solved"): attributes, not fields of the block.
+    # In the forms "plane" and "gicp" fields 2 and 4 of the block are the accepted pairs and sum h: accepted / sum_h name them
+    # (the same arrays as plane_inliers / sum_r2; at huber_delta = inf the plane form's equal the point form's bit for bit)
+    form = "point"             # "point" | "plane" | "gicp"
+    max_corr_dist = 0.0
+    huber_delta = 0.0          # as used; 0 in the point form
+    gicp_epsilon = 0.0         # as used; 0 unless the form is "gicp"
+
+    @property
+    def accepted(self) -> np.ndarray:
+        return self.plane_inliers
+
+    @property
+    def sum_h(self) -> np.ndarray:
+        return self.sum_r2
 
 
 @dataclass
@@ -269,7 +290,7 @@ class _SolverBase:
             self.set_residual(parameters.residual, float(parameters.huber_delta), int(parameters.normal_k), float(parameters.gicp_epsilon))
         w = self.weight_config
         if self._mode == 0 and w.use_weight_mean and w.weight_dist > 0:   # the option belongs to SVNICP's constructor only
-            self.set_particle_weighting("softmin", float(w.weight_dist), float(w.temperature))
+            self.set_particle_weighting("softmin", float(w.weight_dist), float(w.temperature), cost=w.weight_cost)
 
     # -- plumbing -------------------------------------------------------------------------
     @staticmethod
@@ -610,23 +631,57 @@ class _SolverBase:
     # -- score and weight the particles (include/svnicp_hip.h "score and weight the particles") -------------------------------
     _WEIGHTING = {"uniform": 0, "softmin": 1}
 
-    def set_particle_weighting(self, kind="uniform", max_corr_dist: float = 0.0, temperature: float = 0.0) -> None:
+    _SCORE_FORM = {"solved": binding.SCORE_AS_SOLVED, "point": binding.SCORE_POINT, "plane": binding.SCORE_PLANE, "gicp": binding.SCORE_GICP}
+
+    def _objective(self, form, max_corr_dist, huber_delta=None, gicp_epsilon=None) -> "binding.ScoreObjectiveStruct":
+        if form not in self._SCORE_FORM and not isinstance(form, int):
+            raise ValueError(f"form must be one of {sorted(self._SCORE_FORM)}")
+        return binding.ScoreObjectiveStruct(C.sizeof(binding.ScoreObjectiveStruct), int(self._SCORE_FORM.get(form, form)), float(max_corr_dist),
+                                            0.0 if huber_delta is None else float(huber_delta), 0.0 if gicp_epsilon is None else float(gicp_epsilon))
+
+    def set_particle_weighting(self, kind="uniform", max_corr_dist: float = 0.0, temperature: float = 0.0, cost="point",
+                               huber_delta=None, gicp_epsilon=None) -> None:
         """"uniform" (the reference) or "softmin": every following registration ends with one scoring at ``max_corr_dist``
-        and the weights exp(-(cost - cost_min) / temperature) / Z."""
+        and the weights exp(-(cost - cost_min) / temperature) / Z.  ``cost``: "point" (svnicp_set_particle_weighting), or
+        "plane" | "gicp" | "solved" (svnicp_set_particle_weighting_objective; ``huber_delta`` / ``gicp_epsilon`` None: the
+        solver's own)."""
         k = self._WEIGHTING.get(kind, kind)
-        self._check(self._L.svnicp_set_particle_weighting(self._h, int(k), float(max_corr_dist), float(temperature)),
-                    "svnicp_set_particle_weighting")
+        if cost == "point":
+            self._check(self._L.svnicp_set_particle_weighting(self._h, int(k), float(max_corr_dist), float(temperature)),
+                        "svnicp_set_particle_weighting")
+            return
+        obj = self._objective(cost, max_corr_dist, huber_delta, gicp_epsilon)
+        self._check(self._L.svnicp_set_particle_weighting_objective(self._h, int(k), C.byref(obj), float(temperature)),
+                    "svnicp_set_particle_weighting_objective")
+
+    def get_score_objective(self) -> "binding.ScoreObjectiveStruct":
+        """The resolved objective of the last scoring (svnicp_get_score_objective)."""
+        obj = binding.ScoreObjectiveStruct(C.sizeof(binding.ScoreObjectiveStruct))
+        self._check(self._L.svnicp_get_score_objective(self._h, C.byref(obj)), "svnicp_get_score_objective")
+        return obj
 
     def _scores(self, out: np.ndarray, poses: np.ndarray) -> ParticleScores:
-        return ParticleScores(out[:, 0].astype(np.int64), out[:, 1].astype(np.int64), out[:, 2].astype(np.int64),
-                              out[:, 3].copy(), out[:, 4].copy(), out[:, 5].copy(), poses_3x4(poses))
+        o = self.get_score_objective()
+        form = {v: k for k, v in self._SCORE_FORM.items()}[int(o.form)]
+        sc = ParticleScores(out[:, 0].astype(np.int64), out[:, 1].astype(np.int64), out[:, 2].astype(np.int64),
+                            out[:, 3].copy(), out[:, 4].copy(), out[:, 5].copy(), poses_3x4(poses))
+        sc.form, sc.max_corr_dist, sc.huber_delta, sc.gicp_epsilon = form, float(o.max_corr_dist), float(o.huber_delta), float(o.epsilon)
+        return sc
 
-    def score_particles(self, max_corr_dist: float) -> ParticleScores:
-        """Score every particle's final pose through the registration's candidate table at the gate ``max_corr_dist``."""
+    def score_particles(self, max_corr_dist: float, form="point", huber_delta=None, gicp_epsilon=None) -> ParticleScores:
+        """Score every particle's final pose through the registration's candidate table at the gate ``max_corr_dist``.
+        ``form``: "point" (svnicp_score_particles, the default), or "plane" | "gicp" | "solved": the Huber-weighted plane or
+        generalized-ICP residual, or whichever the registration ran with (svnicp_score_particles_objective); ``huber_delta``
+        and ``gicp_epsilon`` None: the solver's own."""
         out, poses = np.zeros((self._P, 6), np.float64), np.zeros((self._P, 12), np.float64)
         dp = C.POINTER(C.c_double)
-        self._check(self._L.svnicp_score_particles(self._h, float(max_corr_dist), out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
-                    "svnicp_score_particles")
+        if form == "point" and huber_delta is None and gicp_epsilon is None:
+            self._check(self._L.svnicp_score_particles(self._h, float(max_corr_dist), out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
+                        "svnicp_score_particles")
+            return self._scores(out, poses)
+        obj = self._objective(form, max_corr_dist, huber_delta, gicp_epsilon)
+        self._check(self._L.svnicp_score_particles_objective(self._h, C.byref(obj), out.ctypes.data_as(dp), poses.ctypes.data_as(dp)),
+                    "svnicp_score_particles_objective")
         return self._scores(out, poses)
 
     def get_particle_scores(self) -> ParticleScores:
